@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: EKS particle-updates/s (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path -- K1 moments, the all-reduce, K2 small
@@ -15,6 +15,13 @@ Frobenius time step), i.e. weak scaling; N = 8 is config C3.  Inputs are in HBM
 before the timed region; a ring of 4 distinct batches (537 MB > the 256 MB
 Infinity Cache) is cycled so that no step re-reads a cache-resident batch.
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs: set-up, pre-warm, W warm-up steps, the K timed
+steps (`value`, `ms_per_step`), the outputs of the last one if --dump-outputs is given, the
+line.  ``--full`` adds the rest, none of it `value`: HIP-event-sampled kernel times and the
+roofline, the clocks and a bare-MFMA calibration, parity against the oracle, the other
+configurations, rules and end-to-end rates (``--no-extras`` skips them), the one-rank
+sharded legs and the numpy CPU baselines (``--no-cpu-baseline`` skips them).
 
 ``python bench.py --gpus N`` without a launcher starts the N ranks itself (a child
 ``python -m torch.distributed.run`` started BEFORE this process touches the GPU) and relays
@@ -583,8 +590,8 @@ def sharded_helper_main():
             env["MASTER_PORT"] = str(sk.getsockname()[1])
         env["MASTER_ADDR"] = "127.0.0.1"
         try:
-            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-extras", "--no-cpu-baseline", "--steps", "20",
-                                  "--warmup", "3"], env=env, capture_output=True, text=True, timeout=240)
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--no-cpu-baseline", "--steps",
+                                  "20", "--warmup", "3"], env=env, capture_output=True, text=True, timeout=240)
             line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
             d = json.loads(line[-1])
             out[key] = dict(value=d["value"], ms_per_step=d["ms_per_step"], ms_per_step_median=d["ms_per_step_median"],
@@ -683,6 +690,27 @@ def cpu_baseline_small(p, n, J, mu, sigma, ustar, y, U0, G0, Gamma, reps=5):
     return round(float(np.median(tl)) * 1e3, 3)
 
 
+RESULT_FIELDS = ("hk", "t_new", "self_bias", "self_bias_data", "bias_data", "bias", "radspec", "lag_bias_data",
+                 "lag_self_bias_data")
+DUMP_BYTES, DUMP_SEED = 32 << 20, 20242
+
+
+def dump_outputs(path, out, res):
+    """``--dump-outputs DIR``: what the last timed step handed its caller -- the new ensemble (p x J in the engine's
+    dtype; rank 0's shard on more than one GPU) as ``U_next.npy`` and every number of the step result as a float64
+    ``<field>.npy``.  An ensemble above DUMP_BYTES is written as a fixed sample of its columns (DUMP_SEED, sorted): the
+    same columns in every run, so that two builds can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    U = out.detach().cpu().numpy()
+    assert U.dtype in (np.float32, np.float64), U.dtype
+    if U.nbytes > DUMP_BYTES:
+        k = DUMP_BYTES // (U.shape[0] * U.itemsize)
+        U = U[:, np.sort(np.random.default_rng(DUMP_SEED).choice(U.shape[1], k, replace=False))]
+    np.save(os.path.join(path, "U_next.npy"), np.ascontiguousarray(U))
+    for name in RESULT_FIELDS:
+        np.save(os.path.join(path, name + ".npy"), np.array(getattr(res, name), dtype=np.float64))
+
+
 def self_launch(args):
     """No launcher (WORLD_SIZE unset) and --gpus N > 1: start the N ranks as children of this process, which
     has not touched the GPU, relay their output, exit with their status."""
@@ -709,9 +737,17 @@ def main():
     ap.add_argument("--update", default="aldi")
     ap.add_argument("--config", default="C2", choices=["C2", "C5"],
                     help="C2: fp32, p=n=256, J=65536/GPU (headline); C5: fp64, p=n=512, J=32768/GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip parity_err and the e2e block")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: HIP-event-sampled kernel times and the roofline, "
+                         "the clocks and a bare-MFMA calibration, parity_err, the other configurations and rules, the "
+                         "one-rank sharded legs, the e2e block and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip parity_err, the other configurations and the e2e block")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config == "C5":
         args.J, args.p, args.n, args.dtype = 32768, 512, 512, "float64"
 
@@ -728,7 +764,7 @@ def main():
     # The one-rank rehearsal of the sharded path (`extra.sharded_one_rank`) runs in fresh processes; their launcher is
     # started HERE, before this process touches the GPU, and sleeps on a pipe until the headline is measured.
     helper = None
-    if (world == 1 and not rehearse and not args.no_extras and args.config == "C2" and plat.backend == "nccl"
+    if (world == 1 and not rehearse and args.full and not args.no_extras and args.config == "C2" and plat.backend == "nccl"
             and os.environ.get("CESX_BENCH_NO_SHARDED_LEG") != "1"):
         try:
             helper = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--sharded-helper"], stdin=subprocess.PIPE,
@@ -786,6 +822,7 @@ def main():
         G = eng.forward_lineal(prob["A"], U)
         batches.append((U, G))
     out = eng.empty(p)
+    u_next = [out]                  # the new ensemble the last finish() returned (the engine's: `out` itself)
     plat.sync()
 
     t_hist = [0.0]
@@ -823,7 +860,7 @@ def main():
             prof["steps"] += int(i == prof["at"])
         prm = engine.step_params(update=args.update, first_step=(i == 0), t_len=min(i, 1), t_last=t_hist[0],
                                  step_index=i)
-        sh.finish(prm, U, G, xi=None, out=out)
+        u_next[0] = sh.finish(prm, U, G, xi=None, out=out)
 
     stamps = []
     sclk_probe = dict(at=-1, val=None)          # read sysfs sclk at this step of an UNTIMED run: the GPU is busy then
@@ -855,9 +892,10 @@ def main():
     import gc
     gc.collect()
     gc.disable()                                # no collector pause inside the timed region (a few hundred us each)
-    eng.profile_enable(True)                    # creates the event pool outside the timed region
-    eng.profile_enable(False)
-    prof["on"] = not os.environ.get("CESX_BENCH_NOPROF")
+    if args.full:
+        eng.profile_enable(True)                # creates the event pool outside the timed region
+        eng.profile_enable(False)
+    prof["on"] = args.full and not os.environ.get("CESX_BENCH_NOPROF")
     prewarm_min_s = float(os.environ.get("CESX_BENCH_PREWARM_S", "2.0"))
     prewarm, win_ms, t_pre = 0, [], time.perf_counter()
     WIN = 512
@@ -922,7 +960,7 @@ def main():
         pre_k1, pre_k3 = eng.profile_read(0), eng.profile_read(1)
         sh.read_collective_ms()
     prof["at"], prof["gap_at"] = -1, -2
-    sclk_probe["at"] = 32
+    sclk_probe["at"] = 32 if args.full else -1
     run_steps(0, 64)                            # (the reads above idled the GPU for a moment: back to work first)
     sclk_before, sclk_probe["at"] = sclk_probe["val"], -1
     if args.warmup:
@@ -944,143 +982,148 @@ def main():
     elapsed = time.perf_counter() - t0
     gc.enable()
     per_step = np.diff(np.array([t0] + stamps)) * 1e3       # ms between consecutive results (pipelined loop)
-    prof["on"] = False
-    eng.profile_enable(False)
-    # the clock the sampled K3 launch ran at (in-kernel s_memtime / s_memrealtime), a bare-MFMA calibration of this
-    # device right behind the timed region, and the sysfs sclk samples around it
-    sh.sample_collectives = False
-    coll_ms = sh.read_collective_ms()
-    gap_ms = pre_gap                                            # end of the second Gram launch -> start of K3 (untimed sample)
-    k3_clock = eng.profile_clock() if prof["steps"] else None
-    calib_tf, calib_ghz = eng.calibrate_mfma(5.0)
-    k3_form = eng.update_form()          # 0 assembled / 1 hk-free / 2 through the Cholesky factor (include/cesx.h)
-    sclk_probe["at"] = args.warmup + args.steps + 16
-    run_steps(args.warmup + args.steps, 32)     # (untimed: the same steps again, the sysfs clock read while they run)
-    plat.sync()
-    sclk_after, sclk_probe["at"] = sclk_probe["val"], -1
+    if args.dump_outputs and rank == 0:                     # (before any later step overwrites `out`)
+        dump_outputs(args.dump_outputs, u_next[0], res)
+    if args.full:
+        prof["on"] = False
+        eng.profile_enable(False)
+        # the clock the sampled K3 launch ran at (in-kernel s_memtime / s_memrealtime), a bare-MFMA calibration of this
+        # device right behind the timed region, and the sysfs sclk samples around it
+        sh.sample_collectives = False
+        coll_ms = sh.read_collective_ms()
+        gap_ms = pre_gap                                        # end of the second Gram launch -> start of K3 (untimed sample)
+        k3_clock = eng.profile_clock() if prof["steps"] else None
+        calib_tf, calib_ghz = eng.calibrate_mfma(5.0)
+        k3_form = eng.update_form()      # 0 assembled / 1 hk-free / 2 through the Cholesky factor (include/cesx.h)
+        sclk_probe["at"] = args.warmup + args.steps + 16
+        run_steps(args.warmup + args.steps, 32)     # (untimed: the same steps again, the sysfs clock read while they run)
+        plat.sync()
+        sclk_after, sclk_probe["at"] = sclk_probe["val"], -1
     if world > 1:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    if not np.isfinite(res.hk) or not bool(torch.isfinite(out).all()):
+    if not np.isfinite(res.hk) or not bool(torch.isfinite(u_next[0]).all()):
         raise SystemExit("non-finite result in the timed region")
 
-    gram_ms, gram_cnt = eng.profile_read(0)
-    upd_ms, upd_cnt = eng.profile_read(1)
-    where = {"gram_kernel(K1)": "timed region", "update_kernel(K3)": "timed region"}
-    if prof["steps"]:                           # the kernel that was not sampled inside the timed region: its untimed sample
-        if dom_is_k3:
-            gram_ms, gram_cnt = pre_k1[0] * prof["steps"], pre_k1[1] * prof["steps"]
-            where["gram_kernel(K1)"] = "untimed step right before the warm-up steps"
-        else:
-            upd_ms, upd_cnt = pre_k3[0] * prof["steps"], pre_k3[1] * prof["steps"]
-            where["update_kernel(K3)"] = "untimed step right before the warm-up steps"
+    if args.full:
+        gram_ms, gram_cnt = eng.profile_read(0)
+        upd_ms, upd_cnt = eng.profile_read(1)
+        where = {"gram_kernel(K1)": "timed region", "update_kernel(K3)": "timed region"}
+        if prof["steps"]:                       # the kernel that was not sampled inside the timed region: its untimed sample
+            if dom_is_k3:
+                gram_ms, gram_cnt = pre_k1[0] * prof["steps"], pre_k1[1] * prof["steps"]
+                where["gram_kernel(K1)"] = "untimed step right before the warm-up steps"
+            else:
+                upd_ms, upd_cnt = pre_k3[0] * prof["steps"], pre_k3[1] * prof["steps"]
+                where["update_kernel(K3)"] = "untimed step right before the warm-up steps"
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
         return
 
-    # algorithmic flops per launch: symmetric-aware Gram of the stacked
-    # anomaly (p+n)^2 per particle; fused update GEMM 2 p (2p+n) per particle
-    nprof = max(prof["steps"], 1)
-    kern = {
-        # per step: K1 is two launches (U x U blocks, then the rest beside the Cholesky), K3 one
-        # (two for aldi_constant) -- the durations of a step's launches are summed
-        "gram_kernel(K1)": dict(ms=gram_ms / nprof, flops=float(p + n) ** 2 * J, launches=gram_cnt / nprof),
-        "update_kernel(K3)": dict(ms=upd_ms / nprof, flops=k3_flops_algorithmic(p, n, J, k3_form), launches=upd_cnt / nprof),
-    }
-    # ... and what the matrix pipe really issues (triangular-aware, block-granular: flops_executed)
-    kern["gram_kernel(K1)"]["flops_executed"], kern["update_kernel(K3)"]["flops_executed"] = flops_executed(p, n, J, args.dtype, k3_form)
-    for k in kern.values():
-        k["tflops"] = k["flops"] / (k["ms"] * 1e-3) / 1e12 if k["ms"] > 0 else 0.0
-        k["tflops_executed"] = k["flops_executed"] / (k["ms"] * 1e-3) / 1e12 if k["ms"] > 0 else 0.0
-    dom = max(kern, key=lambda k: kern[k]["ms"])
-    peak = MFMA_PEAK_TF[np.dtype(args.dtype).name]
     dname = np.dtype(args.dtype).name
     is_c2 = (p, n, J, dname, args.update) == (256, 256, 65536, "float32", "aldi")
     is_c5 = (p, n, J, dname, args.update) == (512, 512, 32768, "float64", "aldi")
     cfg_name = "C2" if is_c2 else "C5" if is_c5 else "custom"
-    # HBM bytes per step of each kernel from the rocprofv3 PMC passes (profiles/traffic.json, taken on the
-    # named config with tools/prof_summary.py; collected in separate --pmc runs as the guide prescribes)
-    traffic_tab, traffic_stale = {}, None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath) and cfg_name != "custom":
-        try:
-            tj = json.load(open(tpath))
-            traffic_tab = tj.get(cfg_name, tj if cfg_name == "C2" and "gram_kernel" in tj else {})
-        except Exception:
-            traffic_tab = {}
-        # counters of ANOTHER build of the kernels are not this line's traffic: the table carries the hash of the
-        # kernel sources its profile ran from (tools/prof_summary.py), compared with the tree this run uses
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            from prof_summary import kernel_sources_sha
-            have, want = traffic_tab.get("_src_sha16"), kernel_sources_sha()
-            if traffic_tab and have != want:
-                traffic_stale = ("profiles/traffic.json[%s] was taken from kernel sources %s (%s), this tree is %s: refused"
-                                 % (cfg_name, have, traffic_tab.get("_source", "?"), want))
-                traffic_tab = {}
-        except Exception as ex:
-            traffic_stale, traffic_tab = "traffic.json could not be checked against the kernel sources (%r): refused" % (ex,), {}
-    k3name = "update4_kernel" if k3_form == 2 else "update2_kernel" if dname == "float32" else ("update3_kernel" if "update3_kernel" in traffic_tab else "update_kernel")
-    tkey = {"gram_kernel(K1)": "gram_kernel", "update_kernel(K3)": k3name}
-    traffic = traffic_tab.get(tkey[dom])
     step_s = elapsed / args.steps
-    esz = np.dtype(args.dtype).itemsize
-    alg_bytes = float(esz * (3 * p + 2 * n)) * J               # s (3p + 2n) per particle-update
-    traffic_source = traffic_stale
-    if traffic_tab:
-        traffic_source = ("profiles/traffic.json[%s] <- profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an "
-                          "EARLIER run of this configuration (2 x FETCH + WRITE, the guide's gfx950 correction), not "
-                          "counters of this run" % (cfg_name, traffic_tab.get("_source", "?")))
-    counter_bytes = (float(sum(v for k, v in traffic_tab.items() if not k.startswith("_") and isinstance(v, (int, float))
-                               # (aliases, the set-up's forward map and the first step's recentring pass are not per step)
-                               and k not in ("gram_kernel", "update_kernel", "colsum_final_kernel", "rowsum_kernel",
-                                             "set_shift_kernel")))
-                     if traffic_tab else None)
-    mfma_util_tab = traffic_tab.get("_mfma_util", {}) if traffic_tab else {}
-    roofline = dict(bound="mfma", kernel=dom, achieved=round(kern[dom]["tflops"], 2), peak=peak,
-                    unit="TFLOP/s", frac=round(kern[dom]["tflops"] / peak, 4), traffic=traffic,
-                    traffic_source=traffic_source,
-                    # `frac` prices the ALGORITHMIC flops of SURVEY.md 8(d) (K3: 2 p (2p + n) J -- the zero blocks of the
-                    # triangular sqrt(2hk) L segment included, which the kernel skips); what the hardware did:
-                    #   frac_executed  flops the kernel really issues / its time / peak
-                    #   mfma_util      SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs), PMC passes of an earlier
-                    #                  run of this configuration (profiles/traffic.json, same source as `traffic`)
-                    frac_executed=round(kern[dom]["tflops_executed"] / peak, 4),
-                    mfma_util=mfma_util_tab.get(tkey[dom]),
-                    calibration=dict(tflops=round(calib_tf, 2), clock_ghz=round(calib_ghz, 4),
-                                     frac_of_calibration=round(kern[dom]["tflops"] / calib_tf, 4) if calib_tf > 0 else None,
-                                     what="bare %s loop (operands in registers, 4 accumulators per wave, 2 x 256 threads "
-                                          "per CU, random operands), ~5 ms, launched right behind the timed region"
-                                          % ("v_mfma_f32_32x32x2_f32" if dname == "float32" else "v_mfma_f64_16x16x4_f64")),
-                    avg_launch_ms=round(kern[dom]["ms"], 4), profiled_steps=prof["steps"],
-                    kernels={k: dict(avg_launch_ms=round(v["ms"], 4), launches_per_step=v["launches"],
-                                     tflops=round(v["tflops"], 2), frac=round(v["tflops"] / peak, 4),
-                                     flops=v["flops"], flops_executed=v["flops_executed"],
-                                     **({"flops_survey_8d": 2.0 * p * (2 * p + n) * J, "update_form": k3_form,
-                                         "flops_note": "K3 through the Cholesky factor: the algorithm needs 2 p (p + 1) + 2 p n flops per "
-                                                       "particle (two triangular products + the gain term), not SURVEY 8(d)'s 2 p (2p + n)"}
-                                        if k == "update_kernel(K3)" and k3_form == 2 else {}),
-                                     frac_executed=round(v["tflops_executed"] / peak, 4),
-                                     mfma_util=mfma_util_tab.get(tkey[k]),
-                                     sampled=where[k],
-                                     traffic=traffic_tab.get(tkey[k]),
-                                     hbm_gbs=(round(traffic_tab[tkey[k]] / (v["ms"] * 1e-3) / 1e9, 1)
-                                              if traffic_tab.get(tkey[k]) and v["ms"] > 0 else None))
-                             for k, v in kern.items()},
-                    step_flops_frac=round(sum(v["flops"] for v in kern.values()) / step_s / 1e12 / peak, 4),
-                    step_flops_executed_frac=round(sum(v["flops_executed"] for v in kern.values()) / step_s / 1e12 / peak, 4),
-                    # the other roofline the north star asks for: HBM bytes (PMC counters) / kernel time / 8 TB/s
-                    hbm_gbs=(round(traffic / (kern[dom]["ms"] * 1e-3) / 1e9, 1) if traffic and kern[dom]["ms"] > 0 else None),
-                    hbm_frac=(round(traffic / (kern[dom]["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                              if traffic and kern[dom]["ms"] > 0 else None),
-                    hbm_peak_gbs=HBM_PEAK_GBS,
-                    step_algorithmic_bytes=alg_bytes,
-                    # every kernel of a step by the same counters (incl. the xi block's write + read and the Gram's
-                    # slab round trip): what the step really moves, from the same earlier PMC run as `traffic`
-                    step_counter_bytes=counter_bytes,
-                    step_algorithmic_hbm_frac=round(alg_bytes / step_s / 1e9 / HBM_PEAK_GBS, 4))
+    if args.full:
+        # algorithmic flops per launch: symmetric-aware Gram of the stacked
+        # anomaly (p+n)^2 per particle; fused update GEMM 2 p (2p+n) per particle
+        nprof = max(prof["steps"], 1)
+        kern = {
+            # per step: K1 is two launches (U x U blocks, then the rest beside the Cholesky), K3 one
+            # (two for aldi_constant) -- the durations of a step's launches are summed
+            "gram_kernel(K1)": dict(ms=gram_ms / nprof, flops=float(p + n) ** 2 * J, launches=gram_cnt / nprof),
+            "update_kernel(K3)": dict(ms=upd_ms / nprof, flops=k3_flops_algorithmic(p, n, J, k3_form), launches=upd_cnt / nprof),
+        }
+        # ... and what the matrix pipe really issues (triangular-aware, block-granular: flops_executed)
+        kern["gram_kernel(K1)"]["flops_executed"], kern["update_kernel(K3)"]["flops_executed"] = flops_executed(p, n, J, args.dtype, k3_form)
+        for k in kern.values():
+            k["tflops"] = k["flops"] / (k["ms"] * 1e-3) / 1e12 if k["ms"] > 0 else 0.0
+            k["tflops_executed"] = k["flops_executed"] / (k["ms"] * 1e-3) / 1e12 if k["ms"] > 0 else 0.0
+        dom = max(kern, key=lambda k: kern[k]["ms"])
+        peak = MFMA_PEAK_TF[np.dtype(args.dtype).name]
+        # HBM bytes per step of each kernel from the rocprofv3 PMC passes (profiles/traffic.json, taken on the
+        # named config with tools/prof_summary.py; collected in separate --pmc runs as the guide prescribes)
+        traffic_tab, traffic_stale = {}, None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath) and cfg_name != "custom":
+            try:
+                tj = json.load(open(tpath))
+                traffic_tab = tj.get(cfg_name, tj if cfg_name == "C2" and "gram_kernel" in tj else {})
+            except Exception:
+                traffic_tab = {}
+            # counters of ANOTHER build of the kernels are not this line's traffic: the table carries the hash of the
+            # kernel sources its profile ran from (tools/prof_summary.py), compared with the tree this run uses
+            try:
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                from prof_summary import kernel_sources_sha
+                have, want = traffic_tab.get("_src_sha16"), kernel_sources_sha()
+                if traffic_tab and have != want:
+                    traffic_stale = ("profiles/traffic.json[%s] was taken from kernel sources %s (%s), this tree is %s: refused"
+                                     % (cfg_name, have, traffic_tab.get("_source", "?"), want))
+                    traffic_tab = {}
+            except Exception as ex:
+                traffic_stale, traffic_tab = "traffic.json could not be checked against the kernel sources (%r): refused" % (ex,), {}
+        k3name = "update4_kernel" if k3_form == 2 else "update2_kernel" if dname == "float32" else ("update3_kernel" if "update3_kernel" in traffic_tab else "update_kernel")
+        tkey = {"gram_kernel(K1)": "gram_kernel", "update_kernel(K3)": k3name}
+        traffic = traffic_tab.get(tkey[dom])
+        esz = np.dtype(args.dtype).itemsize
+        alg_bytes = float(esz * (3 * p + 2 * n)) * J               # s (3p + 2n) per particle-update
+        traffic_source = traffic_stale
+        if traffic_tab:
+            traffic_source = ("profiles/traffic.json[%s] <- profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an "
+                              "EARLIER run of this configuration (2 x FETCH + WRITE, the guide's gfx950 correction), not "
+                              "counters of this run" % (cfg_name, traffic_tab.get("_source", "?")))
+        counter_bytes = (float(sum(v for k, v in traffic_tab.items() if not k.startswith("_") and isinstance(v, (int, float))
+                                   # (aliases, the set-up's forward map and the first step's recentring pass are not per step)
+                                   and k not in ("gram_kernel", "update_kernel", "colsum_final_kernel", "rowsum_kernel",
+                                                 "set_shift_kernel")))
+                         if traffic_tab else None)
+        mfma_util_tab = traffic_tab.get("_mfma_util", {}) if traffic_tab else {}
+        roofline = dict(bound="mfma", kernel=dom, achieved=round(kern[dom]["tflops"], 2), peak=peak,
+                        unit="TFLOP/s", frac=round(kern[dom]["tflops"] / peak, 4), traffic=traffic,
+                        traffic_source=traffic_source,
+                        # `frac` prices the ALGORITHMIC flops of SURVEY.md 8(d) (K3: 2 p (2p + n) J -- the zero blocks of the
+                        # triangular sqrt(2hk) L segment included, which the kernel skips); what the hardware did:
+                        #   frac_executed  flops the kernel really issues / its time / peak
+                        #   mfma_util      SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs), PMC passes of an earlier
+                        #                  run of this configuration (profiles/traffic.json, same source as `traffic`)
+                        frac_executed=round(kern[dom]["tflops_executed"] / peak, 4),
+                        mfma_util=mfma_util_tab.get(tkey[dom]),
+                        calibration=dict(tflops=round(calib_tf, 2), clock_ghz=round(calib_ghz, 4),
+                                         frac_of_calibration=round(kern[dom]["tflops"] / calib_tf, 4) if calib_tf > 0 else None,
+                                         what="bare %s loop (operands in registers, 4 accumulators per wave, 2 x 256 threads "
+                                              "per CU, random operands), ~5 ms, launched right behind the timed region"
+                                              % ("v_mfma_f32_32x32x2_f32" if dname == "float32" else "v_mfma_f64_16x16x4_f64")),
+                        avg_launch_ms=round(kern[dom]["ms"], 4), profiled_steps=prof["steps"],
+                        kernels={k: dict(avg_launch_ms=round(v["ms"], 4), launches_per_step=v["launches"],
+                                         tflops=round(v["tflops"], 2), frac=round(v["tflops"] / peak, 4),
+                                         flops=v["flops"], flops_executed=v["flops_executed"],
+                                         **({"flops_survey_8d": 2.0 * p * (2 * p + n) * J, "update_form": k3_form,
+                                             "flops_note": "K3 through the Cholesky factor: the algorithm needs 2 p (p + 1) + 2 p n flops per "
+                                                           "particle (two triangular products + the gain term), not SURVEY 8(d)'s 2 p (2p + n)"}
+                                            if k == "update_kernel(K3)" and k3_form == 2 else {}),
+                                         frac_executed=round(v["tflops_executed"] / peak, 4),
+                                         mfma_util=mfma_util_tab.get(tkey[k]),
+                                         sampled=where[k],
+                                         traffic=traffic_tab.get(tkey[k]),
+                                         hbm_gbs=(round(traffic_tab[tkey[k]] / (v["ms"] * 1e-3) / 1e9, 1)
+                                                  if traffic_tab.get(tkey[k]) and v["ms"] > 0 else None))
+                                 for k, v in kern.items()},
+                        step_flops_frac=round(sum(v["flops"] for v in kern.values()) / step_s / 1e12 / peak, 4),
+                        step_flops_executed_frac=round(sum(v["flops_executed"] for v in kern.values()) / step_s / 1e12 / peak, 4),
+                        # the other roofline the north star asks for: HBM bytes (PMC counters) / kernel time / 8 TB/s
+                        hbm_gbs=(round(traffic / (kern[dom]["ms"] * 1e-3) / 1e9, 1) if traffic and kern[dom]["ms"] > 0 else None),
+                        hbm_frac=(round(traffic / (kern[dom]["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                                  if traffic and kern[dom]["ms"] > 0 else None),
+                        hbm_peak_gbs=HBM_PEAK_GBS,
+                        step_algorithmic_bytes=alg_bytes,
+                        # every kernel of a step by the same counters (incl. the xi block's write + read and the Gram's
+                        # slab round trip): what the step really moves, from the same earlier PMC run as `traffic`
+                        step_counter_bytes=counter_bytes,
+                        step_algorithmic_hbm_frac=round(alg_bytes / step_s / 1e9 / HBM_PEAK_GBS, 4))
     if world == 1 and not rehearse:
         par = "dp1: one GPU holds the whole ensemble, no collective is issued"
     elif sh.single_allreduce:
@@ -1100,13 +1143,6 @@ def main():
                prewarm_steps=prewarm, prewarm_s=round(prewarm_s, 3), prewarm_window_ms=[round(w, 4) for w in win_ms],
                rccl_nranks=rccl_nranks,
                rccl_comms=(eng.comm_count() if hasattr(eng, "comm_count") else 0),      # 2: one communicator per stream (include/cesx.h)
-               clock=dict(k3_ghz=round(k3_clock, 4) if k3_clock else None,
-                          k3_how="s_memtime / s_memrealtime of one wave of the last HIP-event-sampled update launch (%s)"
-                                 % where["update_kernel(K3)"],
-                          calibration_ghz=round(calib_ghz, 4), sclk_before=sclk_before, sclk_after=sclk_after,
-                          sclk_how="sysfs pp_dpm_sclk level marked current, read by the host WHILE an untimed run of the "
-                                   "same steps is in flight (an idle GPU reads 100-700 MHz): 32 steps before the warm-up "
-                                   "steps, and 16 steps into a 32-step run behind the timed region and the calibration loop"),
                higher_is_better=True, scaling="weak", vs_baseline=None,
                dtype={"float32": "f32", "float64": "f64"}[dname], data="synthetic",
                config=dict(workload="%s per GPU: synthetic linear-Gaussian forward map, J=%d particles/GPU "
@@ -1116,23 +1152,32 @@ def main():
                            timed_region="the update engine on HBM-resident inputs: K1 moments, (all-reduce), K2, K3 "
                                         "with on-device noise and the host's read of hk / t / metrics of every step. "
                                         "A ring of 4 resident (U, G = A U) batches is cycled; the forward map and the "
-                                        "feedback of U_next are NOT in the timed step (see e2e.device_chain for the "
-                                        "chained loop); %d untimed pre-warm steps (%.1f s) precede the warm-up" % (prewarm, prewarm_s)),
-               roofline=roofline,
+                                        "feedback of U_next are NOT in the timed step (see e2e.device_chain of --full for "
+                                        "the chained loop); %d untimed pre-warm steps (%.1f s) precede the warm-up" % (prewarm, prewarm_s)),
                # what a SCALE line needs to explain its own efficiency (rank 0, the sampled step of the timed region)
-               sampled_step=dict(gram_end_to_k3_start_ms=round(gap_ms, 4) if gap_ms is not None else None,
-                                 collective_mode=("none" if world == 1 and not rehearse else
+               sampled_step=dict(collective_mode=("none" if world == 1 and not rehearse else
                                                   "single" if sh.single_allreduce else "head+tail"),
                                  collectives_per_step=(0 if world == 1 and not rehearse else 1 if sh.single_allreduce else 2),
-                                 mode_choice=mode_choice,
-                                 collective_ms={k: dict(doubles=v[0], ms=round(v[1], 4)) for k, v in coll_ms.items()},
-                                 how="the interval: HIP events of an UNTIMED step of their own right before the warm-up steps "
-                                     "(nothing else time-stamped in it): kernel-bound stop of the second Gram launch -> "
-                                     "kernel-bound start of K3; the collectives: a recorded event pair around each all-reduce of "
-                                     "the timed region's sampled step, on the stream that issues it (the pair itself adds a few "
-                                     "us to that step)"))
-    if world == 1 and not rehearse and not args.no_extras:
-        del batches, out, sh, eng
+                                 mode_choice=mode_choice))
+    if args.full:
+        rec["clock"] = dict(k3_ghz=round(k3_clock, 4) if k3_clock else None,
+                            k3_how="s_memtime / s_memrealtime of one wave of the last HIP-event-sampled update launch (%s)"
+                                   % where["update_kernel(K3)"],
+                            calibration_ghz=round(calib_ghz, 4), sclk_before=sclk_before, sclk_after=sclk_after,
+                            sclk_how="sysfs pp_dpm_sclk level marked current, read by the host WHILE an untimed run of the "
+                                     "same steps is in flight (an idle GPU reads 100-700 MHz): 32 steps before the warm-up "
+                                     "steps, and 16 steps into a 32-step run behind the timed region and the calibration loop")
+        rec["roofline"] = roofline
+        rec["sampled_step"].update(
+            gram_end_to_k3_start_ms=round(gap_ms, 4) if gap_ms is not None else None,
+            collective_ms={k: dict(doubles=v[0], ms=round(v[1], 4)) for k, v in coll_ms.items()},
+            how="the interval: HIP events of an UNTIMED step of their own right before the warm-up steps "
+                "(nothing else time-stamped in it): kernel-bound stop of the second Gram launch -> "
+                "kernel-bound start of K3; the collectives: a recorded event pair around each all-reduce of "
+                "the timed region's sampled step, on the stream that issues it (the pair itself adds a few "
+                "us to that step)")
+    if world == 1 and not rehearse and args.full and not args.no_extras:
+        del batches, out, u_next, sh, eng
         torch.cuda.empty_cache()
         rec["parity_err"] = parity_check(engine, prob, p, n, args.dtype, args.update)
         if is_c2:
@@ -1173,7 +1218,7 @@ def main():
                 helper = None
             rec["extra"] = extra
         rec["e2e"] = e2e_block(engine, prob, p, n, J, args.dtype, args.update, local)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline(prob, p, n, J, np.dtype(args.dtype).type)
     if helper is not None:                       # (not asked: it exits on the empty line)
         try:

@@ -38,7 +38,10 @@ def manifest():
 
 @pytest.fixture(scope="session")
 def golden_steps():
-    return dict(np.load(os.path.join(GOLDEN, "steps.npz")))
+    arrays = {}
+    for name in ("steps_1.npz", "steps_2.npz"):         # (two halves of the cases: each file under 1 MiB)
+        arrays.update(np.load(os.path.join(GOLDEN, name)))
+    return arrays
 
 
 @pytest.fixture(scope="session")

@@ -234,11 +234,13 @@ def test_bench_rank_control_flow_on_two_gloo_ranks():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "tests", "bench_rehearsal.py"), "--gpus", "2", "--steps", "3",
            "--warmup", "1"]
-    for pin in (None, "0"):
-        # (no pin: both ranks time both collective modes behind the pre-warm and keep the same, faster one -- round 6)
+    for pin, full in ((None, False), ("0", False), ("0", True)):
+        # (no pin: both ranks time both collective modes behind the pre-warm and keep the same, faster one -- round 6;
+        #  --full: the untimed steps and the calibration behind the timed region, on every rank)
         env_run = dict(env) if pin is None else dict(env, CESX_SINGLE_ALLREDUCE=pin)
         env_run.pop("CESX_SINGLE_ALLREDUCE", None) if pin is None else None
-        res = subprocess.run(cmd, env=env_run, cwd=root, capture_output=True, text=True, timeout=600)
+        res = subprocess.run(cmd + (["--full"] if full else []), env=env_run, cwd=root, capture_output=True, text=True,
+                             timeout=600)
         assert res.returncode == 0, res.stderr[-2000:]
         lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
         assert len(lines) == 1, res.stdout[-2000:]
@@ -254,3 +256,7 @@ def test_bench_rank_control_flow_on_two_gloo_ranks():
         else:
             assert ss["mode_choice"] is None and ss["collectives_per_step"] == 2 and "pinned" in rec["config"]["parallelism"]
         assert rec["prewarm_steps"] == 512 and rec["scaling"] == "weak"
+        if full:
+            assert {"roofline", "clock"} <= set(rec) and "collective_ms" in ss
+        else:                                   # a plain run measures the headline only
+            assert not {"roofline", "clock", "cpu_baseline", "e2e", "extra", "parity_err"} & set(rec)
