@@ -3,6 +3,7 @@
 #pragma once
 #include <cstddef>
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <string>
 #include <vector>
@@ -486,20 +487,16 @@ struct Engine {
 // ---------------------------------------------------------------------------
 // kernel launchers (defined in the .hip files)
 // ---------------------------------------------------------------------------
-struct UpdateSrc {            // one K-segment of the update GEMM
-    const void* ptr;          // (rows x J) array, or nullptr for on-device noise
-    int rows;                 // real rows
-    int kind;                 // 0 = memory, 1 = philox noise
-    int tri;                  // 1: the W columns of this segment are lower triangular (sqrt(2hk) L)
-};
-
 int launch_colsum(Engine& e, const void* U, const void* G, double* sums, hipStream_t s);
 int launch_set_shift(Engine& e, const double* sums, hipStream_t s);
 int launch_gram(Engine& e, int part, const void* U, const void* G, double* mom, hipStream_t s, bool no_reduce = false);   // part 0 / 1
 int launch_gram_reduce(Engine& e, int part, double* mom, hipStream_t s, hipEvent_t stop = nullptr, const MetricFin* fin = nullptr);   // the fp64 slab reduce of that launch (stop: bound to its completion)
 // kernels_gram2.hip (LDS-DMA Gram): CESX_OK, an error, or -1 when the launch does not qualify (caller falls back)
 int launch_gram2(Engine& e, int part, const void* U, const void* G, hipStream_t s);
-int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int phase, hipStream_t s, bool upd2_ok = false);
+// upd_ok: an update kernel takes the hk-free image of this step (pick_update_kernel)
+int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int phase, hipStream_t s, bool upd_ok = false);
+// whether launch_dense (phase 0) writes the hk-free image for this step when an update kernel takes it
+bool dense_hkfree(const Engine& e, const cesx_step_params& prm);
 // Kernels of the caller's stream and of the side stream may WAIT for each other inside a launch (the polled join of
 // launch_dense) only when the two streams cannot share a hardware queue: HIP maps the streams of one priority level
 // onto a few queues, and a waiter in front of what it waits for in one in-order queue never ends.  True when `s` has a
@@ -507,32 +504,68 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
 bool stream_below_side(Engine& e, hipStream_t s);
 int launch_chol_async(Engine& e, int update, const double* mom, hipStream_t s, bool ev_a_bound = false);
 int refresh_factor(Engine& e, hipStream_t s);
-// whether an update launch [xi; U; G] -> Unext of this engine qualifies for the LDS-DMA fp32 kernel (kernels_update2.hip)
-bool update2_qualifies(const Engine& e, const void* U, const void* G, const void* xi, const void* Unext);
-struct UpdateOpt {
+struct UpdateSrc {            // one K-segment of the update GEMM
+    const void* ptr;          // (rows x J) array, or nullptr for on-device noise
+    int rows;                 // real rows
+    int kind;                 // 0 = memory, 1 = philox noise
+    int tri;                  // 1: the W columns of this segment are lower triangular (sqrt(2hk) L)
+};
+struct UpdateAdd {            // an optional epilogue term  + c * ptr  (out_rows x J), c = *cp * imm, or imm when cp == nullptr
+    const void* ptr = nullptr;
+    const double* cp = nullptr;
+    double imm = 0.0;
+};
+// One update launch  out = W . [segments] + bias (+ add1 + add2)  (kernels_update*.hip); call sites name the fields they use.
+struct UpdateLaunch {
+    int out_rows = 0;
+    const void* W = nullptr;       // [rpad][ktot] row-major (update_kernel)
+    const void* Wf = nullptr;      // the same W in the fragment-major order of the LDS-DMA kernels (wf_index / wd_index), or the hk-free
+                                   // image Engine::d_Wq; nullptr: update_kernel only
+    int ktot = 0;
+    const void* bias = nullptr;    // [rpad] or nullptr
+    UpdateSrc src[3] = {};
+    int nsrc = 0;
+    UpdateAdd add1, add2;
+    void* out = nullptr;
+    double* absmax_part = nullptr; // per-workgroup max |out|, or nullptr
+    uint64_t step_index = 0;       // Philox counter of in-kernel noise
+    bool metrics = false;          // data metrics over the K-segment metric_seg (it holds G)
+    int metric_seg = 1;
+    const double* hkp = nullptr;   // != nullptr: Wf is the hk-free image, segments [xi | U | G] with the triangular one first; the
+    const double* s2p = nullptr;   // accumulators are scaled by *s2p / *hkp behind the first segment and the result (+ bias) by *hkp
     const unsigned long long* fault = nullptr;   // != nullptr: the launch leaves `out` untouched when *fault == fault_seq (a polled join that ran out)
     unsigned long long fault_seq = 0;
-    int ldw = 0;          // row stride of W (0: = ktot)
-    const double* hkp = nullptr;   // != nullptr (LDS-DMA fp32 kernel, triangular segment FIRST): W carries no time step -- the accumulators
-    const double* s2p = nullptr;   // are scaled by *s2p / *hkp behind the first segment and the result (+ bias) by *hkp in the epilogue
-    int metric_seg = 1;   // K-segment that holds G (data metrics)
-    const void* wf = nullptr;  // fragment-major copy of the WHOLE W (fp32): enables the LDS-DMA kernel
-    int prof = -1;        // profiling slot (1 = K3) or -1
+    int prof = -1;                 // profiling slot (1 = K3) or -1
 };
-int launch_update(Engine& e, int out_rows, const void* W, int ktot, const void* bias,
-                  const UpdateSrc* src, int nsrc,
-                  const void* add1, const double* c1, double c1_imm,
-                  const void* add2, const double* c2, double c2_imm,
-                  void* out, double* absmax_part, uint64_t step_index, bool metrics,
-                  const UpdateOpt& opt, hipStream_t s);
+// the K-segments of a launch, resolved once for every kernel (k-tiles of 16; every segment is padded to whole tiles)
+struct UpdateSegs {
+    int kt[3];        // first k-tile of each segment (0x7fffffff: absent)
+    int tri_seg;      // segment with lower-triangular W columns, -1: none
+    bool noise;       // a segment is drawn in-kernel
+    bool al16;        // every segment read from memory is non-null and 16-byte aligned
+    bool ok;          // 1 to 3 segments that add up to ktot
+};
+UpdateSegs update_segments(const UpdateLaunch& L);
+enum class UpdateKernel {
+    None,             // an hk-free image that no kernel takes
+    Update4,          // update4_kernel: the chained hk-free image (K3 through the Cholesky factor)
+    Update2s, Update2, Update3s, Update3,   // the LDS-DMA kernels, fp32 / fp64, small (out_rows <= 64) or tiled
+    Generic           // update_kernel
+};
+// the kernel launch_update runs for L; cesx_apply asks it before launch_dense commits the step to the hk-free image
+UpdateKernel pick_update_kernel(const Engine& e, const UpdateLaunch& L);
+int launch_update(Engine& e, const UpdateLaunch& L, hipStream_t s);
 int update_grid_blocks(Engine& e, int out_rows);
-// kernels_update2.hip: returns CESX_OK, an error, or -1 when the launch does not qualify (caller falls back)
-int launch_update2(Engine& e, int out_rows, const void* Wf, int ktot, const void* bias,
-                   const UpdateSrc* src, int nsrc,
-                   const void* add1, const double* c1, double c1_imm,
-                   const void* add2, const double* c2, double c2_imm,
-                   void* out, double* absmax_part, uint64_t step_index, bool metrics,
-                   const UpdateOpt& opt, hipStream_t s);
+// the kernels behind launch_update (L checked, g = update_segments(L)); small: update2s_kernel / update3s_kernel
+int launch_update2(Engine& e, const UpdateLaunch& L, const UpdateSegs& g, bool small, hipStream_t s);
+int launch_update3(Engine& e, const UpdateLaunch& L, const UpdateSegs& g, bool small, hipStream_t s);
+int launch_update4(Engine& e, const UpdateLaunch& L, hipStream_t s);     // the noise segment from memory
+int update2_lds(const Engine& e);     // dynamic LDS of one update2_kernel / update3_kernel workgroup
+int update3_lds(const Engine& e);
+constexpr int U2S_MAX_KT = 12;        // update2s_kernel / update3s_kernel: ktot <= 192
+constexpr int U3S_MAX_KT = 12;
+// the shapes the chained form takes (decided once per problem, cesx_set_problem)
+bool update4_shape_ok(const Engine& e);
 // index of W[i][k] (row i of the zero-padded rpad x ktot matrix, nkt = ktot / 16) in the fragment-major
 // image: for every 256-row chunk y and k-tile kt, 16 pieces (g, rb) of 64 lanes x 4 floats; lane
 // (lh, li) of piece (g, rb) holds W[256 y + 32 rb + li][16 kt + 2 (4 g + v) + lh], v = 0..3
@@ -560,15 +593,6 @@ __host__ __device__ inline size_t wc_index_Lt(int r, int k) {
 __host__ __device__ inline size_t wc_index_K(int i, int c) {
     return wc_slot(18 + (c >> 4), i >> 5, i & 31, c & 15);
 }
-// kernels_update4.hip: CESX_OK, an error, or -1 when the launch does not qualify
-int launch_update4(Engine& e, const void* U, const void* G, const void* xi, void* out, bool metrics, const UpdateOpt& opt, hipStream_t s);
-bool update4_shape_ok(const Engine& e);
-// kernels_update3.hip (fp64 LDS-DMA update): CESX_OK, an error, or -1 when the launch does not qualify
-int launch_update3(Engine& e, int out_rows, const void* Wd, int ktot, const void* bias,
-                   const UpdateSrc* src, int nsrc,
-                   const void* add1, const double* c1, double c1_imm,
-                   const void* add2, const double* c2, double c2_imm,
-                   void* out, double* absmax_part, bool metrics, const UpdateOpt& opt, hipStream_t s);
 // index of W[i][k] in the fp64 fragment-major image read by update3_kernel: for every 256-row chunk y, k-tile kt
 // and 16-row block rb two pieces (sp) of 64 lanes x 2 doubles; lane (lr, li) = 16 lr + li of piece sp holds
 // W[256 y + 16 rb + li][16 kt + 4 (2 sp + e) + lr], e = 0, 1
@@ -630,5 +654,39 @@ void set_global_error(const std::string& msg);
             return CESX_EHIP;                                                       \
         }                                                                           \
     } while (0)
+
+// the argument fields every update kernel but update4_kernel shares (UpdArgs<T>, Upd2Args, Upd3Args)
+template <typename T, typename A>
+inline void pack_update_common(A& a, const Engine& e, const UpdateLaunch& L, const UpdateSegs& g) {
+    a.out_rows = L.out_rows; a.bias = (const T*)L.bias;
+    a.J = e.J;
+    a.out = (T*)L.out;
+    a.add1 = (const T*)L.add1.ptr; a.c1p = L.add1.cp; a.c1i = L.add1.imm;
+    a.add2 = (const T*)L.add2.ptr; a.c2p = L.add2.cp; a.c2i = L.add2.imm;
+    a.absmax_part = L.absmax_part;
+    a.rowc = (const T*)e.d_rowc;
+    a.metric_part = L.metrics ? e.d_metric_part : nullptr;
+    a.metric_seg = L.metric_seg;
+    a.tri_seg = g.tri_seg;
+    a.fault = L.fault; a.fault_seq = L.fault_seq;
+}
+
+// One launch of an LDS-DMA update kernel (256 threads): its dynamic LDS, the grid (Engine::last_update_grid*: the partial
+// results it leaves), and the profiling events bound to the kernel's own start / end; a launch with both events also has
+// wave 0 of workgroup 0 store its clocks (a.clk = Engine::d_clk, cesx_profile_clock).
+template <typename K, typename A>
+int launch_update_bound(Engine& e, K kern, dim3 grid, int lds, A& a, int prof_which, hipStream_t s) {
+    CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    e.last_update_grid_x = (int)grid.x;
+    e.last_update_grid = (int)(grid.x * grid.y);
+    {
+        ProfScope prof(e, prof_which, s, true);
+        a.clk = (prof.a && prof.b) ? e.d_clk : nullptr;
+        if (prof.on()) hipExtLaunchKernelGGL(kern, grid, dim3(256), (unsigned)lds, s, prof.a, prof.b, 0, a);
+        else hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
+    }
+    CESX_HIP(hipGetLastError());
+    return CESX_OK;
+}
 
 }  // namespace cesx

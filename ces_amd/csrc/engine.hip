@@ -120,55 +120,48 @@ int finish_step(Engine& e, const cesx_step_params& prm, hipStream_t s) {
     return CESX_OK;
 }
 
+// the buffer of cesx_prefetch_noise that holds this step's noise block (-1: none)
+int prefetched_block(const Engine& e, uint64_t step_index) {
+    for (int b = 0; b < 2; ++b)
+        if (e.d_xi[b] && e.xi_step[b] == (long long)step_index) return b;
+    return -1;
+}
+
 // the noise block of this step drawn ahead by cesx_prefetch_noise (nullptr: draw inside the update kernel)
 const void* prefetched_noise(Engine& e, const cesx_step_params& prm, hipStream_t s) {
     // drawn on the side stream behind chol(C); its own event, waited for HERE (right before the update kernel):
     // K2's scalar and assemble kernels do not need the block and run beside the draw
-    for (int b = 0; b < 2; ++b) {
-        if (!e.d_xi[b] || e.xi_step[b] != (long long)prm.step_index) continue;
-        // a block drawn behind an EARLIER chol(C) precedes this step's chol(C) on the side stream: a stream that has
-        // waited for this step's ev_b is already ordered behind the draw
-        const bool ordered = e.xi_seq[b] < e.evb_waited_seq && s == e.evb_waited_stream;
-        if (!ordered && hipStreamWaitEvent(s, e.ev_x[b], 0) != hipSuccess) return nullptr;
-        return e.d_xi[b];
+    const int b = prefetched_block(e, prm.step_index);
+    if (b < 0) return nullptr;
+    // a block drawn behind an EARLIER chol(C) precedes this step's chol(C) on the side stream: a stream that has
+    // waited for this step's ev_b is already ordered behind the draw
+    const bool ordered = e.xi_seq[b] < e.evb_waited_seq && s == e.evb_waited_stream;
+    if (!ordered && hipStreamWaitEvent(s, e.ev_x[b], 0) != hipSuccess) return nullptr;
+    return e.d_xi[b];
+}
+
+// the update launch of an eks / aldi step: W [U; G; xi] + b, or (hkfree) the coefficient image without the time step
+// (launch_dense): [L | a I - M + I/hk | -K] against [xi; U; G] -- through the Cholesky factor where it is the chained one
+UpdateLaunch main_update(Engine& e, const cesx_step_params& prm, const void* U, const void* G, const void* xi, void* Unext,
+                         bool hkfree) {
+    const UpdateSrc su{U, e.p, 0, 0}, sg{G, e.n, 0, 0}, sx{xi, e.p, xi ? 0 : 1, 1};
+    UpdateLaunch L{.out_rows = e.p, .W = e.d_W, .Wf = e.d_Wf, .ktot = e.ktot, .bias = e.d_bias, .src = {su, sg, sx}, .nsrc = 3,
+                   .out = Unext, .step_index = prm.step_index, .metrics = true, .prof = 1};
+    if (e.last_join_polled) { L.fault = e.d_cholflag + 1; L.fault_seq = e.chol_seq; }
+    if (hkfree) {
+        L.Wf = e.d_Wq;
+        L.src[0] = sx; L.src[1] = su; L.src[2] = sg;
+        L.metric_seg = 2;
+        L.hkp = &e.d_scal->hk;
+        L.s2p = &e.d_scal->sqrt2hk;
     }
-    return nullptr;
+    return L;
 }
 
 int run_update_main(Engine& e, const cesx_step_params& prm, const void* U, const void* G, const void* xi,
                     void* Unext, hipStream_t s) {
     if (!xi) xi = prefetched_noise(e, prm, s);
-    UpdateSrc src[3] = {{U, e.p, 0, 0}, {G, e.n, 0, 0}, {xi, e.p, xi ? 0 : 1, 1}};
-    UpdateOpt opt;
-    opt.prof = 1;
-    opt.wf = e.d_Wf;
-    if (e.last_join_polled) { opt.fault = e.d_cholflag + 1; opt.fault_seq = e.chol_seq; }
-    if (e.last_hkfree && e.chain) {
-        // K3 through the Cholesky factor (kernels_update4.hip): the chained image, xi from memory -- a block that was neither
-        // injected nor drawn ahead is drawn here, into an engine buffer, by the kernel that draws the prefetched ones
-        if (!xi) {
-            if (!e.d_xi_tmp) CESX_HIP(hipMalloc(&e.d_xi_tmp, (size_t)e.p * (size_t)e.J * e.esz));
-            TRY(launch_noise(e, prm.step_index, e.d_xi_tmp, s));
-            xi = e.d_xi_tmp;
-        }
-        opt.hkp = &e.d_scal->hk;
-        opt.s2p = &e.d_scal->sqrt2hk;
-        int rc4 = launch_update4(e, U, G, xi, Unext, true, opt, s);
-        e.last_metric_parts = e.last_update_grid_x;
-        return rc4;
-    }
-    if (e.last_hkfree) {
-        // the coefficient image without the time step (launch_dense): [L | a I - M + I/hk | -K] against [xi; U; G]
-        src[0] = UpdateSrc{xi, e.p, xi ? 0 : 1, 1};
-        src[1] = UpdateSrc{U, e.p, 0, 0};
-        src[2] = UpdateSrc{G, e.n, 0, 0};
-        opt.wf = e.d_Wq;
-        opt.metric_seg = 2;
-        opt.hkp = &e.d_scal->hk;
-        opt.s2p = &e.d_scal->sqrt2hk;
-    }
-    int rc = launch_update(e, e.p, e.d_W, e.ktot, e.d_bias, src, 3, nullptr, nullptr, 0.0, nullptr, nullptr, 0.0,
-                           Unext, nullptr, prm.step_index, true, opt, s);
+    const int rc = launch_update(e, main_update(e, prm, U, G, xi, Unext, e.last_hkfree), s);
     e.last_metric_parts = e.last_update_grid_x;
     return rc;
 }
@@ -189,11 +182,8 @@ const void* whitened_G(Engine& e, const void* G, hipStream_t s, bool force, int*
     // (reused only inside the step that whitened it: the same array, the same stream, no cesx_moments* call since)
     if (!force && e.gw_src == G && e.gw_stream == s && e.gw_calls == e.moments_calls) return e.d_Gw;
     // G~ = L_Gamma^{-1} G: one K segment with lower-triangular coefficients (the kernel skips the zero blocks), no bias
-    UpdateSrc src[1] = {{G, e.n, 0, 1}};
-    UpdateOpt opt;
-    opt.wf = e.d_Wwh_f;
-    *rc = launch_update(e, e.n, e.d_Wwh, e.kn, nullptr, src, 1, nullptr, nullptr, 0.0, nullptr, nullptr, 0.0, e.d_Gw,
-                        nullptr, 0, false, opt, s);
+    *rc = launch_update(e, UpdateLaunch{.out_rows = e.n, .W = e.d_Wwh, .Wf = e.d_Wwh_f, .ktot = e.kn, .src = {{G, e.n, 0, 1}}, .nsrc = 1,
+                                        .out = e.d_Gw}, s);
     if (*rc != CESX_OK) return nullptr;
     e.gw_src = G; e.gw_stream = s; e.gw_calls = e.moments_calls;
     return e.d_Gw;
@@ -694,11 +684,9 @@ int cesx_apply_drift(cesx_handle h, const cesx_step_params* prm, const double* m
     hipStream_t s = (hipStream_t)stream;
     WHITEN(e, G, s, false);
     TRY(launch_dense(e, *prm, mom, 1, s));
-    UpdateSrc src[2] = {{U, e.p, 0, 0}, {G, e.n, 0, 0}};
-    UpdateOpt opt;
-    opt.wf = e.d_Wf;
-    TRY(launch_update(e, e.p, e.d_W, e.kp + e.kn, e.d_bias, src, 2, nullptr, nullptr, 0.0, nullptr, nullptr, 0.0,
-                      Unext, e.d_absmax_part, prm->step_index, true, opt, s));
+    TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.d_W, .Wf = e.d_Wf, .ktot = e.kp + e.kn, .bias = e.d_bias,
+                                      .src = {{U, e.p, 0, 0}, {G, e.n, 0, 0}}, .nsrc = 2, .out = Unext,
+                                      .absmax_part = e.d_absmax_part, .step_index = prm->step_index, .metrics = true}, s));
     e.last_metric_parts = e.last_update_grid_x;
     const int nparts = e.last_update_grid;
     TRY(finish_metrics(e, mom, G, false, s));
@@ -718,11 +706,9 @@ int cesx_apply_finish(cesx_handle h, const cesx_step_params* prm, const double* 
     TRY(launch_dense(e, *prm, nullptr, 2, s));
     // U_next = sqrt(2hk) L xi + 1 * U + hk * drift   (drift currently lives in U_next)
     if (!xi) xi = prefetched_noise(e, *prm, s);
-    UpdateSrc src[1] = {{xi, e.p, xi ? 0 : 1, 1}};
-    UpdateOpt opt;
-    opt.wf = e.d_Wf;
-    TRY(launch_update(e, e.p, e.d_W, e.kp, nullptr, src, 1, U, nullptr, 1.0, Unext, &e.d_scal->hk, 1.0, Unext,
-                      nullptr, prm->step_index, false, opt, s));
+    TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.d_W, .Wf = e.d_Wf, .ktot = e.kp, .src = {{xi, e.p, xi ? 0 : 1, 1}},
+                                      .nsrc = 1, .add1 = {U, nullptr, 1.0}, .add2 = {Unext, &e.d_scal->hk, 1.0}, .out = Unext,
+                                      .step_index = prm->step_index}, s));
     return finish_step(e, *prm, s);
 }
 
@@ -742,8 +728,13 @@ int cesx_apply(cesx_handle h, const cesx_step_params* prm, const double* mom, co
     hipStream_t s = (hipStream_t)stream;
     e.last_apply = Engine::LastApply{true, *prm, mom, U, G, xi, Unext, s, e.moments_calls};     // (the caller's G: a re-run whitens it again if need be)
     WHITEN(e, G, s, false);
-    // (whether the update launch qualifies for the LDS-DMA kernel is known here: the hk-free K2 has no other consumer)
-    TRY(launch_dense(e, *prm, mom, 0, s, update2_qualifies(e, U, G, xi, Unext)));
+    // (the kernel that would take this step's hk-free image is known here: the hk-free K2 has no other consumer)
+    const UpdateKernel hk = pick_update_kernel(e, main_update(e, *prm, U, G, xi, Unext, true));
+    // the chained form reads its noise from memory: a block neither injected nor drawn ahead goes into an engine buffer,
+    // allocated here -- nothing is allocated once K2 is enqueued
+    if (hk == UpdateKernel::Update4 && !xi && prefetched_block(e, prm->step_index) < 0 && dense_hkfree(e, *prm) && !e.d_xi_tmp)
+        CESX_HIP(hipMalloc(&e.d_xi_tmp, (size_t)e.p * (size_t)e.J * e.esz));
+    TRY(launch_dense(e, *prm, mom, 0, s, hk != UpdateKernel::None));
     TRY(run_update_main(e, *prm, U, G, xi, Unext, s));
     // (Moving this last small kernel to the side stream was tried: the event record + wait pair costs
     //  as much GPU idle time as the 7 us kernel itself.)
@@ -907,10 +898,8 @@ int cesx_forward_lineal(cesx_handle h, const void* A, const void* b, const void*
     CESX_HIP(hipMemsetAsync(e.d_Wfwd, 0, (size_t)e.rpad * e.kp * e.esz, s));
     CESX_HIP(hipMemcpy2DAsync(e.d_Wfwd, (size_t)e.kp * e.esz, A, (size_t)e.p * e.esz, (size_t)e.p * e.esz, e.n,
                               hipMemcpyDeviceToDevice, s));
-    UpdateSrc src[1] = {{U, e.p, 0, 0}};
-    UpdateOpt opt;
-    return launch_update(e, e.n, e.d_Wfwd, e.kp, b, src, 1, nullptr, nullptr, 0.0, nullptr, nullptr, 0.0, G,
-                         nullptr, 0, false, opt, s);
+    return launch_update(e, UpdateLaunch{.out_rows = e.n, .W = e.d_Wfwd, .ktot = e.kp, .bias = b, .src = {{U, e.p, 0, 0}}, .nsrc = 1,
+                                         .out = G}, s);
 }
 
 int cesx_forward_set_lineal(cesx_handle h, const void* A, const void* b, void* stream) {
@@ -930,11 +919,9 @@ int cesx_forward_apply(cesx_handle h, const void* U, void* G, void* stream) {
     if (!U || !G) { e.err = "cesx_forward_apply: null pointer"; return CESX_EINVAL; }
     if (!e.fwd_set) { e.err = "cesx_forward_apply: cesx_forward_set_lineal has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
-    UpdateSrc src[1] = {{U, e.p, 0, 0}};
-    UpdateOpt opt;
-    opt.wf = e.d_Wfwd_f;
-    return launch_update(e, e.n, e.d_Wfwd, e.kp, e.fwd_has_b ? e.d_bfwd : nullptr, src, 1, nullptr, nullptr, 0.0, nullptr,
-                         nullptr, 0.0, G, nullptr, 0, false, opt, (hipStream_t)stream);
+    return launch_update(e, UpdateLaunch{.out_rows = e.n, .W = e.d_Wfwd, .Wf = e.d_Wfwd_f, .ktot = e.kp,
+                                         .bias = e.fwd_has_b ? e.d_bfwd : nullptr, .src = {{U, e.p, 0, 0}}, .nsrc = 1, .out = G},
+                         (hipStream_t)stream);
 }
 
 int cesx_profile_enable(cesx_handle h, int on) {

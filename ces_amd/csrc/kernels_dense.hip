@@ -1933,7 +1933,14 @@ bool stream_below_side(Engine& e, hipStream_t s) {
     return hipStreamGetPriority(s, &pr) == hipSuccess && pr > e.side_prio;
 }
 
-int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int phase, hipStream_t s, bool upd2_ok) {
+bool dense_hkfree(const Engine& e, const cesx_step_params& prm) {
+    // hk kept out of the coefficient matrix (cesx_internal.h, Engine::d_Wq): the side stream wrote L, a I - M, M mu, M ubar
+    // for this factorisation, ONE launch adds the rest and the update kernel takes hk at run time
+    const bool img_ok = e.hkfree_ok && e.d_Wq != nullptr && e.cfg.dtype == CESX_F32 && e.update_v2 && potrf_ld(e.p) <= 256;
+    return prm.update == CESX_UPDATE_ALDI && prm.time_step == CESX_TS_DEFAULT && img_ok && (e.chol_inflight ? e.side_img : true);
+}
+
+int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int phase, hipStream_t s, bool upd_ok) {
     const int p = e.p, n = e.n, mx = p > n ? p : n;
     const bool f32 = e.cfg.dtype == CESX_F32;
     int rc;
@@ -1956,10 +1963,7 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
     // (early, centring fused into the Cholesky's load: the U part is done HERE, with the G part, and leaves the
     //  status word alone -- the side stream carried nothing but the factorisation)
     const int what = !early ? 3 : e.chol_fused_center ? (3 | 4) : 2;
-    // hk kept out of the coefficient matrix (cesx_internal.h, Engine::d_Wq): the side stream wrote L, a I - M, M mu, M ubar
-    // for this factorisation, ONE launch adds the rest and the update kernel takes hk at run time
-    const bool img_ok = e.hkfree_ok && e.d_Wq != nullptr && f32 && e.update_v2 && potrf_ld(p) <= 256;
-    const bool hkfree = upd2_ok && fused_finish && prm.time_step == CESX_TS_DEFAULT && img_ok && (early ? e.side_img : true);
+    const bool hkfree = upd_ok && phase == 0 && dense_hkfree(e, prm);
     e.last_hkfree = false;
     if (hkfree) {
         // the side stream is joined by the LAST workgroup of that launch (a polled word, under the conditions of the polled

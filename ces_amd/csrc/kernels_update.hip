@@ -55,7 +55,7 @@ struct UpdArgs {
     // rowc[i] = {gbar_i, y_i, 1/Gamma_ii, 0}; metric_part[block] = {sum q_r^2, sum q_e^2}
     const T* rowc; double* metric_part; int metric_seg;
     int tri_seg;      // K-segment whose W columns are lower triangular (sqrt(2hk) L), -1 if none
-    const unsigned long long* fault; unsigned long long fault_seq;   // fault != nullptr and *fault == fault_seq: leave `out` untouched (UpdateOpt)
+    const unsigned long long* fault; unsigned long long fault_seq;   // fault != nullptr and *fault == fault_seq: leave `out` untouched (UpdateLaunch)
 };
 
 template <typename T, bool ALIGNED, int WCT>
@@ -385,81 +385,105 @@ void noise_kernel(T* __restrict__ xi, int p, long long J, long long j_offset, un
 }
 
 // ---------------------------------------------------------------------------
-// opt.ldw    row stride of W (0: = ktot)
-template <typename T, int WCT>
-static int update_launch(Engine& e, UpdArgs<T>& a, bool aligned, int out_rows, int prof_which, hipStream_t s) {
+template <typename T>
+static int update_t(Engine& e, const UpdateLaunch& L, const UpdateSegs& g, hipStream_t s) {
     using C = UpdCfg<T>;
-    constexpr int RC = 4 * C::WR * Mfma<T>::TILE, BN = WCT * Mfma<T>::TILE;
-    dim3 grid((unsigned)((e.J + BN - 1) / BN), (unsigned)((out_rows + RC - 1) / RC));
+    constexpr int RC = 4 * C::WR * Mfma<T>::TILE, BN = C::WC * Mfma<T>::TILE;
+    UpdArgs<T> a{};
+    pack_update_common<T>(a, e, L, g);
+    a.W = (const T*)L.W; a.ktot = L.ktot; a.ldw = L.ktot;
+    for (int i = 0; i < 3; ++i) {
+        const bool on = i < L.nsrc;
+        a.src[i] = on ? (const T*)L.src[i].ptr : nullptr;
+        a.src_rows[i] = on ? L.src[i].rows : 0;
+        a.src_k0[i] = on ? g.kt[i] * BK : 0x7fffffff;
+        a.src_kind[i] = on ? L.src[i].kind : 0;
+    }
+    a.nsrc = L.nsrc;
+    a.j_offset = e.cfg.j_offset;
+    a.seed_lo = (unsigned)e.cfg.seed; a.seed_hi = (unsigned)(e.cfg.seed >> 32); a.step = (unsigned)L.step_index;
+    const bool aligned = e.J % Mfma<T>::VEC == 0 && (uintptr_t)L.W % 16 == 0 && g.al16;
+    dim3 grid((unsigned)((e.J + BN - 1) / BN), (unsigned)((L.out_rows + RC - 1) / RC));
     const int lds = 2 * (RC * C::STRIDE_W + BK * (BN + C::XPAD)) * (int)sizeof(T) + 64 + e.kn * 4 * (int)sizeof(T);
-    auto kern = aligned ? update_kernel<T, true, WCT> : update_kernel<T, false, WCT>;
+    auto kern = aligned ? update_kernel<T, true, C::WC> : update_kernel<T, false, C::WC>;
     CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     e.last_update_grid_x = (int)grid.x;
     e.last_update_grid = (int)(grid.x * grid.y);
     {
-        ProfScope prof(e, prof_which, s);
+        ProfScope prof(e, L.prof, s);
         hipLaunchKernelGGL(kern, grid, dim3(UPD_THREADS), lds, s, a);
     }
     CESX_HIP(hipGetLastError());
     return CESX_OK;
 }
 
-template <typename T>
-static int update_t(Engine& e, int out_rows, const void* W, int ktot, const void* bias,
-                    const UpdateSrc* src, int nsrc, const void* add1, const double* c1, double c1_imm,
-                    const void* add2, const double* c2, double c2_imm, void* out, double* absmax_part,
-                    uint64_t step_index, bool metrics, const UpdateOpt& opt, hipStream_t s) {
-    UpdArgs<T> a{};
-    a.W = (const T*)W; a.ktot = ktot; a.ldw = opt.ldw ? opt.ldw : ktot; a.bias = (const T*)bias; a.out_rows = out_rows;
-    int k0 = 0;
-    bool aligned = (e.J % Mfma<T>::VEC == 0) && ((uintptr_t)W % 16 == 0) && (a.ldw % Mfma<T>::VEC == 0);
-    for (int i = 0; i < 3; ++i) {
-        a.src[i] = nullptr; a.src_rows[i] = 0; a.src_k0[i] = 0x7fffffff; a.src_kind[i] = 0;
+UpdateSegs update_segments(const UpdateLaunch& L) {
+    UpdateSegs g{{0x7fffffff, 0x7fffffff, 0x7fffffff}, -1, false, true, false};
+    if (L.nsrc < 1 || L.nsrc > 3) return g;
+    int kt = 0;
+    for (int i = 0; i < L.nsrc; ++i) {
+        const UpdateSrc& q = L.src[i];
+        g.kt[i] = kt;
+        kt += (q.rows + BK - 1) / BK;
+        if (q.tri) g.tri_seg = i;
+        if (q.kind != 0) g.noise = true;
+        else if (!q.ptr || (uintptr_t)q.ptr % 16 != 0) g.al16 = false;
     }
-    for (int i = 0; i < nsrc; ++i) {
-        a.src[i] = (const T*)src[i].ptr;
-        a.src_rows[i] = src[i].rows;
-        a.src_k0[i] = k0;
-        a.src_kind[i] = src[i].kind;
-        k0 += (src[i].rows + BK - 1) / BK * BK;
-        if (src[i].kind == 0 && (uintptr_t)src[i].ptr % 16 != 0) aligned = false;
-    }
-    if (k0 != ktot) { e.err = "update: K segments do not add up to ktot"; return CESX_EINVAL; }
-    a.nsrc = nsrc;
-    a.J = e.J; a.j_offset = e.cfg.j_offset;
-    a.out = (T*)out;
-    a.add1 = (const T*)add1; a.c1p = c1; a.c1i = c1_imm;
-    a.add2 = (const T*)add2; a.c2p = c2; a.c2i = c2_imm;
-    a.absmax_part = absmax_part;
-    a.rowc = (const T*)e.d_rowc;
-    a.metric_part = metrics ? e.d_metric_part : nullptr;
-    a.metric_seg = opt.metric_seg;
-    a.fault = opt.fault; a.fault_seq = opt.fault_seq;
-    a.tri_seg = -1;
-    for (int i = 0; i < nsrc; ++i)
-        if (src[i].tri) a.tri_seg = i;
-    a.seed_lo = (unsigned)e.cfg.seed; a.seed_hi = (unsigned)(e.cfg.seed >> 32); a.step = (unsigned)step_index;
-    return update_launch<T, UpdCfg<T>::WC>(e, a, aligned, out_rows, opt.prof, s);
+    g.ok = kt * BK == L.ktot;
+    return g;
 }
 
-int launch_update(Engine& e, int out_rows, const void* W, int ktot, const void* bias,
-                  const UpdateSrc* src, int nsrc, const void* add1, const double* c1, double c1_imm,
-                  const void* add2, const double* c2, double c2_imm, void* out, double* absmax_part,
-                  uint64_t step_index, bool metrics, const UpdateOpt& opt, hipStream_t s) {
-    if (opt.wf && e.update_v2) {
-        // LDS-DMA fast paths (kernels_update2.hip fp32, kernels_update3.hip fp64); -1 = this launch does not qualify
-        const int rc = e.cfg.dtype == CESX_F32
-            ? launch_update2(e, out_rows, opt.wf, ktot, bias, src, nsrc, add1, c1, c1_imm, add2, c2, c2_imm, out,
-                             absmax_part, step_index, metrics, opt, s)
-            : launch_update3(e, out_rows, opt.wf, ktot, bias, src, nsrc, add1, c1, c1_imm, add2, c2, c2_imm, out,
-                             absmax_part, metrics, opt, s);
-        if (rc != -1) return rc;
+UpdateKernel pick_update_kernel(const Engine& e, const UpdateLaunch& L) {
+    const UpdateSegs g = update_segments(L);
+    const bool f32 = e.cfg.dtype == CESX_F32;
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    // the LDS-DMA kernels (kernels_update2.hip fp32, kernels_update3.hip fp64): the fragment-major W, 16-byte aligned rows
+    // everywhere, the LDS of two workgroups per CU; fp64 reads every segment from memory
+    const bool dma = L.Wf && e.update_v2 && e.J % 4 == 0 && e.J >= 4 && g.al16 && al16(L.Wf) && al16(L.out) &&
+                     al16(L.add1.ptr) && al16(L.add2.ptr) &&
+                     (f32 ? update2_lds(e) <= 80 * 1024 : !g.noise && update3_lds(e) <= 78 * 1024);
+    if (L.hkp) {
+        // the hk-free image: the fp32 LDS-DMA kernels only -- through the Cholesky factor when the image is the chained one
+        if (!f32 || !dma) return UpdateKernel::None;
+        if (e.chain) return UpdateKernel::Update4;
     }
-    if (opt.hkp) { e.err = "update: the hk-free coefficient image has no fallback kernel"; return CESX_EINVAL; }
-    return e.cfg.dtype == CESX_F32
-        ? update_t<float>(e, out_rows, W, ktot, bias, src, nsrc, add1, c1, c1_imm, add2, c2, c2_imm, out, absmax_part, step_index, metrics, opt, s)
-        : update_t<double>(e, out_rows, W, ktot, bias, src, nsrc, add1, c1, c1_imm, add2, c2, c2_imm, out, absmax_part, step_index, metrics, opt, s);
+    if (!dma) return UpdateKernel::Generic;
+    // a small coefficient matrix: the whole problem of a workgroup LDS resident (update2s_kernel / update3s_kernel)
+    const int nkt = L.ktot / BK;
+    const bool small = L.out_rows <= 64 && e.update_small;
+    if (f32) return small && nkt <= U2S_MAX_KT && e.J < (1ll << 26) ? UpdateKernel::Update2s : UpdateKernel::Update2;
+    return small && nkt <= U3S_MAX_KT ? UpdateKernel::Update3s : UpdateKernel::Update3;
+}
+
+int launch_update(Engine& e, const UpdateLaunch& L, hipStream_t s) {
+    const UpdateSegs g = update_segments(L);
+    if (!g.ok) { e.err = "update: K segments do not add up to ktot"; return CESX_EINVAL; }
+    if (L.hkp && (!L.s2p || L.nsrc != 3 || g.tri_seg != 0 || L.add1.ptr || L.add2.ptr)) {
+        e.err = "update: the hk-free form needs [xi | U | G] with the triangular segment first";
+        return CESX_EINVAL;
+    }
+    const UpdateKernel k = pick_update_kernel(e, L);
+    switch (k) {
+    case UpdateKernel::Update4: {
+        if (L.src[0].kind == 0) return launch_update4(e, L, s);
+        // update4_kernel reads xi from memory: a block that was neither injected nor drawn ahead is drawn here, into the
+        // engine buffer cesx_apply allocated for it, by the kernel that draws the prefetched ones
+        if (!e.d_xi_tmp) { e.err = "update: no buffer for the noise block of the chained form"; return CESX_ESTATE; }
+        if (int rc = launch_noise(e, L.step_index, e.d_xi_tmp, s)) return rc;
+        UpdateLaunch Lx = L;
+        Lx.src[0] = UpdateSrc{e.d_xi_tmp, e.p, 0, 1};
+        return launch_update4(e, Lx, s);
+    }
+    case UpdateKernel::Update2s:
+    case UpdateKernel::Update2: return launch_update2(e, L, g, k == UpdateKernel::Update2s, s);
+    case UpdateKernel::Update3s:
+    case UpdateKernel::Update3: return launch_update3(e, L, g, k == UpdateKernel::Update3s, s);
+    case UpdateKernel::Generic: return e.cfg.dtype == CESX_F32 ? update_t<float>(e, L, g, s) : update_t<double>(e, L, g, s);
+    case UpdateKernel::None: break;
+    }
+    e.err = "update: the hk-free coefficient image has no fallback kernel";
+    return CESX_EINVAL;
 }
 
 // upper bound of the number of workgroups of any update launch (sizes the partial-result buffers)

@@ -19,7 +19,6 @@
 // (it would otherwise drain the ring with vmcnt(0) at the first ds_read of every tile).
 // Bound: MFMA (v_mfma_f32_32x32x2_f32).
 #include "cesx_internal.h"
-#include <hip/hip_ext.h>
 
 namespace cesx {
 
@@ -50,8 +49,8 @@ struct Upd2Args {
     int stagger_from;     // workgroups with a linear index >= this start late (see the kernel)
     int stagger_n;        // ... by this many s_sleep(100) = 6.4k cycles each
     long long* clk;       // profiled launches only: wave 0 of workgroup (0, 0) writes its {s_memtime, s_memrealtime} ticks
-    const unsigned long long* fault; unsigned long long fault_seq;   // fault != nullptr and *fault == fault_seq: leave `out` untouched (UpdateOpt)
-    const double* hkp; const double* s2p;      // HKF instantiations: the time step and sqrt(2 hk), read at run time (UpdateOpt)
+    const unsigned long long* fault; unsigned long long fault_seq;   // fault != nullptr and *fault == fault_seq: leave `out` untouched (UpdateLaunch)
+    const double* hkp; const double* s2p;      // HKF instantiations: the time step and sqrt(2 hk), read at run time (UpdateLaunch)
 };
 
 // wait until at most `n` of this wave's DMAs are outstanding, retire its LDS traffic, barrier
@@ -529,10 +528,9 @@ void update2_kernel(const Upd2Args a) {
 // Here the WHOLE problem of a workgroup -- 64 rows x 64 particles x ktot -- is LDS resident: every DMA of W and [U; G; xi]
 // is issued up front (24 per wave), ONE wait, ONE barrier, then the MFMAs; wave (rb, cb) owns one 32 x 32 block.
 // Same W image (wf_index), same arguments, same Philox counters as update2_kernel; the triangular segment's zero blocks
-// are multiplied (0 x finite = 0).  Chosen by the SHAPE alone (launch_update2), so every call flow of a problem runs it.
+// are multiplied (0 x finite = 0).  Chosen by the SHAPE alone (pick_update_kernel), so every call flow of a problem runs it.
 // ---------------------------------------------------------------------------
 constexpr int U2S_BN = 64;            // particles per workgroup
-constexpr int U2S_MAX_KT = 12;        // ktot <= 192
 template <bool NOISE, bool HKF>
 __global__ __launch_bounds__(U2_THREADS)
 void update2s_kernel(const Upd2Args a) {
@@ -714,93 +712,34 @@ void update2s_kernel(const Upd2Args a) {
     }
 }
 
-bool update2_qualifies(const Engine& e, const void* U, const void* G, const void* xi, const void* Unext) {
-    if (e.cfg.dtype != CESX_F32 || !e.update_v2) return false;
-    if (e.J % 4 != 0 || e.J < 4 || e.ktot % U2_BK != 0) return false;
-    if (U2_RING * (U2_WSLOT + U2_XSLOT) + e.kn * 16 > 80 * 1024) return false;
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    return U && G && Unext && al16(U) && al16(G) && al16(Unext) && (!xi || al16(xi));
-}
+int update2_lds(const Engine& e) { return U2_RING * (U2_WSLOT + U2_XSLOT) + e.kn * 16; }
 
-int launch_update2(Engine& e, int out_rows, const void* Wf, int ktot, const void* bias,
-                   const UpdateSrc* src, int nsrc,
-                   const void* add1, const double* c1, double c1_imm,
-                   const void* add2, const double* c2, double c2_imm,
-                   void* out, double* absmax_part, uint64_t step_index, bool metrics,
-                   const UpdateOpt& opt, hipStream_t s) {
-    // qualifies: fp32, whole W, 16-byte aligned rows everywhere, LDS budget for two workgroups per CU
-    if (e.cfg.dtype != CESX_F32 || !Wf || opt.ldw != 0 || nsrc < 1 || nsrc > 3) return -1;
-    if (e.J % 4 != 0 || e.J < 4 || ktot % U2_BK != 0) return -1;
-    const int lds = U2_RING * (U2_WSLOT + U2_XSLOT) + e.kn * 16;
-    if (lds > 80 * 1024) return -1;
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    if (!al16(Wf) || !al16(out) || (add1 && !al16(add1)) || (add2 && !al16(add2))) return -1;
+int launch_update2(Engine& e, const UpdateLaunch& L, const UpdateSegs& g, bool small, hipStream_t s) {
     Upd2Args a{};
-    a.Wf = (const float*)Wf; a.nkt = ktot / U2_BK; a.out_rows = out_rows; a.bias = (const float*)bias;
-    const float* sp[3] = {nullptr, nullptr, nullptr};
-    int rows[3] = {1, 1, 1}, kind[3] = {0, 0, 0}, kt0[3] = {0, 0x7fffffff, 0x7fffffff};
-    int k0 = 0;
-    a.tri_seg = -1;
-    for (int i = 0; i < nsrc; ++i) {
-        if (src[i].kind == 0 && (!src[i].ptr || !al16(src[i].ptr))) return -1;
-        sp[i] = (const float*)src[i].ptr; rows[i] = src[i].rows; kind[i] = src[i].kind; kt0[i] = k0 / U2_BK;
-        if (src[i].tri) a.tri_seg = i;
-        k0 += (src[i].rows + U2_BK - 1) / U2_BK * U2_BK;
-    }
-    if (k0 != ktot) { e.err = "update: K segments do not add up to ktot"; return CESX_EINVAL; }
-    a.src0 = sp[0]; a.src1 = sp[1]; a.src2 = sp[2];
-    a.rows0 = rows[0]; a.rows1 = rows[1]; a.rows2 = rows[2];
-    a.kind0 = kind[0]; a.kind1 = kind[1]; a.kind2 = kind[2];
-    a.kt1 = kt0[1]; a.kt2 = kt0[2];
-    a.J = e.J; a.j_offset = e.cfg.j_offset;
-    a.out = (float*)out;
-    a.add1 = (const float*)add1; a.c1p = c1; a.c1i = c1_imm;
-    a.add2 = (const float*)add2; a.c2p = c2; a.c2i = c2_imm;
-    a.absmax_part = absmax_part;
-    a.seed_lo = (unsigned)e.cfg.seed; a.seed_hi = (unsigned)(e.cfg.seed >> 32); a.step = (unsigned)step_index;
-    a.rowc = (const float*)e.d_rowc;
-    a.metric_part = metrics ? e.d_metric_part : nullptr;
-    a.metric_seg = opt.metric_seg;
-    a.fault = opt.fault; a.fault_seq = opt.fault_seq;
-    a.hkp = opt.hkp; a.s2p = opt.s2p;
-    if (opt.hkp && (!opt.s2p || nsrc != 3 || a.tri_seg != 0 || add1 || add2)) { e.err = "update: the hk-free form needs [xi | U | G] with the triangular segment first"; return CESX_EINVAL; }
-    const bool noise = kind[0] != 0 || kind[1] != 0 || kind[2] != 0;
-    if (out_rows <= 64 && a.nkt <= U2S_MAX_KT && e.J < (1ll << 26) && e.update_small) {
-        // small coefficient matrix: the whole problem of a workgroup LDS resident (update2s_kernel)
+    pack_update_common<float>(a, e, L, g);
+    a.Wf = (const float*)L.Wf; a.nkt = L.ktot / U2_BK;
+    const UpdateSrc none{nullptr, 1, 0, 0};
+    const UpdateSrc &s0 = L.src[0], &s1 = L.nsrc > 1 ? L.src[1] : none, &s2 = L.nsrc > 2 ? L.src[2] : none;
+    a.src0 = (const float*)s0.ptr; a.src1 = (const float*)s1.ptr; a.src2 = (const float*)s2.ptr;
+    a.rows0 = s0.rows; a.rows1 = s1.rows; a.rows2 = s2.rows;
+    a.kind0 = s0.kind; a.kind1 = s1.kind; a.kind2 = s2.kind;
+    a.kt1 = g.kt[1]; a.kt2 = g.kt[2];
+    a.j_offset = e.cfg.j_offset;
+    a.seed_lo = (unsigned)e.cfg.seed; a.seed_hi = (unsigned)(e.cfg.seed >> 32); a.step = (unsigned)L.step_index;
+    a.hkp = L.hkp; a.s2p = L.s2p;
+    if (small) {
         const int lds_s = a.nkt * 8192 + (a.nkt * U2_BK * 4 + 64 + 2 * 4 * U2S_BN) * 4;
-        dim3 grid_s((unsigned)((e.J + U2S_BN - 1) / U2S_BN));
-        auto kern = opt.hkp ? (noise ? update2s_kernel<true, true> : update2s_kernel<false, true>)
-                            : (noise ? update2s_kernel<true, false> : update2s_kernel<false, false>);
-        CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_s));
-        e.last_update_grid_x = (int)grid_s.x;
-        e.last_update_grid = (int)grid_s.x;
-        {
-            ProfScope prof(e, opt.prof, s, true);
-            a.clk = (prof.a && prof.b) ? e.d_clk : nullptr;
-            if (prof.on()) hipExtLaunchKernelGGL(kern, grid_s, dim3(U2_THREADS), (unsigned)lds_s, s, prof.a, prof.b, 0, a);
-            else hipLaunchKernelGGL(kern, grid_s, dim3(U2_THREADS), lds_s, s, a);
-        }
-        CESX_HIP(hipGetLastError());
-        return CESX_OK;
+        auto kern = L.hkp ? (g.noise ? update2s_kernel<true, true> : update2s_kernel<false, true>)
+                          : (g.noise ? update2s_kernel<true, false> : update2s_kernel<false, false>);
+        return launch_update_bound(e, kern, dim3((unsigned)((e.J + U2S_BN - 1) / U2S_BN)), lds_s, a, L.prof, s);
     }
-    dim3 grid((unsigned)((e.J + U2_BN - 1) / U2_BN), (unsigned)((out_rows + U2_RC - 1) / U2_RC));
+    dim3 grid((unsigned)((e.J + U2_BN - 1) / U2_BN), (unsigned)((L.out_rows + U2_RC - 1) / U2_RC));
     // the dispatcher gives every CU one workgroup before any CU gets its second: from there on start late
     a.stagger_from = (long long)grid.x * grid.y > e.num_cus ? e.num_cus : 0x7fffffff;
     a.stagger_n = 2;
-    auto kern = opt.hkp ? (noise ? update2_kernel<true, true> : update2_kernel<false, true>)
-                        : (noise ? update2_kernel<true, false> : update2_kernel<false, false>);
-    CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    e.last_update_grid_x = (int)grid.x;
-    e.last_update_grid = (int)(grid.x * grid.y);
-    {
-        ProfScope prof(e, opt.prof, s, true);
-        a.clk = (prof.a && prof.b) ? e.d_clk : nullptr;
-        if (prof.on()) hipExtLaunchKernelGGL(kern, grid, dim3(U2_THREADS), (unsigned)lds, s, prof.a, prof.b, 0, a);
-        else hipLaunchKernelGGL(kern, grid, dim3(U2_THREADS), lds, s, a);
-    }
-    CESX_HIP(hipGetLastError());
-    return CESX_OK;
+    auto kern = L.hkp ? (g.noise ? update2_kernel<true, true> : update2_kernel<false, true>)
+                      : (g.noise ? update2_kernel<true, false> : update2_kernel<false, false>);
+    return launch_update_bound(e, kern, grid, update2_lds(e), a, L.prof, s);
 }
 
 }  // namespace cesx

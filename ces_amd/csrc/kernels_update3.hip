@@ -20,7 +20,6 @@
 //  * one barrier per k-tile; two workgroups per CU cover each other's barrier and epilogue.
 // Bound: MFMA.
 #include "cesx_internal.h"
-#include <hip/hip_ext.h>
 
 namespace cesx {
 
@@ -42,7 +41,7 @@ struct Upd3Args {
     const double* rowc; double* metric_part; int metric_seg;
     int tri_seg;
     long long* clk;       // profiled launches only: wave 0 of workgroup (0, 0) writes its {s_memtime, s_memrealtime} ticks
-    const unsigned long long* fault; unsigned long long fault_seq;   // fault != nullptr and *fault == fault_seq: leave `out` untouched (UpdateOpt)
+    const unsigned long long* fault; unsigned long long fault_seq;   // fault != nullptr and *fault == fault_seq: leave `out` untouched (UpdateLaunch)
 };
 
 __global__ __launch_bounds__(U3_THREADS, 2)
@@ -282,7 +281,6 @@ void update3_kernel(const Upd3Args a) {
 // and owns two 16 x 16 blocks.  Same image (wd_index) and arguments as update3_kernel; chosen by the shape alone.
 // ---------------------------------------------------------------------------
 constexpr int U3S_BN = 32;
-constexpr int U3S_MAX_KT = 12;
 __global__ __launch_bounds__(U3_THREADS)
 void update3s_kernel(const Upd3Args a) {
     using d4 = double __attribute__((ext_vector_type(4)));
@@ -441,73 +439,24 @@ void update3s_kernel(const Upd3Args a) {
     }
 }
 
-// returns CESX_OK, an error, or -1 when the launch does not qualify (caller falls back to update_kernel)
-int launch_update3(Engine& e, int out_rows, const void* Wd, int ktot, const void* bias,
-                   const UpdateSrc* src, int nsrc,
-                   const void* add1, const double* c1, double c1_imm,
-                   const void* add2, const double* c2, double c2_imm,
-                   void* out, double* absmax_part, bool metrics, const UpdateOpt& opt, hipStream_t s) {
-    if (e.cfg.dtype != CESX_F64 || !Wd || opt.ldw != 0 || nsrc < 1 || nsrc > 3) return -1;
-    if (e.J % 4 != 0 || e.J < 4 || ktot % U3_BK != 0) return -1;
-    const int lds = U3_RING * U3_XSLOT + U3_THREADS * 64 + e.kn * 32;      // (the epilogue's 16 KiB metric scratch reuses the ring)
-    if (lds > 78 * 1024) return -1;
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    if (!al16(Wd) || !al16(out) || (add1 && !al16(add1)) || (add2 && !al16(add2))) return -1;
+int update3_lds(const Engine& e) { return U3_RING * U3_XSLOT + U3_THREADS * 64 + e.kn * 32; }     // (the epilogue's 16 KiB metric scratch reuses the ring)
+
+int launch_update3(Engine& e, const UpdateLaunch& L, const UpdateSegs& g, bool small, hipStream_t s) {
     Upd3Args a{};
-    a.Wd = (const double*)Wd; a.nkt = ktot / U3_BK; a.out_rows = out_rows; a.bias = (const double*)bias;
-    const double* sp[3] = {nullptr, nullptr, nullptr};
-    int rows[3] = {1, 1, 1}, kt0[3] = {0, 0x7fffffff, 0x7fffffff};
-    int k0 = 0;
-    a.tri_seg = -1;
-    for (int i = 0; i < nsrc; ++i) {
-        if (src[i].kind != 0 || !src[i].ptr || !al16(src[i].ptr)) return -1;      // in-kernel noise: register-staged kernel
-        sp[i] = (const double*)src[i].ptr; rows[i] = src[i].rows; kt0[i] = k0 / U3_BK;
-        if (src[i].tri) a.tri_seg = i;
-        k0 += (src[i].rows + U3_BK - 1) / U3_BK * U3_BK;
-    }
-    if (k0 != ktot) { e.err = "update: K segments do not add up to ktot"; return CESX_EINVAL; }
-    for (int i = nsrc; i < 3; ++i) sp[i] = sp[0];
-    a.src0 = sp[0]; a.src1 = sp[1]; a.src2 = sp[2];
-    a.rows0 = rows[0]; a.rows1 = rows[1]; a.rows2 = rows[2];
-    a.kt1 = kt0[1]; a.kt2 = kt0[2];
-    a.J = e.J;
-    a.out = (double*)out;
-    a.add1 = (const double*)add1; a.c1p = c1; a.c1i = c1_imm;
-    a.add2 = (const double*)add2; a.c2p = c2; a.c2i = c2_imm;
-    a.absmax_part = absmax_part;
-    a.rowc = (const double*)e.d_rowc;
-    a.metric_part = metrics ? e.d_metric_part : nullptr;
-    a.metric_seg = opt.metric_seg;
-    a.fault = opt.fault; a.fault_seq = opt.fault_seq;
-    if (out_rows <= 64 && a.nkt <= U3S_MAX_KT && e.update_small) {
-        // small coefficient matrix: the whole tile of a workgroup LDS resident, W in registers (update3s_kernel)
+    pack_update_common<double>(a, e, L, g);
+    a.Wd = (const double*)L.Wf; a.nkt = L.ktot / U3_BK;
+    // (absent segments: the pointer of the first one)
+    const UpdateSrc &s0 = L.src[0], &s1 = L.src[L.nsrc > 1 ? 1 : 0], &s2 = L.src[L.nsrc > 2 ? 2 : 0];
+    a.src0 = (const double*)s0.ptr; a.src1 = (const double*)s1.ptr; a.src2 = (const double*)s2.ptr;
+    a.rows0 = s0.rows; a.rows1 = L.nsrc > 1 ? s1.rows : 1; a.rows2 = L.nsrc > 2 ? s2.rows : 1;
+    a.kt1 = g.kt[1]; a.kt2 = g.kt[2];
+    if (small) {
+        // W in registers, the whole tile of a workgroup LDS resident (update3s_kernel)
         const int lds_s = a.nkt * 4096 + (a.nkt * U3_BK * 4 + 64 + 2 * 8 * U3S_BN) * 8;
-        dim3 grid_s((unsigned)((e.J + U3S_BN - 1) / U3S_BN));
-        CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(update3s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_s));
-        e.last_update_grid_x = (int)grid_s.x;
-        e.last_update_grid = (int)grid_s.x;
-        {
-            ProfScope prof(e, opt.prof, s, true);
-            a.clk = (prof.a && prof.b) ? e.d_clk : nullptr;
-            if (prof.on()) hipExtLaunchKernelGGL(update3s_kernel, grid_s, dim3(U3_THREADS), (unsigned)lds_s, s, prof.a, prof.b, 0, a);
-            else hipLaunchKernelGGL(update3s_kernel, grid_s, dim3(U3_THREADS), lds_s, s, a);
-        }
-        CESX_HIP(hipGetLastError());
-        return CESX_OK;
+        return launch_update_bound(e, update3s_kernel, dim3((unsigned)((e.J + U3S_BN - 1) / U3S_BN)), lds_s, a, L.prof, s);
     }
-    dim3 grid((unsigned)((e.J + U3_BN - 1) / U3_BN), (unsigned)((out_rows + U3_RC - 1) / U3_RC));
-    CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(update3_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    e.last_update_grid_x = (int)grid.x;
-    e.last_update_grid = (int)(grid.x * grid.y);
-    {
-        ProfScope prof(e, opt.prof, s, true);
-        a.clk = (prof.a && prof.b) ? e.d_clk : nullptr;
-        if (prof.on()) hipExtLaunchKernelGGL(update3_kernel, grid, dim3(U3_THREADS), (unsigned)lds, s, prof.a, prof.b, 0, a);
-        else hipLaunchKernelGGL(update3_kernel, grid, dim3(U3_THREADS), lds, s, a);
-    }
-    CESX_HIP(hipGetLastError());
-    return CESX_OK;
+    dim3 grid((unsigned)((e.J + U3_BN - 1) / U3_BN), (unsigned)((L.out_rows + U3_RC - 1) / U3_RC));
+    return launch_update_bound(e, update3_kernel, grid, update3_lds(e), a, L.prof, s);
 }
 
 }  // namespace cesx

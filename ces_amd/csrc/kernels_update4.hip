@@ -28,7 +28,6 @@
 // coefficient pieces is re-filled BEHIND that barrier (its readers are past it), the first half in front of it.
 // Bound: MFMA (v_mfma_f32_32x32x2_f32).
 #include "cesx_internal.h"
-#include <hip/hip_ext.h>
 #include <utility>
 
 namespace cesx {
@@ -379,41 +378,31 @@ void update4_kernel(const Upd4Args a) {
 }
 
 // the shapes the chained form takes (decided once per problem, cesx_set_problem): fp32, eight 32-row blocks, a G segment whose
-// row constants fit beside the ring, 32-bit DMA offsets; pointer alignment is checked per call by update2_qualifies
+// row constants fit beside the ring, 32-bit DMA offsets; pointer alignment is checked per call by pick_update_kernel
 bool update4_shape_ok(const Engine& e) {
     if (e.cfg.dtype != CESX_F32 || !e.update_v2 || e.d_Wq == nullptr) return false;
     if (e.p <= 224 || e.p > 256 || e.rpad != 256 || e.kn > 256) return false;
     return e.J % 4 == 0 && e.J >= 4 && e.J < (1ll << 26);
 }
 
-int launch_update4(Engine& e, const void* U, const void* G, const void* xi, void* out, bool metrics, const UpdateOpt& opt, hipStream_t s) {
-    if (!e.chain || !U || !G || !xi || !out || !opt.hkp || !opt.s2p) { e.err = "update4: not a chained hk-free launch"; return CESX_EINVAL; }
+// L: the step's hk-free launch, segments [xi | U | G] (all from memory), Wf the chained image
+int launch_update4(Engine& e, const UpdateLaunch& L, hipStream_t s) {
     Upd4Args a{};
-    a.Wc = (const float*)e.d_Wq; a.ng = e.kn / 16; a.p = e.p; a.n = e.n;
-    a.U = (const float*)U; a.G = (const float*)G; a.xi = (const float*)xi;
-    a.bias = (const float*)e.d_bias;
+    a.Wc = (const float*)L.Wf; a.ng = e.kn / 16; a.p = e.p; a.n = e.n;
+    a.xi = (const float*)L.src[0].ptr; a.U = (const float*)L.src[1].ptr; a.G = (const float*)L.src[2].ptr;
+    a.bias = (const float*)L.bias;
     a.J = e.J;
-    a.out = (float*)out;
+    a.out = (float*)L.out;
     a.rowc = (const float*)e.d_rowc;
-    a.metric_part = metrics ? e.d_metric_part : nullptr;
-    a.hkp = opt.hkp; a.s2p = opt.s2p; a.alphap = &e.d_scal->alpha;
-    a.fault = opt.fault; a.fault_seq = opt.fault_seq;
+    a.metric_part = L.metrics ? e.d_metric_part : nullptr;
+    a.hkp = L.hkp; a.s2p = L.s2p; a.alphap = &e.d_scal->alpha;
+    a.fault = L.fault; a.fault_seq = L.fault_seq;
     const int lds = U4_RING * (U4_ASLOT + U4_XSLOT) + e.kn * 16 + 1024;
     dim3 grid((unsigned)((e.J + U4_BN - 1) / U4_BN));
     // the dispatcher gives every CU one workgroup before any CU gets its second: from there on start late
     a.stagger_from = (long long)grid.x > e.num_cus ? e.num_cus : 0x7fffffff;
     a.stagger_n = 2;          // (0 ... 4 x 6.4k cycles: no difference at C2, tools/ab_env.py round 6; 7: the CU's store path)
-    CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(update4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    e.last_update_grid_x = (int)grid.x;
-    e.last_update_grid = (int)grid.x;
-    {
-        ProfScope prof(e, opt.prof, s, true);
-        a.clk = (prof.a && prof.b) ? e.d_clk : nullptr;
-        if (prof.on()) hipExtLaunchKernelGGL(update4_kernel, grid, dim3(U4_THREADS), (unsigned)lds, s, prof.a, prof.b, 0, a);
-        else hipLaunchKernelGGL(update4_kernel, grid, dim3(U4_THREADS), lds, s, a);
-    }
-    CESX_HIP(hipGetLastError());
-    return CESX_OK;
+    return launch_update_bound(e, update4_kernel, grid, lds, a, L.prof, s);
 }
 
 }  // namespace cesx

@@ -2,6 +2,7 @@
 #include "../ces_amd/csrc/kernels_update.hip"
 #include "../ces_amd/csrc/kernels_update2.hip"
 #include "../ces_amd/csrc/kernels_update3.hip"
+#include "../ces_amd/csrc/kernels_update4.hip"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
