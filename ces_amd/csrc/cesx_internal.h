@@ -303,8 +303,16 @@ struct Engine {
     cesx_config cfg{};
     std::string err;
     bool problem_set = false, shift_valid = false;
-    bool chol_inflight = false;    // cesx_chol_async ran for the current moments; cesx_apply joins the side stream
-    bool chol_fused_center = false;   // ... with the centring fused into the factorisation's load (no U-only centring launch on the side stream)
+    struct Factor {                     // chol(C) of the current moments (kernels_dense.hip: launch_chol_async, factor_C, join_side)
+        bool inflight = false;          // cesx_chol_async ran for the current moments and launch_dense has not joined the side stream yet
+        bool fused_center = false;      // the last cesx_chol_async fused the centring into the factorisation's load (no U-only centring launch)
+        bool img = false;               // the last cesx_chol_async stores L into d_Wq (image_ok for its update rule)
+        bool signals = false;           // the last cesx_chol_async stores seq into d_cholflag (its last kernel does)
+        unsigned long long seq = 0;     // cesx_chol_async calls so far: the sequence number of the last one
+        unsigned long long waited_seq = 0; hipStream_t waited_stream = nullptr;      // the last one launch_dense joined, and on which stream
+        bool polled = false;            // the last launch_dense (phase 0 / 1) joined through the polled word, not the event
+        bool image_only = false;        // the last factorisation into d_L wrote the chained image only: d_L does not hold it (ensure_factor)
+    } fac;
     bool fuse_center_auto = true;     // no CESX_FUSE_CENTER given: fused where the step takes the hk-free form AND the second Gram launch is
                                       // short (Engine::gram_b_short: small ensembles -- the side chain is then the step's critical path and
                                       // the host's launches its floor; C4 0.0790 -> 0.0728 ms/step, round 4), not at C2 (see below)
@@ -370,7 +378,6 @@ struct Engine {
     int* d_ns_skip = nullptr;
     bool ns_ok = true;             // CESX_NS_WARM=0: always the factorisation
     double ns_r0_last = 1e300;     // ||I - A X_prev||_F^2 of the last step's warm-start attempt (cesx_result reads it from the result block)
-    const int* gate = nullptr;     // != nullptr while spd_inverse enqueues its factorisation chain: those kernels return when *gate != 0
     double *d_spec = nullptr;      // spectral rule: {sum 2^-k log N_k, 2^-k, degenerate flag, pad} + 2 x ceil(n/16)^2 partial sums of squares
     double *d_absmax = nullptr;    // [1]
     void   *d_rowc = nullptr;        // [kn][4] {gbar_i, y_i, 1/Gamma_ii, 0} engine dtype (K3 data metrics)
@@ -402,7 +409,6 @@ struct Engine {
     unsigned* d_ticket = nullptr;  // arrival counter of tail_aldi_kernel
     bool hkfree_ok = true;         // CESX_HKFREE=0 switches the path off
     bool update_small = true;      // CESX_UPDATE_SMALL=0: update2_kernel also for out_rows <= 64 (dev A/B)
-    bool side_img = false;         // the factorisation in flight stores L into d_Wq (launch_chol_async)
     bool last_hkfree = false;      // the last launch_dense took the path: the update launch reads d_Wq in the order [xi; U; G]
     // ---- K3 through the Cholesky factor (round 6; kernels_update4.hip) ----
     // With a diagonal Sigma, C Sigma^{-1} (U - mu) = L (L^T Sigma^{-1} U) - M mu: two triangular products instead of the dense M U.
@@ -411,8 +417,6 @@ struct Engine {
     // every call flow of a problem runs the same kernels.
     bool chain = false;            // d_Wq is in the chained layout and the hk-free step launches update4_kernel
     bool chain_ok = true;          // CESX_CHAIN=0: the hk-free form of round 4 (update2_kernel<., true>) also where the chained one qualifies
-    bool skip_L_hint = false;      // set by the callers of the factorisation: the step it belongs to is (expected to be) a chained one
-    bool L_stale = false;          // the last factorisation wrote the chained image only: d_L does not hold its factor (refresh_factor)
     void* d_xi_tmp = nullptr;      // [p][J] a noise block drawn right in front of update4_kernel when none was prefetched or injected
     void* d_Wfwd = nullptr;        // forward-map staging [npad][kp]
     void* d_Wfwd_f = nullptr;      // the same map in the fragment-major order of the LDS-DMA update kernels (cesx_forward_set_lineal)
@@ -446,20 +450,15 @@ struct Engine {
     // next one runs beside K2's latency-bound kernels with nothing waiting for it.
     void* d_xi[2] = {nullptr, nullptr};
     long long xi_step[2] = {-1, -1};                 // step index block b holds (-1: none)
-    unsigned long long xi_seq[2] = {0, 0};           // chol_seq of the cesx_chol_async call that drew block b
+    unsigned long long xi_seq[2] = {0, 0};           // Factor::seq of the cesx_chol_async call that drew block b
     long long xi_want = -1;          // step index asked for by cesx_prefetch_noise, drawn behind the next chol(C)
     bool xi_lookahead = true;        // CESX_NOISE_LOOKAHEAD=0 switches the second draw off
-    unsigned long long chol_seq = 0;              // cesx_chol_async calls so far
     // ---- the side stream joined through a polled word instead of a barrier packet (round 3, launch_dense) ----
     bool poll_join_ok = true;                     // CESX_POLL_JOIN=0: always join the side stream with the event
-    unsigned long long* d_cholflag = nullptr;     // chol_seq of the last factorisation that completed on the side stream, stored by the kernel itself
-    bool chol_signals = false;                    // the factorisation in flight stores that word (its last kernel does)
-    unsigned long long evb_waited_seq = 0;        // ... the last one whose ev_b a stream has waited for,
-    hipStream_t evb_waited_stream = nullptr;      // and that stream
+    unsigned long long* d_cholflag = nullptr;     // Factor::seq of the last factorisation that completed on the side stream, stored by the kernel itself
     // ---- the polled join made safe (round 4) ----
     int side_prio = 0; bool side_has_prio = false;   // priority of the side stream (cesx_create)
     unsigned long long poll_ticks = 200000000ull; // bound of the poll in 100-MHz wall-clock ticks (2 s; CESX_POLL_TIMEOUT_MS)
-    bool last_join_polled = false;                // the last launch_dense joined the side stream through the polled word
     unsigned long long poll_recoveries = 0;       // steps whose poll ran out and that cesx_result re-ran with chol(C) in line
     bool in_retry = false;
     unsigned long long test_drop_signal_at = 0;   // CESX_TEST_DROP_CHOL_SIGNAL (tests): that factorisation does not store its word
@@ -503,7 +502,7 @@ bool dense_hkfree(const Engine& e, const cesx_step_params& prm);
 // strictly lower priority than the side stream (a numerically greater one).
 bool stream_below_side(Engine& e, hipStream_t s);
 int launch_chol_async(Engine& e, int update, const double* mom, hipStream_t s, bool ev_a_bound = false);
-int refresh_factor(Engine& e, hipStream_t s);
+int ensure_factor(Engine& e, hipStream_t s);      // d_L for a host reader: re-factors C in line when it is in the chained image only
 struct UpdateSrc {            // one K-segment of the update GEMM
     const void* ptr;          // (rows x J) array, or nullptr for on-device noise
     int rows;                 // real rows

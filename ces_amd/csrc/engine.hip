@@ -135,7 +135,7 @@ const void* prefetched_noise(Engine& e, const cesx_step_params& prm, hipStream_t
     if (b < 0) return nullptr;
     // a block drawn behind an EARLIER chol(C) precedes this step's chol(C) on the side stream: a stream that has
     // waited for this step's ev_b is already ordered behind the draw
-    const bool ordered = e.xi_seq[b] < e.evb_waited_seq && s == e.evb_waited_stream;
+    const bool ordered = e.xi_seq[b] < e.fac.waited_seq && s == e.fac.waited_stream;
     if (!ordered && hipStreamWaitEvent(s, e.ev_x[b], 0) != hipSuccess) return nullptr;
     return e.d_xi[b];
 }
@@ -147,7 +147,7 @@ UpdateLaunch main_update(Engine& e, const cesx_step_params& prm, const void* U, 
     const UpdateSrc su{U, e.p, 0, 0}, sg{G, e.n, 0, 0}, sx{xi, e.p, xi ? 0 : 1, 1};
     UpdateLaunch L{.out_rows = e.p, .W = e.d_W, .Wf = e.d_Wf, .ktot = e.ktot, .bias = e.d_bias, .src = {su, sg, sx}, .nsrc = 3,
                    .out = Unext, .step_index = prm.step_index, .metrics = true, .prof = 1};
-    if (e.last_join_polled) { L.fault = e.d_cholflag + 1; L.fault_seq = e.chol_seq; }
+    if (e.fac.polled) { L.fault = e.d_cholflag + 1; L.fault_seq = e.fac.seq; }
     if (hkfree) {
         L.Wf = e.d_Wq;
         L.src[0] = sx; L.src[1] = su; L.src[2] = sg;
@@ -815,7 +815,7 @@ int cesx_result(cesx_handle h, cesx_step_result* out) {
         // From here on this engine joins its side stream with the event, and the step is re-run once with chol(C)
         // in line on the caller's stream (correct whatever the side stream is doing).
         e.poll_join_ok = false;
-        if (e.last_apply.valid && !e.in_retry && e.last_join_polled && !e.last_apply.mom_reused) {
+        if (e.last_apply.valid && !e.in_retry && e.fac.polled && !e.last_apply.mom_reused) {
             const Engine::LastApply la = e.last_apply;
             e.in_retry = true;
             // whatever a pipelined driver put on the side stream behind the failed step (the centring + chol(C) of moments of
@@ -824,7 +824,7 @@ int cesx_result(cesx_handle h, cesx_step_result* out) {
                 SET_DEVICE(e);
                 CESX_HIP(hipStreamSynchronize(e.side));
             }
-            e.chol_inflight = false;
+            e.fac.inflight = false;
             int rc = cesx_apply(h, &la.prm, la.mom, la.U, la.G, la.xi, la.Unext, (void*)la.s);
             if (rc == CESX_OK) rc = cesx_result(h, out);
             e.in_retry = false;
@@ -1084,8 +1084,8 @@ int cesx_debug_dense(cesx_handle h, double* ubar, double* gbar, double* C, doubl
     SET_DEVICE(e);
     FLUSH(e);
     CESX_HIP(hipDeviceSynchronize());
-    if (L && e.L_stale) {          // K3 through the Cholesky factor: the step kept L in its coefficient image only; factor C again
-        TRY(refresh_factor(e, nullptr));
+    if (L) {          // (K3 through the Cholesky factor: a step that kept L in its coefficient image only -- factored again here)
+        TRY(ensure_factor(e, nullptr));
         CESX_HIP(hipDeviceSynchronize());
     }
     const size_t p = e.p, n = e.n;

@@ -563,7 +563,7 @@ void potrf_reg_kernel(int n, int np, const double* __restrict__ A, double* __res
             }
             // (CHAINV == 2: the fp64 factor is NOT written back -- the image is all a chained step reads, and the one
             //  CU's store path (~18 B/clk marginal) is what the image stores cost: 97.9 us without an image, 108.2 with both images
-            //  AND the factor, tools/potrf_bench; whoever reads Engine::d_L afterwards re-factors C first, Engine::L_stale)
+            //  AND the factor, tools/potrf_bench; whoever reads Engine::d_L afterwards re-factors C first, ensure_factor)
             double* dst = Lp + (size_t)(kb + r) * ldl + kb;
 #pragma clang loop unroll(full)
             for (int j = 0; j < QNB; ++j) {
@@ -1407,7 +1407,7 @@ __global__ void lineal_fix_kernel(MomLayout ml, const double* __restrict__ T, co
 }
 
 static int gemm(Engine& e, hipStream_t s, int m, int n, int k, double alpha, const double* A, long long a0,
-                long long a1, const double* B, long long b0, long long b1, double* C);
+                long long a1, const double* B, long long b0, long long b1, double* C, const int* gate = nullptr);
 
 int launch_moments_lineal(Engine& e, double* mom, hipStream_t s) {
     const int p = e.p, n = e.n;
@@ -1438,43 +1438,46 @@ __global__ void hk_sum_kernel(int len, const Scalars* __restrict__ sc, const dou
 static inline dim3 g1(long long len, int bs = 256) { return dim3((unsigned)((len + bs - 1) / bs)); }
 
 static int gemm(Engine& e, hipStream_t s, int m, int n, int k, double alpha, const double* A, long long a0,
-                long long a1, const double* B, long long b0, long long b1, double* C) {
+                long long a1, const double* B, long long b0, long long b1, double* C, const int* gate) {
     // (small output, long k: K split over the waves of a workgroup -- a 256^3 product 20 -> 8 us, NOTEBOOK.md section 3; else 2 x 2 blocks per workgroup)
     if (k >= 64 && (long long)((m + 15) / 16) * ((n + 15) / 16) <= 4096)
         hipLaunchKernelGGL(gemm_splitk_kernel, dim3((n + 15) / 16, (m + 15) / 16), dim3(DT), 0, s, m, n, k, alpha, A, a0,
-                           a1, B, b0, b1, C, n, e.gate);
+                           a1, B, b0, b1, C, n, gate);
     else
     hipLaunchKernelGGL(gemm_kernel, dim3((n + 31) / 32, (m + 31) / 32), dim3(DT), 0, s, m, n, k, alpha, A, a0,
-                       a1, B, b0, b1, C, n, (const double*)nullptr, e.gate);
+                       a1, B, b0, b1, C, n, (const double*)nullptr, gate);
     CESX_HIP(hipGetLastError());
     return CESX_OK;
 }
 
 struct PotrfCen { const double* sa = nullptr; const double* N = nullptr; int unbiased = 0; };    // centring fused into the load
+struct PotrfLaunch {                              // one factorisation launch (potrf); call sites name the fields they use
+    const double* A = nullptr; int lda = 0;       // the SPD matrix (lda 0: n)
+    double* L = nullptr; int ldl = 0;             // its factor (ldl 0: potrf_ld(n); entries above the diagonal undefined)
+    hipEvent_t stop = nullptr;                    // an event to complete with the factorisation (potrf)
+    PotrfCen cen{};                               // centring fused into the load (A: the raw second moments)
+    unsigned long long* done = nullptr; unsigned long long done_val = 0;      // stored by the chain's last kernel
+    float* wq = nullptr;                          // the hk-free update's image (one-kernel factorisations)
+    const int* gate = nullptr;                    // != nullptr: the kernels return when *gate != 0 (spd_inverse)
+    bool write_L = true;                          // false: a chained image is all the step reads, L is not written back
+};
 
 template <int SLOTS>
-static int potrf_reg_launch(Engine& e, hipStream_t s, int n, int np, const double* A, double* Lp, int lda = 0, int ldl = 0,
-                            hipEvent_t stop = nullptr,        // stop: event bound to this kernel's own completion signal
-                            PotrfCen cen = PotrfCen(),
-                            unsigned long long* done = nullptr, unsigned long long done_val = 0, float* wq = nullptr) {
+static int potrf_reg_launch(Engine& e, hipStream_t s, int n, int np, const PotrfLaunch& f) {
     constexpr int NPMAX = SLOTS <= 2 ? 64 : SLOTS <= 5 ? 128 : SLOTS <= 10 ? 192 : 256;
-    const double* wq_sinv = (wq != nullptr && e.chain) ? (const double*)e.d_sw : (const double*)nullptr;      // the chained image (kernels_update4.hip)
-    const size_t lds = (size_t)3 * QNB * (2 * NPMAX + 4) * 8 + ((cen.sa || wq_sinv) ? (size_t)2 * NPMAX * 8 : 0);      // panel x 2, its negative (each k-row behind NPMAX zeros), the row sums of a fused centring, -1 / Sigma_kk
+    const double* wq_sinv = (f.wq != nullptr && e.chain) ? (const double*)e.d_sw : (const double*)nullptr;      // the chained image (kernels_update4.hip)
+    const size_t lds = (size_t)3 * QNB * (2 * NPMAX + 4) * 8 + ((f.cen.sa || wq_sinv) ? (size_t)2 * NPMAX * 8 : 0);      // panel x 2, its negative (each k-row behind NPMAX zeros), the row sums of a fused centring, -1 / Sigma_kk
     auto kern = potrf_reg_kernel<SLOTS, 0>;
-    // the chained image is all a chained step reads: the fp64 factor is written back only when the step may turn out NOT to be one
-    // (Engine::skip_L_hint: the caller knows, or the previous step was chained -- a wrong guess costs one in-line factorisation)
-    const bool skip_L = wq_sinv != nullptr && Lp == e.d_L && e.skip_L_hint;
-    if (Lp == e.d_L) e.L_stale = skip_L;
-    if constexpr (SLOTS == 17) { if (wq_sinv) kern = skip_L ? potrf_reg_kernel<SLOTS, 2> : potrf_reg_kernel<SLOTS, 1>; }      // (Engine::chain implies 224 < p <= 256)
+    if constexpr (SLOTS == 17) { if (wq_sinv) kern = !f.write_L ? potrf_reg_kernel<SLOTS, 2> : potrf_reg_kernel<SLOTS, 1>; }      // (Engine::chain implies 224 < p <= 256)
     else if (wq_sinv) { e.err = "potrf: the chained image needs 224 < p <= 256"; return CESX_EINVAL; }
     CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (stop)
-        hipExtLaunchKernelGGL(kern, dim3(1), dim3(PRT), (unsigned)lds, s, nullptr, stop, 0, n, np, A, Lp,
-                              &e.d_scal->status, (long long*)nullptr, lda, ldl, cen.sa, cen.N, cen.unbiased, done, done_val,
-                              wq, e.ktot / 16, e.kp, e.gate, wq_sinv);
+    if (f.stop)
+        hipExtLaunchKernelGGL(kern, dim3(1), dim3(PRT), (unsigned)lds, s, nullptr, f.stop, 0, n, np, f.A, f.L,
+                              &e.d_scal->status, (long long*)nullptr, f.lda, f.ldl, f.cen.sa, f.cen.N, f.cen.unbiased, f.done,
+                              f.done_val, f.wq, e.ktot / 16, e.kp, f.gate, wq_sinv);
     else
-    hipLaunchKernelGGL(kern, dim3(1), dim3(PRT), lds, s, n, np, A, Lp, &e.d_scal->status, (long long*)nullptr,
-                       lda, ldl, cen.sa, cen.N, cen.unbiased, done, done_val, wq, e.ktot / 16, e.kp, e.gate, wq_sinv);
+    hipLaunchKernelGGL(kern, dim3(1), dim3(PRT), lds, s, n, np, f.A, f.L, &e.d_scal->status, (long long*)nullptr,
+                       f.lda, f.ldl, f.cen.sa, f.cen.N, f.cen.unbiased, f.done, f.done_val, f.wq, e.ktot / 16, e.kp, f.gate, wq_sinv);
     CESX_HIP(hipGetLastError());
     return CESX_OK;
 }
@@ -1604,65 +1607,59 @@ __global__ void pad_copy_kernel(int n, int np, const double* __restrict__ A, dou
 // potrf_ld(n) = n rounded up to 32; entries above the diagonal are undefined).
 int potrf_ld(int n) { return (n + PNB - 1) / PNB * PNB; }
 
-static int potrf_reg_any(Engine& e, hipStream_t s, int n, int np, const double* A, double* Lp, int lda, int ldl,
-                         hipEvent_t stop = nullptr, PotrfCen cen = PotrfCen(),
-                         unsigned long long* done = nullptr, unsigned long long done_val = 0, float* wq = nullptr) {
+static int potrf_reg_any(Engine& e, hipStream_t s, int n, int np, const PotrfLaunch& f) {
     const int T = np / 16, ntile = T * (T + 1) / 2, slots = (ntile + 7) / 8;
-    if (slots <= 2) return potrf_reg_launch<2>(e, s, n, np, A, Lp, lda, ldl, stop, cen, done, done_val, wq);       // np <= 64
-    if (slots <= 5) return potrf_reg_launch<5>(e, s, n, np, A, Lp, lda, ldl, stop, cen, done, done_val, wq);       // np <= 128
-    if (slots <= 10) return potrf_reg_launch<10>(e, s, n, np, A, Lp, lda, ldl, stop, cen, done, done_val, wq);     // np <= 192
-    if (slots <= 17) return potrf_reg_launch<17>(e, s, n, np, A, Lp, lda, ldl, stop, cen, done, done_val, wq);     // np <= 256
+    if (slots <= 2) return potrf_reg_launch<2>(e, s, n, np, f);       // np <= 64
+    if (slots <= 5) return potrf_reg_launch<5>(e, s, n, np, f);       // np <= 128
+    if (slots <= 10) return potrf_reg_launch<10>(e, s, n, np, f);     // np <= 192
+    if (slots <= 17) return potrf_reg_launch<17>(e, s, n, np, f);     // np <= 256
     e.err = "potrf: diagonal block too large for the register kernel";
     return CESX_EINVAL;
 }
 
 static int trsm_reg(Engine& e, hipStream_t s, int nr, int nc, const double* A, int lda, const double* L, int ldl,
-                    double* X, int ldx) {
+                    double* X, int ldx, const int* gate) {
     const dim3 grid((nr + 63) / 64), block(PRT);
     const int slots = (4 * (nc / 16) + 7) / 8;
-    if (slots <= 2) hipLaunchKernelGGL(trsm_reg_kernel<2>, grid, block, 0, s, nr, nc, A, lda, L, ldl, X, ldx, e.gate);
-    else if (slots <= 4) hipLaunchKernelGGL(trsm_reg_kernel<4>, grid, block, 0, s, nr, nc, A, lda, L, ldl, X, ldx, e.gate);
-    else if (slots <= 6) hipLaunchKernelGGL(trsm_reg_kernel<6>, grid, block, 0, s, nr, nc, A, lda, L, ldl, X, ldx, e.gate);
-    else hipLaunchKernelGGL(trsm_reg_kernel<8>, grid, block, 0, s, nr, nc, A, lda, L, ldl, X, ldx, e.gate);
+    if (slots <= 2) hipLaunchKernelGGL(trsm_reg_kernel<2>, grid, block, 0, s, nr, nc, A, lda, L, ldl, X, ldx, gate);
+    else if (slots <= 4) hipLaunchKernelGGL(trsm_reg_kernel<4>, grid, block, 0, s, nr, nc, A, lda, L, ldl, X, ldx, gate);
+    else if (slots <= 6) hipLaunchKernelGGL(trsm_reg_kernel<6>, grid, block, 0, s, nr, nc, A, lda, L, ldl, X, ldx, gate);
+    else hipLaunchKernelGGL(trsm_reg_kernel<8>, grid, block, 0, s, nr, nc, A, lda, L, ldl, X, ldx, gate);
     CESX_HIP(hipGetLastError());
     return CESX_OK;
 }
 
-// stop (optional): an event to complete with the factorisation.  One-kernel factorisations bind it to the kernel's own
+// f.stop (optional): an event to complete with the factorisation.  One-kernel factorisations bind it to the kernel's own
 // completion signal (hipExtLaunchKernel: no separate marker packet on the stream -- a marker costs ~6 us before the
 // next kernel of the stream starts); the blocked path records it behind its last kernel.
-static int potrf(Engine& e, hipStream_t s, int n, const double* A, double* Lp, hipEvent_t stop = nullptr,
-                 unsigned long long* done = nullptr, unsigned long long done_val = 0,      // done: stored by the chain's last kernel
-                 float* wq = nullptr) {                                                      // wq: the hk-free update's image (one-kernel factorisations)
+static int potrf(Engine& e, hipStream_t s, int n, const PotrfLaunch& f) {
     const int np = potrf_ld(n);
-    if (np <= 256) {
-        return potrf_reg_any(e, s, n, np, A, Lp, 0, 0, stop, PotrfCen(), done, done_val, wq);
-    }
+    if (np <= 256) return potrf_reg_any(e, s, n, np, f);
     // Blocked right-looking factorisation with 256-wide diagonal blocks (p > 256): register
     // Cholesky of the diagonal block, register TRSM of the rows below it (64 rows per
     // workgroup), fp64 GEMM for the trailing update -- on a work copy bordered by the identity.
     if (!e.d_Lwork) { e.err = "potrf: no workspace for the blocked factorisation"; return CESX_EINVAL; }
     double* W = e.d_Lwork;
-    hipLaunchKernelGGL(pad_copy_kernel, g1((long long)np * np), dim3(256), 0, s, n, np, A, W);
+    hipLaunchKernelGGL(pad_copy_kernel, g1((long long)np * np), dim3(256), 0, s, n, np, f.A, W);
     CESX_HIP(hipGetLastError());
     int rc;
     for (int k0 = 0; k0 < np; k0 += 256) {
         const int nb = std::min(256, np - k0), below = np - k0 - nb;
-        double* Lkk = Lp + (size_t)k0 * np + k0;
+        double* Lkk = f.L + (size_t)k0 * np + k0;
         // (the LAST diagonal block's factorisation is the chain's last kernel: it carries the completion word)
         const bool last = below == 0;
-        if ((rc = potrf_reg_any(e, s, nb, nb, W + (size_t)k0 * np + k0, Lkk, np, np, nullptr, PotrfCen(),
-                                last ? done : nullptr, done_val))) return rc;
+        if ((rc = potrf_reg_any(e, s, nb, nb, {.A = W + (size_t)k0 * np + k0, .lda = np, .L = Lkk, .ldl = np,
+                                               .done = last ? f.done : nullptr, .done_val = f.done_val, .gate = f.gate}))) return rc;
         if (below > 0) {
-            double* X = Lp + (size_t)(k0 + nb) * np + k0;
-            if ((rc = trsm_reg(e, s, below, nb, W + (size_t)(k0 + nb) * np + k0, np, Lkk, np, X, np))) return rc;
+            double* X = f.L + (size_t)(k0 + nb) * np + k0;
+            if ((rc = trsm_reg(e, s, below, nb, W + (size_t)(k0 + nb) * np + k0, np, Lkk, np, X, np, f.gate))) return rc;
             double* W22 = W + (size_t)(k0 + nb) * np + k0 + nb;
             hipLaunchKernelGGL(gemm_kernel, dim3((below + 31) / 32, (below + 31) / 32), dim3(DT), 0, s, below, below, nb, -1.0,
                                X, (long long)np, 1LL, X, 1LL, (long long)np, W22, np, W22);
             CESX_HIP(hipGetLastError());
         }
     }
-    if (stop) CESX_HIP(hipEventRecord(stop, s));
+    if (f.stop) CESX_HIP(hipEventRecord(f.stop, s));
     return CESX_OK;
 }
 
@@ -1679,8 +1676,8 @@ __global__ void block_copy_kernel(int nr, int nb, const double* __restrict__ A, 
 // multiple of 32, padding = identity), nr rows.  np <= 256: one register TRSM; larger: column blocks
 // of 256, X_k = (A_k - sum_{j<k} X_j L_kj^T) L_kk^{-T}, the sum by fp64 GEMMs into the workspace.
 static int trsm_right_lt(Engine& e, hipStream_t s, int nr, int np, const double* A, int lda, const double* L, int ldl,
-                         double* X, int ldx) {
-    if (np <= 256) return trsm_reg(e, s, nr, np, A, A ? lda : 0, L, ldl, X, ldx);
+                         double* X, int ldx, const int* gate) {
+    if (np <= 256) return trsm_reg(e, s, nr, np, A, A ? lda : 0, L, ldl, X, ldx, gate);
     if (!e.d_Lwork) { e.err = "trsm: no workspace"; return CESX_EINVAL; }
     double* R = e.d_Lwork;
     int rc;
@@ -1694,7 +1691,7 @@ static int trsm_right_lt(Engine& e, hipStream_t s, int nr, int np, const double*
                                X + j0, (long long)ldx, 1LL, L + (size_t)k0 * ldl + j0, 1LL, (long long)ldl, R, nb, R);
             CESX_HIP(hipGetLastError());
         }
-        if ((rc = trsm_reg(e, s, nr, nb, R, nb, L + (size_t)k0 * ldl + k0, ldl, X + k0, ldx))) return rc;
+        if ((rc = trsm_reg(e, s, nr, nb, R, nb, L + (size_t)k0 * ldl + k0, ldl, X + k0, ldx, gate))) return rc;
     }
     return CESX_OK;
 }
@@ -1889,24 +1886,39 @@ static int spd_inverse(Engine& e, hipStream_t s, int n, const double* A, const d
         hipLaunchKernelGGL(ns_resid_kernel, dim3(nb, nb), dim3(DT), 0, s, n, A, (const double*)out, Rb[0], partsf, (const double*)parts0, npart,
                            e.d_ns_skip, e.d_scal, accum ? 1 : 0);
         CESX_HIP(hipGetLastError());
-        e.gate = e.d_ns_skip;
     }
-    rc = potrf(e, s, n, A, e.d_t1);
-    if (rc == CESX_OK) rc = trsm_right_lt(e, s, n, np, nullptr, 0, e.d_t1, np, e.d_t2, np);
+    const int* gate = warm ? e.d_ns_skip : nullptr;          // (the chain below returns at once when the warm start was taken)
+    rc = potrf(e, s, n, {.A = A, .L = e.d_t1, .gate = gate});
+    if (rc == CESX_OK) rc = trsm_right_lt(e, s, n, np, nullptr, 0, e.d_t1, np, e.d_t2, np, gate);
     // X is upper triangular: X[i][k] = 0 for k < i; columns >= n of the rows < n are zero
     // (K split over the waves of a workgroup for the sizes of K2: 21 -> 7 us at n = 256)
-    if (rc == CESX_OK) rc = gemm(e, s, n, n, n, 1.0, e.d_t2, (long long)np, 1LL, e.d_t2, 1LL, (long long)np, out);
-    e.gate = nullptr;
+    if (rc == CESX_OK) rc = gemm(e, s, n, n, n, 1.0, e.d_t2, (long long)np, 1LL, e.d_t2, 1LL, (long long)np, out, gate);
     if (rc != CESX_OK) return rc;
     if (keep) e.ns_cur[which] ^= 1;
     *Ainv = out;
     return CESX_OK;
 }
 
+// chol(C) of the current moments into d_L (f.wq: and into the hk-free image), the one writer of Engine::Factor::image_only.
+// chained: the step it belongs to is (expected to be) a chained one, whose image is all that step reads -- the fp64 factor is
+// then not written back (the caller knows, or the previous step was chained: a wrong guess costs one in-line factorisation)
+static int factor_C(Engine& e, hipStream_t s, PotrfLaunch f, bool chained) {
+    f.L = e.d_L;
+    f.write_L = !(chained && f.wq != nullptr && e.chain);
+    e.fac.image_only = !f.write_L;
+    return potrf(e, s, e.p, f);
+}
+
+// the fp64 factor of the current covariance in d_L, for every host reader of it (launch_dense, assemble, cesx_debug_dense)
+int ensure_factor(Engine& e, hipStream_t s) {
+    return e.fac.image_only ? factor_C(e, s, {.A = e.d_C}, false) : CESX_OK;
+}
+
 template <typename T>
 static int assemble(Engine& e, hipStream_t s, int mode, int ktot, double sw) {
     const int mx = e.p > e.n ? e.p : e.n;
     const long long len = (long long)e.rpad * ktot;
+    if (const int rc = ensure_factor(e, s)) return rc;
     hipLaunchKernelGGL(assemble_kernel<T>, g1(len), dim3(256), 0, s, mode, e.p, e.n, e.kp, e.kn, e.rpad, ktot,
                        sw, e.d_scal, e.d_M, e.d_K, e.d_L, potrf_ld(e.p), e.d_P, e.d_PK, e.d_mv, mx, e.d_ubar, e.d_gbar,
                        e.d_y, (const double*)e.d_gw, (T*)e.d_W, (T*)e.d_bias,
@@ -1916,15 +1928,16 @@ static int assemble(Engine& e, hipStream_t s, int mode, int ktot, double sw) {
     return CESX_OK;
 }
 
-// the fp64 factor of the last step's covariance, for callers that read Engine::d_L (cesx_debug_dense): the chained factorisation
-// keeps it in the image only
-int refresh_factor(Engine& e, hipStream_t s) {
-    if (!e.L_stale) return CESX_OK;
-    return potrf(e, s, e.p, e.d_C, e.d_L);
+// center_kernel on the current moments; join, join_want, fault: the polled join of the G part (bounded by Engine::poll_ticks)
+static int launch_center(Engine& e, hipStream_t s, dim3 grid, dim3 block, const double* mom, int unbiased, int what, double* lag,
+                         const unsigned long long* join = nullptr, unsigned long long join_want = 0, unsigned long long* fault = nullptr) {
+    hipLaunchKernelGGL(center_kernel, grid, block, 0, s, MomView{e.p, e.n, mom}, e.d_shift64, e.d_y, e.d_ustar, (const double*)e.d_gw,
+                       e.diag_sigma ? (const double*)e.d_sw : (const double*)nullptr, unbiased, what, e.d_ubar, e.d_gbar, e.d_m, e.d_dg,
+                       e.d_C, e.d_Cug, e.d_See, e.d_Srr, e.d_K, e.d_M, e.d_part, e.d_scal, lag, join, join_want, fault, fault ? e.poll_ticks : 0ull);
+    CESX_HIP(hipGetLastError());
+    return CESX_OK;
 }
 
-// phase 0: everything for eks / aldi.  phase 1: aldi_constant drift coefficients.
-// phase 2: aldi_constant noise coefficients after hk is known.
 bool stream_below_side(Engine& e, hipStream_t s) {
     if (!e.side_has_prio || s == e.side) return false;
     // asked of the runtime at every cesx_apply (a cheap host call): a verdict cached by stream HANDLE would be inherited by
@@ -1933,13 +1946,38 @@ bool stream_below_side(Engine& e, hipStream_t s) {
     return hipStreamGetPriority(s, &pr) == hipSuccess && pr > e.side_prio;
 }
 
+// L may go into the hk-free image for this update rule (cesx_internal.h, Engine::d_Wq)
+static bool image_ok(const Engine& e, int update) {
+    return update == CESX_UPDATE_ALDI && e.hkfree_ok && e.d_Wq != nullptr && e.cfg.dtype == CESX_F32 && e.update_v2 &&
+        potrf_ld(e.p) <= 256;
+}
+
 bool dense_hkfree(const Engine& e, const cesx_step_params& prm) {
     // hk kept out of the coefficient matrix (cesx_internal.h, Engine::d_Wq): the side stream wrote L, a I - M, M mu, M ubar
     // for this factorisation, ONE launch adds the rest and the update kernel takes hk at run time
-    const bool img_ok = e.hkfree_ok && e.d_Wq != nullptr && e.cfg.dtype == CESX_F32 && e.update_v2 && potrf_ld(e.p) <= 256;
-    return prm.update == CESX_UPDATE_ALDI && prm.time_step == CESX_TS_DEFAULT && img_ok && (e.chol_inflight ? e.side_img : true);
+    return prm.time_step == CESX_TS_DEFAULT && image_ok(e, prm.update) && (!e.fac.inflight || e.fac.img);
 }
 
+// what both launch_dense paths ask of a polled join: a signalling factorisation in flight, one device, no shared hardware queue
+static bool poll_join_possible(Engine& e, hipStream_t s) {
+    return e.fac.inflight && e.poll_join_ok && e.fac.signals && e.J == e.Jg && s != e.side && stream_below_side(e, s);
+}
+
+// every launch_dense (phase 0 / 1): s joins the factorisation in flight, if any, through the event or (polled) a launch's poll
+static int join_side(Engine& e, hipStream_t s, bool polled) {
+    e.fac.polled = polled;
+    if (!e.fac.inflight) return CESX_OK;
+    if (!polled) CESX_HIP(hipStreamWaitEvent(s, e.ev_b, 0));
+    // (polled: no queue-level wait was issued, but the launches behind are ordered behind chol(C) all the same -- the
+    //  poll ended on its word, or it ran out and they leave the step untouched (the update launch checks the same
+    //  fault word).  A noise block drawn BEFORE this chol(C) on the side stream is therefore complete: take_noise
+    //  relies on exactly that, as it does behind the event.)
+    e.fac.waited_seq = e.fac.seq; e.fac.waited_stream = s; e.fac.inflight = false;
+    return CESX_OK;
+}
+
+// phase 0: everything for eks / aldi.  phase 1: aldi_constant drift coefficients.
+// phase 2: aldi_constant noise coefficients after hk is known.
 int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int phase, hipStream_t s, bool upd_ok) {
     const int p = e.p, n = e.n, mx = p > n ? p : n;
     const bool f32 = e.cfg.dtype == CESX_F32;
@@ -1957,32 +1995,28 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
     // data flow allows: the G part of the centring needs the moments only; the scalar kernel is the first to
     // read what the side stream wrote (trace / bias partials, later L).  One event each way per step -- every
     // record / wait pair costs ~6 us of idle GPU.
-    const bool early = e.chol_inflight;
+    const bool early = e.fac.inflight;
     const bool fused_finish = phase == 0 && prm.update == CESX_UPDATE_ALDI &&
         (prm.time_step == CESX_TS_DEFAULT || prm.time_step == CESX_TS_SPECTRAL);
     // (early, centring fused into the Cholesky's load: the U part is done HERE, with the G part, and leaves the
     //  status word alone -- the side stream carried nothing but the factorisation)
-    const int what = !early ? 3 : e.chol_fused_center ? (3 | 4) : 2;
+    const int what = !early ? 3 : e.fac.fused_center ? (3 | 4) : 2;
     const bool hkfree = upd_ok && phase == 0 && dense_hkfree(e, prm);
     e.last_hkfree = false;
     if (hkfree) {
         // the side stream is joined by the LAST workgroup of that launch (a polled word, under the conditions of the polled
         // join below), else by the event in front of it; no factorisation in flight: the U part runs here, in line
-        const bool polled = early && e.poll_join_ok && e.chol_signals && e.J == e.Jg && s != e.side && stream_below_side(e, s);
+        const bool polled = poll_join_possible(e, s);
         // (no factorisation in flight: in line, the same kernels the side stream would have run -- with CESX_FUSE_CENTER=1 the
         //  factorisation forms C while it loads S_aa and the tail launch forms the rest of the U part itself)
-        const int self_u = (early ? e.chol_fused_center : (e.fuse_center_ok || (e.fuse_center_auto && e.gram_b_short))) ? 1 : 0;
-        e.skip_L_hint = true;          // (an in-line factorisation of a step that IS hk-free)
-        if (!early && self_u) {
-            PotrfCen cen{mv.mom + e.ml.sa(), mv.mom, unbiased};
-            if ((rc = potrf_reg_any(e, s, p, potrf_ld(p), mv.mom + e.ml.Saa(), e.d_L, p, 0, nullptr, cen, nullptr, 0, (float*)e.d_Wq))) return rc;
-        } else if (!early) {
-            hipLaunchKernelGGL(center_kernel, dim3(NPB), dim3(DT), 0, s, mv, e.d_shift64, e.d_y, e.d_ustar,
-                               (const double*)e.d_gw, e.diag_sigma ? (const double*)e.d_sw : (const double*)nullptr, unbiased, 1, e.d_ubar, e.d_gbar,
-                               e.d_m, e.d_dg, e.d_C, e.d_Cug, e.d_See, e.d_Srr, e.d_K, e.d_M, e.d_part, e.d_scal, (double*)nullptr);
-            CESX_HIP(hipGetLastError());
-            if ((rc = potrf(e, s, p, e.d_C, e.d_L, nullptr, nullptr, 0, (float*)e.d_Wq))) return rc;
-        } else if (!polled) CESX_HIP(hipStreamWaitEvent(s, e.ev_b, 0));
+        const int self_u = (early ? e.fac.fused_center : (e.fuse_center_ok || (e.fuse_center_auto && e.gram_b_short))) ? 1 : 0;
+        if (!early) {
+            PotrfLaunch f{.A = e.d_C, .wq = (float*)e.d_Wq};
+            if (self_u) { f.A = mom + e.ml.Saa(); f.lda = p; f.cen = {mom + e.ml.sa(), mom, unbiased}; }
+            else if ((rc = launch_center(e, s, dim3(NPB), dim3(DT), mom, unbiased, 1, nullptr))) return rc;
+            if ((rc = factor_C(e, s, f, true))) return rc;          // (an in-line factorisation of a step that IS hk-free)
+        }
+        if ((rc = join_side(e, s, polled))) return rc;
         auto tail_kern = !e.diag_sigma ? tail_aldi_kernel<true, false> : e.chain ? tail_aldi_kernel<false, true> : tail_aldi_kernel<false, false>;
         hipLaunchKernelGGL(tail_kern, dim3(NPB), dim3(DT), 0, s, mv, prm, (const double*)e.d_shift64, (const double*)e.d_y,
                            (const double*)e.d_gw, e.d_gbar, e.d_m, e.d_dg, e.d_Cug, e.d_See, e.d_Srr, e.d_K, e.d_part, e.d_scal,
@@ -1991,14 +2025,8 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
                            e.d_ubar, e.d_C, e.d_M, (float*)e.d_Wq, e.ktot / 16, e.kp,
                            e.kn, (float*)e.d_bias, (float*)e.d_shiftT, e.d_shift64, (float*)e.d_rowc,
                            e.d_ticket, polled ? (const unsigned long long*)e.d_cholflag : (const unsigned long long*)nullptr,
-                           (unsigned long long)e.chol_seq, e.d_cholflag + 1, e.poll_ticks);
+                           (unsigned long long)e.fac.seq, e.d_cholflag + 1, e.poll_ticks);
         CESX_HIP(hipGetLastError());
-        e.last_join_polled = polled;
-        if (early) {
-            e.evb_waited_seq = e.chol_seq;
-            e.evb_waited_stream = s;
-            e.chol_inflight = false;
-        }
         e.last_hkfree = true;
         return CESX_OK;
     }
@@ -2007,32 +2035,15 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
     // chol(C) has stored its sequence number, and the assembly launch reads what that stream wrote with agent-scope
     // loads (no queue-level acquire stands between that stream's kernels and it).  Only where nothing else sits between the two and reads those results (ALDI, default time
     // step, diagonal Gamma / Sigma, one device), and only for the one-kernel factorisation that signals.
-    const bool can_poll = fused_finish && prm.time_step == CESX_TS_DEFAULT && early && !e.chol_fused_center && e.poll_join_ok &&
-        e.chol_signals && e.diag_sigma && e.J == e.Jg && s != e.side && stream_below_side(e, s);
-    const bool polled = can_poll && !(early && e.L_stale);      // (a factor that must be re-formed in line: joined with the event)
-    hipLaunchKernelGGL(center_kernel, dim3(NPB), dim3(DT), 0, s, mv, e.d_shift64, e.d_y, e.d_ustar,
-                       (const double*)e.d_gw,
-                       e.diag_sigma ? e.d_sw : (const double*)nullptr, unbiased, what, e.d_ubar, e.d_gbar,
-                       e.d_m, e.d_dg, e.d_C, e.d_Cug, e.d_See, e.d_Srr, e.d_K, e.d_M, e.d_part, e.d_scal, e.d_lag,
-                       polled ? (const unsigned long long*)e.d_cholflag : (const unsigned long long*)nullptr,
-                       (unsigned long long)e.chol_seq, e.d_cholflag + 1, e.poll_ticks);
-    CESX_HIP(hipGetLastError());
-    e.last_join_polled = polled;
-    if (!early)
-        if ((rc = potrf(e, s, p, e.d_C, e.d_L))) return rc;
-    if (early) {
-        if (!polled) CESX_HIP(hipStreamWaitEvent(s, e.ev_b, 0));
-        // the factorisation in flight expected a chained step and kept L in the image only (the time-step rule changed, or the
-        // ensembles of this call do not qualify): factor C again, in line
-        if (e.L_stale && (rc = refresh_factor(e, s))) return rc;
-        // (polled: no queue-level wait was issued, but the launches behind are ordered behind chol(C) all the same -- the
-        //  poll ended on its word, or it ran out and they leave the step untouched (the update launch checks the same
-        //  fault word).  A noise block drawn BEFORE this chol(C) on the side stream is therefore complete: take_noise
-        //  relies on exactly that, as it does behind the event.)
-        e.evb_waited_seq = e.chol_seq;
-        e.evb_waited_stream = s;
-        e.chol_inflight = false;
-    }
+    const bool polled = fused_finish && prm.time_step == CESX_TS_DEFAULT && !e.fac.fused_center && e.diag_sigma && poll_join_possible(e, s) &&
+        !e.fac.image_only;      // (a factor that must be re-formed in line: joined with the event)
+    if ((rc = launch_center(e, s, dim3(NPB), dim3(DT), mom, unbiased, what, e.d_lag, polled ? e.d_cholflag : nullptr, e.fac.seq,
+                            e.d_cholflag + 1))) return rc;
+    if ((rc = join_side(e, s, polled))) return rc;
+    if (!early && (rc = factor_C(e, s, {.A = e.d_C}, false))) return rc;
+    // the factorisation in flight expected a chained step and kept L in the image only (the time-step rule changed, or the
+    // ensembles of this call do not qualify): factor C again, in line
+    if ((rc = ensure_factor(e, s))) return rc;
     if (!e.diag_sigma)
         if ((rc = gemm(e, s, p, p, p, 1.0, e.d_C, p, 1, e.d_Sinv, p, 1, e.d_M))) return rc;
     if (prm.time_step == CESX_TS_SPECTRAL && prm.update != CESX_UPDATE_ALDI_CONSTANT) {
@@ -2056,6 +2067,7 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
         CESX_HIP(hipGetLastError());
     }
     if (fused_finish) {
+        if (e.fac.image_only) { e.err = "launch_dense: d_L does not hold the factor"; return CESX_ESTATE; }     // (ensure_factor above)
         const int nwb = (int)(((long long)e.rpad * e.ktot + DT - 1) / DT), nvb = (p + DT / 64 - 1) / (DT / 64);
         auto go = [&](auto tag, auto poll_tag) {
             using T = decltype(tag);
@@ -2065,7 +2077,7 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
                                (const double*)e.d_y, (const double*)e.d_gbar, (const double*)e.d_mu,
                                (const double*)e.d_ubar, (const double*)e.d_gw, mx, e.d_mv, (T*)e.d_W,
                                (T*)e.d_bias, (T*)e.d_shiftT, e.d_shift64, (T*)e.d_rowc, (float*)e.d_Wf,
-                               (const unsigned long long*)(e.d_cholflag + 1), (unsigned long long)e.chol_seq);
+                               (const unsigned long long*)(e.d_cholflag + 1), (unsigned long long)e.fac.seq);
         };
         auto pick = [&](auto tag) {
             if (polled) go(tag, std::true_type{});
@@ -2125,8 +2137,7 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
 // several devices, all-reduced): C = S_uu / div + 1e-8 I, M, ubar, then chol(C) on the engine's
 // side stream.  cesx_apply joins it right before W is assembled.
 int launch_chol_async(Engine& e, int update, const double* mom, hipStream_t s, bool ev_a_bound) {
-    const int p = e.p, n = e.n;
-    MomView mv{p, n, mom};
+    const int p = e.p;
     const int unbiased = update == CESX_UPDATE_EKS ? 0 : 1;
     // the whole U-only part of K2 (centre, C, M, then chol(C)) goes to the side stream: the main
     // stream continues with the second Gram launch straight after the U x U reduce
@@ -2141,38 +2152,27 @@ int launch_chol_async(Engine& e, int update, const double* mom, hipStream_t s, b
     //  against 0.0805 ms/step with it fused, the one workgroup's load phase is the longer way; stays opt-in)
     // the hk-free update's share of the side stream (cesx_internal.h, Engine::d_Wq): whether the step takes that path is
     // decided in cesx_apply (time-step rule, alignment of the ensembles); storing L into the image costs the factorisation ~1 us
-    const bool img = e.hkfree_ok && e.d_Wq != nullptr && e.cfg.dtype == CESX_F32 && update == CESX_UPDATE_ALDI && e.update_v2 &&
-        potrf_ld(p) <= 256;
-    e.chol_fused_center = potrf_ld(p) <= 256 && (e.fuse_center_ok || (e.fuse_center_auto && img && e.gram_b_short));
-    e.side_img = false;
-    e.skip_L_hint = e.last_hkfree;      // (whether THIS step is hk-free is decided in cesx_apply: expect what the last one was)
-    if (e.chol_fused_center) {
-        e.side_img = img;
+    e.fac.img = image_ok(e, update);
+    e.fac.fused_center = potrf_ld(p) <= 256 && (e.fuse_center_ok || (e.fuse_center_auto && e.fac.img && e.gram_b_short));
+    // ev_b: C, M, ubar, L -- what K2's scalar and assemble kernels read.  (CESX_TEST_DROP_CHOL_SIGNAL=k, tests only: the k-th
+    // factorisation does not store its word -- the polled join of that step runs out)
+    PotrfLaunch f{.A = e.d_C, .stop = e.ev_b, .done = e.test_drop_signal_at == e.fac.seq + 1 ? nullptr : e.d_cholflag,
+                  .done_val = e.fac.seq + 1, .wq = e.fac.img ? (float*)e.d_Wq : (float*)nullptr};
+    if (e.fac.fused_center) {
         // p <= 256 (one register-resident factorisation): the covariance is formed while the kernel loads the raw
         // second moments -- no centring launch (13 us + a kernel boundary) in front of the 100-us Cholesky, which is
         // what the caller's stream ends up waiting for; cesx_apply's own centring launch does the U part with the G
         // part (C, M, ubar, the trace / bias partials: nothing the factorisation needs)
-        const int np = potrf_ld(p);
-        PotrfCen cen{mv.mom + e.ml.sa(), mv.mom, unbiased};
-        float* wq = img ? (float*)e.d_Wq : (float*)nullptr;
-        // (CESX_TEST_DROP_CHOL_SIGNAL=k, tests only: the k-th factorisation does not store its word)
-        unsigned long long* flag = e.test_drop_signal_at == e.chol_seq + 1 ? nullptr : e.d_cholflag;
-        if ((rc = potrf_reg_any(e, e.side, p, np, mv.mom + e.ml.Saa(), e.d_L, p, 0, e.ev_b, cen, flag, e.chol_seq + 1, wq))) return rc;
+        f.A = mom + e.ml.Saa(); f.lda = p; f.cen = {mom + e.ml.sa(), mom, unbiased};
     } else {
-    e.side_img = img;
-    float* wq = e.side_img ? (float*)e.d_Wq : (float*)nullptr;
-    // (few workgroups -> 1024 threads each: 8 x 256 threads took 25 us for the 65 k elements of C, latency bound)
-    hipLaunchKernelGGL(center_kernel, dim3(std::min(NPB, e.center_u_wgs)), dim3(e.center_u_wgs < NPB ? 1024 : DT), 0, e.side, mv, e.d_shift64, e.d_y, e.d_ustar,
-                       (const double*)e.d_gw,
-                       e.diag_sigma ? e.d_sw : (const double*)nullptr, unbiased, 1, e.d_ubar, e.d_gbar,
-                       e.d_m, e.d_dg, e.d_C, e.d_Cug, e.d_See, e.d_Srr, e.d_K, e.d_M, e.d_part, e.d_scal, (double*)nullptr);
-    CESX_HIP(hipGetLastError());
-    // (CESX_TEST_DROP_CHOL_SIGNAL=k, tests only: the k-th factorisation does not store its word -- the polled join of that step runs out)
-    unsigned long long* flag = e.test_drop_signal_at == e.chol_seq + 1 ? nullptr : e.d_cholflag;
-    if ((rc = potrf(e, e.side, p, e.d_C, e.d_L, e.ev_b, flag, e.chol_seq + 1, wq))) return rc;      // ev_b: C, M, ubar, L -- what K2's scalar and assemble kernels read
+        // (few workgroups -> 1024 threads each: 8 x 256 threads took 25 us for the 65 k elements of C, latency bound)
+        if ((rc = launch_center(e, e.side, dim3(std::min(NPB, e.center_u_wgs)), dim3(e.center_u_wgs < NPB ? 1024 : DT), mom,
+                                unbiased, 1, nullptr))) return rc;
     }
-    e.chol_signals = true;      // (the one-kernel factorisation, or the last diagonal block of the blocked one, stores the word)
-    ++e.chol_seq;
+    // (whether THIS step is hk-free is decided in cesx_apply: expect what the last one was)
+    if ((rc = factor_C(e, e.side, f, e.last_hkfree))) return rc;
+    e.fac.signals = true;      // (the one-kernel factorisation, or the last diagonal block of the blocked one, stores the word)
+    ++e.fac.seq;
     if (e.xi_want >= 0 && e.d_xi[0]) {
         // noise blocks asked for by cesx_prefetch_noise (cesx_internal.h): this step's, unless the lookahead of an
         // earlier step drew it, then the next step's.  Nothing but the update kernel that reads a block waits for it.
@@ -2180,7 +2180,7 @@ int launch_chol_async(Engine& e, int update, const double* mom, hipStream_t s, b
             if ((rc = launch_noise(e, (uint64_t)step, e.d_xi[b], e.side))) return rc;
             CESX_HIP(hipEventRecord(e.ev_x[b], e.side));
             e.xi_step[b] = step;
-            e.xi_seq[b] = e.chol_seq;
+            e.xi_seq[b] = e.fac.seq;
             return CESX_OK;
         };
         int have = e.xi_step[0] == e.xi_want ? 0 : (e.d_xi[1] && e.xi_step[1] == e.xi_want) ? 1 : -1;
@@ -2192,7 +2192,7 @@ int launch_chol_async(Engine& e, int update, const double* mom, hipStream_t s, b
             if ((rc = draw(e.xi_want + 1, have ^ 1))) return rc;
         e.xi_want = -1;
     }
-    e.chol_inflight = true;
+    e.fac.inflight = true;
     return CESX_OK;
 }
 

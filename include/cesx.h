@@ -413,7 +413,8 @@ int cesx_debug_gram_plan(int p, int n_obs, int dtype, int part, int wg_budget, l
 
 /* Copies the engine's current small dense state to HOST buffers (any may be
    NULL): ubar (p), gbar (n), C (p x p), L = chol(C) (p x p), K (p x n),
-   M = C Sigma^{-1} (p x p).  Synchronises. */
+   M = C Sigma^{-1} (p x p).  Synchronises.  After a step that kept L in its coefficient image only
+   (cesx_debug_update_form 2), L is factored again from the C the engine holds now. */
 int cesx_debug_dense(cesx_handle h, double* ubar, double* gbar, double* C, double* L,
                      double* K, double* M);
 

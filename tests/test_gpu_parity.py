@@ -966,7 +966,7 @@ def test_a_step_that_turns_out_not_to_be_chained_refactors(eng_mod, monkeypatch)
     """The factorisation is enqueued (cesx_chol_async, beside the second Gram launch) before the step's time-step rule is
     known; expecting a chained step it keeps L in the coefficient image only.  When the step then takes another rule
     (here: `spectral` and `constant` in the middle of a default-rule chain, pipelined) the assembled form needs the fp64
-    factor: launch_dense re-factors C in line (Engine::L_stale).  Same chain as an engine that never chains."""
+    factor: launch_dense re-factors C in line (ensure_factor).  Same chain as an engine that never chains."""
     from ces_amd.dist import ShardedUpdate
     p, n, J = 256, 96, 4096
     d = _synthetic(p, n, J, seed=77)
