@@ -424,6 +424,20 @@ struct Engine {
     bool  fwd_set = false, fwd_has_b = false;
     double *d_A64 = nullptr, *d_b64 = nullptr;   // the installed map in fp64 (n x p, n): cesx_moments_rest_lineal
     double *d_lvec = nullptr;                    // [2][n] c = A s_u + b - s_g and A sa
+    // ---- Metropolis-Hastings over the columns (cesx_mh_*, kernels_mh.hip) ----
+    std::vector<double> h_LSi, h_mu;   // L_Sigma^{-1} and mu of the problem (cesx_set_problem): the dense prior's image
+    int mh_kind = -1;                  // CESX_MH_RW / CESX_MH_PCN after cesx_mh_set_proposal, -1: none (cesx_set_problem drops it)
+    double mh_a = 1.0;                 // P = mh_a U + (b S) xi
+    bool mh_dense_prior = false;       // RW with a dense Sigma: the prior term is scored through w = L_Sigma^{-1} (u - mu)
+    bool mh_started = false;
+    unsigned long long mh_steps = 0;   // cesx_mh_accept calls since cesx_mh_start
+    void *d_mh_W = nullptr, *d_mh_Wf = nullptr;     // b S zero padded [rpad][kp], row-major and in the LDS-DMA kernels' order
+    void *d_mh_Li = nullptr, *d_mh_Li_f = nullptr;  // dense prior: L_Sigma^{-1} in the same two layouts
+    void *d_mh_lb = nullptr;                        // dense prior: -L_Sigma^{-1} mu [rpad] (the bias of the w launch)
+    void *d_mh_w = nullptr;                         // dense prior: [p][J] w of the states being scored
+    void *d_mh_xi = nullptr;                        // fp64: [p][J] the step's noise block (update3_kernel reads segments from memory)
+    double* d_mh_phi = nullptr;                     // [J] phi of the chains' current states
+    unsigned long long* d_mh_cnt = nullptr;         // [J] accepted proposals per chain
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -616,6 +630,9 @@ int launch_noise(Engine& e, uint64_t step_index, void* xi, hipStream_t s);
 int launch_stage_forward(Engine& e, const void* A, const void* b, hipStream_t s);   // A, b -> d_Wfwd, d_Wfwd_f, d_bfwd
 int launch_moments_lineal(Engine& e, double* mom, hipStream_t s);                   // G part of the moments from the head + the installed linear map
 int launch_calibrate(Engine& e, double target_ms, double* tflops, double* clock_ghz, hipStream_t s);   // kernels_calib.hip
+// kernels_mh.hip: phi of the states X (with their forward map G, whitened when Gamma is dense) of every chain; start: into
+// Engine::d_mh_phi, counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
+int launch_mh_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s);
 
 // Event pair for one profiled launch (cesx_profile_*).  bound = false: the pair is RECORDED around the launch (two
 // marker packets: they delay the stream by ~6 us each and the interval includes that).  bound = true: the caller

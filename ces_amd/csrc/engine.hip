@@ -426,7 +426,8 @@ void cesx_destroy(cesx_handle h) {
                     e.d_C, e.d_L, e.d_Cug, e.d_See, e.d_Srr, e.d_K, e.d_Kp, e.d_M, e.d_P, e.d_PK,
                     e.d_t1, e.d_t2, e.d_t3, e.d_t4, e.d_spec, e.d_ns_x[0][0], e.d_ns_x[0][1], e.d_ns_x[1][0], e.d_ns_x[1][1], e.d_ns_r[0], e.d_ns_r[1], e.d_ns_r[2],
                     e.d_ns_parts, e.d_ns_skip, e.d_mv, e.d_part, e.d_scal, e.d_absmax,
-                    e.d_absmax_part, e.d_clk, e.d_cholflag, e.d_lag, e.d_A64, e.d_b64, e.d_lvec, e.d_Wq, e.d_ticket};
+                    e.d_absmax_part, e.d_clk, e.d_cholflag, e.d_lag, e.d_A64, e.d_b64, e.d_lvec, e.d_Wq, e.d_ticket,
+                    e.d_mh_W, e.d_mh_Wf, e.d_mh_Li, e.d_mh_Li_f, e.d_mh_lb, e.d_mh_w, e.d_mh_xi, e.d_mh_phi, e.d_mh_cnt};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     for (int w = 0; w < 2; ++w)
@@ -463,6 +464,8 @@ int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const 
     //  the handle WITHOUT a problem -- cesx_moments* / cesx_apply then return CESX_ESTATE -- instead of half of the new one)
     const bool whiten = !is_diagonal(n, Gamma);
     e.problem_set = false;
+    e.mh_kind = -1;                // (a new problem drops the MH proposal: include/cesx.h)
+    e.mh_started = false;
     e.whiten = false;
     e.gw_src = nullptr;
     std::vector<double> gw(n), yi(y, y + n), Gi(Gamma, Gamma + (size_t)n * n);
@@ -499,6 +502,8 @@ int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const 
     if (!host_chol(p, Sigma, L)) { e.err = "Sigma is not symmetric positive definite"; return CESX_ENOTPD; }
     host_tri_inverse(p, L, Li);
     host_spd_inverse(p, Li, inv);
+    e.h_LSi = Li;
+    e.h_mu.assign(mu, mu + p);
     e.diag_sigma = is_diagonal(p, Sigma);
     std::vector<double> sw(p);
     for (int i = 0; i < p; ++i) sw[i] = 1.0 / Sigma[(size_t)i * p + i];
@@ -922,6 +927,145 @@ int cesx_forward_apply(cesx_handle h, const void* U, void* G, void* stream) {
     return launch_update(e, UpdateLaunch{.out_rows = e.n, .W = e.d_Wfwd, .Wf = e.d_Wfwd_f, .ktot = e.kp,
                                          .bias = e.fwd_has_b ? e.d_bfwd : nullptr, .src = {{U, e.p, 0, 0}}, .nsrc = 1, .out = G},
                          (hipStream_t)stream);
+}
+
+// ---- Sample: Metropolis-Hastings over the columns (ces/sample.py; kernels_mh.hip) ----
+
+// the Philox step word of an MH draw: a counter domain of its own (include/cesx.h)
+static unsigned mh_step_word(uint64_t step_index) { return (unsigned)(step_index | 0x80000000ull); }
+
+// a lower-triangular p x p fp64 matrix (row-major), zero padded into the update kernels' [rpad][kp] layouts, engine dtype
+static int mh_upload_tri(Engine& e, const double* M, void** rm_dev, void** fm_dev) {
+    const size_t len = (size_t)e.rpad * e.kp;
+    std::vector<double> rm(len, 0.0), fm(len, 0.0);
+    const int nkt = e.kp / 16;
+    for (int i = 0; i < e.p; ++i)
+        for (int k = 0; k <= i; ++k) {
+            const double v = M[(size_t)i * e.p + k];
+            rm[(size_t)i * e.kp + k] = v;
+            fm[e.cfg.dtype == CESX_F32 ? wf_index(i, k, nkt) : wd_index(i, k, nkt)] = v;
+        }
+    char* t;
+    if (!*rm_dev) { TRY(dmalloc(e, &t, len * e.esz)); *rm_dev = t; }
+    if (!*fm_dev) { TRY(dmalloc(e, &t, len * e.esz)); *fm_dev = t; }
+    TRY(upload_T(e, *rm_dev, rm.data(), len));
+    return upload_T(e, *fm_dev, fm.data(), len);
+}
+
+// phi of the states X with their forward map G (cesx_mh_start: into the engine's phi; cesx_mh_accept: the test and U := X)
+static int mh_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s) {
+    WHITEN(e, G, s, true);
+    // a dense prior: w = L_Sigma^{-1} X - L_Sigma^{-1} mu, one triangular product (the kernel skips the zero blocks)
+    if (e.mh_dense_prior)
+        TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.d_mh_Li, .Wf = e.d_mh_Li_f, .ktot = e.kp, .bias = e.d_mh_lb,
+                                          .src = {{X, e.p, 0, 1}}, .nsrc = 1, .out = e.d_mh_w}, s));
+    return launch_mh_score(e, start, X, G, U, logu, step, s);
+}
+
+int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!S) { e.err = "cesx_mh_set_proposal: null pointer"; return CESX_EINVAL; }
+    if (kind != CESX_MH_RW && kind != CESX_MH_PCN) { e.err = "cesx_mh_set_proposal: unknown proposal kind"; return CESX_EINVAL; }
+    if (kind == CESX_MH_PCN && !(beta > 0.0 && beta <= 1.0)) { e.err = "cesx_mh_set_proposal: pCN needs 0 < beta <= 1"; return CESX_EINVAL; }
+    if (!e.problem_set) { e.err = "cesx_set_problem has not been called"; return CESX_ESTATE; }
+    const int p = e.p;
+    for (int i = 0; i < p; ++i)
+        for (int k = i + 1; k < p; ++k)
+            if (S[(size_t)i * p + k] != 0.0) { e.err = "cesx_mh_set_proposal: S is not lower triangular"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    CESX_HIP(hipDeviceSynchronize());          // (the images below may be read by launches still in flight)
+    e.mh_kind = -1;
+    e.mh_started = false;
+    const double b = kind == CESX_MH_PCN ? std::sqrt(beta) : 1.0;          // ces/sample.py:202: sqrt(beta), not beta
+    std::vector<double> bS(S, S + (size_t)p * p);
+    for (double& v : bS) v *= b;
+    TRY(mh_upload_tri(e, bS.data(), &e.d_mh_W, &e.d_mh_Wf));
+    e.mh_dense_prior = kind == CESX_MH_RW && !e.diag_sigma;
+    char* t;
+    if (e.mh_dense_prior) {
+        TRY(mh_upload_tri(e, e.h_LSi.data(), &e.d_mh_Li, &e.d_mh_Li_f));
+        std::vector<double> lb(e.rpad, 0.0);
+        for (int i = 0; i < p; ++i) {
+            double acc = 0.0;
+            for (int k = 0; k <= i; ++k) acc += e.h_LSi[(size_t)i * p + k] * e.h_mu[k];
+            lb[i] = -acc;
+        }
+        if (!e.d_mh_lb) { TRY(dmalloc(e, &t, (size_t)e.rpad * e.esz)); e.d_mh_lb = t; }
+        TRY(upload_T(e, e.d_mh_lb, lb.data(), e.rpad));
+        if (!e.d_mh_w) { TRY(dmalloc(e, &t, (size_t)p * (size_t)e.J * e.esz)); e.d_mh_w = t; }
+    }
+    if (e.cfg.dtype == CESX_F64 && !e.d_mh_xi) { TRY(dmalloc(e, &t, (size_t)p * (size_t)e.J * 8)); e.d_mh_xi = t; }
+    if (!e.d_mh_phi) TRY(dmalloc(e, &e.d_mh_phi, (size_t)e.J * 8));
+    if (!e.d_mh_cnt) TRY(dmalloc(e, &e.d_mh_cnt, (size_t)e.J * 8));
+    e.mh_a = kind == CESX_MH_PCN ? std::sqrt(1.0 - beta * beta) : 1.0;
+    e.mh_kind = kind;
+    return CESX_OK;
+}
+
+int cesx_mh_start(cesx_handle h, const void* U, const void* G, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U || !G) { e.err = "cesx_mh_start: null pointer"; return CESX_EINVAL; }
+    if (e.mh_kind < 0 || !e.problem_set) { e.err = "cesx_mh_start: no proposal (cesx_mh_set_proposal after cesx_set_problem)"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(mh_score(e, true, U, G, nullptr, nullptr, 0u, (hipStream_t)stream));
+    e.mh_started = true;
+    e.mh_steps = 0;
+    return CESX_OK;
+}
+
+int cesx_mh_propose(cesx_handle h, uint64_t step_index, const void* U, const void* xi, void* P, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U || !P) { e.err = "cesx_mh_propose: null pointer"; return CESX_EINVAL; }
+    if (U == P) { e.err = "cesx_mh_propose: P must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_propose: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    if (e.mh_kind < 0) { e.err = "cesx_mh_propose: cesx_mh_set_proposal has not been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned sw = mh_step_word(step_index);
+    // fp64: the block is drawn into the engine's buffer first (update3_kernel reads every segment from memory)
+    if (!xi && e.cfg.dtype == CESX_F64) {
+        TRY(launch_noise(e, sw, e.d_mh_xi, s));
+        xi = e.d_mh_xi;
+    }
+    return launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.d_mh_W, .Wf = e.d_mh_Wf, .ktot = e.kp,
+                                         .src = {{xi, e.p, xi ? 0 : 1, 1}}, .nsrc = 1, .add1 = {U, nullptr, e.mh_a}, .out = P,
+                                         .step_index = sw}, s);
+}
+
+int cesx_mh_accept(cesx_handle h, uint64_t step_index, void* U, const void* P, const void* GP, const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U || !P || !GP) { e.err = "cesx_mh_accept: null pointer"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    if (e.mh_kind < 0 || !e.mh_started) { e.err = "cesx_mh_accept: cesx_mh_start has not been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(mh_score(e, false, P, GP, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    ++e.mh_steps;
+    return CESX_OK;
+}
+
+int cesx_mh_stats(cesx_handle h, unsigned long long* steps, double* rate, unsigned long long* per_chain) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!steps || !rate) { e.err = "cesx_mh_stats: null pointer"; return CESX_EINVAL; }
+    if (!e.mh_started) { e.err = "cesx_mh_stats: cesx_mh_start has not been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    std::vector<unsigned long long> c((size_t)e.J);
+    CESX_HIP(hipDeviceSynchronize());
+    CESX_HIP(hipMemcpy(c.data(), e.d_mh_cnt, (size_t)e.J * 8, hipMemcpyDeviceToHost));
+    unsigned long long sum = 0;
+    for (unsigned long long v : c) sum += v;
+    *steps = e.mh_steps;
+    *rate = e.mh_steps ? (double)sum / ((double)e.mh_steps * (double)e.J) : 0.0;
+    if (per_chain) std::memcpy(per_chain, c.data(), (size_t)e.J * 8);
+    return CESX_OK;
 }
 
 int cesx_profile_enable(cesx_handle h, int on) {

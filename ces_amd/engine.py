@@ -19,6 +19,7 @@ F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
 ABI_VERSION = 1
+MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
            "cesx_step", "cesx_result", "cesx_moments_len", "cesx_colsum", "cesx_set_shift",
@@ -28,7 +29,8 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_prefetch_noise", "cesx_forward_set_lineal", "cesx_forward_apply", "cesx_moments_uu_chol", "cesx_debug_poll_recoveries", "cesx_comm_unique_id", "cesx_comm_init", "cesx_comm_destroy", "cesx_comm_nranks",
            "cesx_comm_stats", "cesx_allreduce_head", "cesx_allreduce_tail", "cesx_allreduce_whole", "cesx_allreduce_sum", "cesx_allreduce_max", "cesx_moments_uu_handover", "cesx_debug_gram_plan",
            "cesx_profile_clock", "cesx_calibrate_mfma", "cesx_profile_gap", "cesx_moments_rest_lineal", "cesx_copy_cols_async",
-           "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count")
+           "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count",
+           "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats")
 
 
 class Config(C.Structure):
@@ -159,6 +161,11 @@ def load_library(path=None):
     lib.cesx_profile_gap.argtypes = [vp, dp]
     lib.cesx_copy_cols_async.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, i32, vp]
     lib.cesx_calibrate_mfma.argtypes = [vp, C.c_double, dp, dp, vp]
+    lib.cesx_mh_set_proposal.argtypes = [vp, i32, dp, C.c_double]
+    lib.cesx_mh_start.argtypes = [vp, vp, vp, vp]
+    lib.cesx_mh_propose.argtypes = [vp, u64, vp, vp, vp, vp]
+    lib.cesx_mh_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+    lib.cesx_mh_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), dp, C.POINTER(C.c_ulonglong)]
     if lib.cesx_abi_version() != ABI_VERSION:
         raise ImportError("libcesx.so ABI %d != binding ABI %d" % (lib.cesx_abi_version(), ABI_VERSION))
     if path == LIB_PATH:
@@ -767,6 +774,51 @@ class Engine:
             self._check(self.lib.cesx_forward_apply(self._h, U.data_ptr(), out.data_ptr(), self._stream()))
         self._keep_fwd = (U, out)
         return out
+
+    # -- Metropolis-Hastings over the columns (include/cesx.h, cesx_mh_*; ces_amd/sample.py drives it) --
+    def mh_set_proposal(self, update, S, beta=0.5):
+        """The proposal of MCMC.model_mh: update None (random walk, P = U + S xi) or 'pCN' (P = sqrt(1 - beta^2) U +
+        sqrt(beta) S xi); S the p x p lower-triangular scales (cesx_mh_set_proposal)."""
+        if update not in MH_KINDS:
+            raise ValueError("unknown MH update %r" % (update,))
+        S = np.ascontiguousarray(np.asarray(S, dtype=np.float64).reshape(self.p, self.p))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_set_proposal(self._h, MH_KINDS[update], _dptr(S), float(beta)))
+
+    def mh_start(self, U, G):
+        """phi of the current states U with their forward map G; the accept counters cleared (cesx_mh_start)."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_start(self._h, U.data_ptr(), G.data_ptr(), self._stream()))
+        self._keep_mh = (U, G)
+
+    def mh_propose(self, step_index, U, xi=None, out=None):
+        """P = a U + b S xi (cesx_mh_propose); xi None: drawn on device in the MH counter domain of step_index."""
+        out = self.empty(self.p) if out is None else out
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_propose(self._h, int(step_index), U.data_ptr(),
+                                                 None if xi is None else xi.data_ptr(), out.data_ptr(), self._stream()))
+        self._keep_mh_p = (U, xi, out)
+        return out
+
+    def mh_accept(self, step_index, U, P, GP, logu=None):
+        """phi(P), the test log u < phi(U) - phi(P), U := P on the accepted columns (cesx_mh_accept); logu None: the
+        device uniform of step_index, else a float64 device tensor of J values."""
+        if logu is not None:
+            assert logu.dtype == torch.float64 and logu.numel() == self.J and logu.is_contiguous()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_accept(self._h, int(step_index), U.data_ptr(), P.data_ptr(), GP.data_ptr(),
+                                                None if logu is None else logu.data_ptr(), self._stream()))
+        self._keep_mh_a = (U, P, GP, logu)
+
+    def mh_stats(self, per_chain=False):
+        """(accept calls since mh_start, overall accept rate[, per-chain counters]) (cesx_mh_stats; synchronises)."""
+        steps, rate = C.c_ulonglong(0), C.c_double(0.0)
+        buf = np.zeros(self.J, dtype=np.uint64) if per_chain else None
+        self._check(self.lib.cesx_mh_stats(self._h, C.byref(steps), C.byref(rate),
+                                           None if buf is None else buf.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        if per_chain:
+            return int(steps.value), rate.value, buf
+        return int(steps.value), rate.value
 
     def profile_enable(self, on=True):
         """on: False / True, 2 = bind only the events cesx_profile_gap needs, 3 / 4 = the update / the moments

@@ -369,6 +369,47 @@ int cesx_forward_lineal(cesx_handle h, const void* A_dev, const void* b_dev,
 int cesx_forward_set_lineal(cesx_handle h, const void* A_dev, const void* b_dev, void* stream);
 int cesx_forward_apply(cesx_handle h, const void* U_dev, void* G_dev, void* stream);
 
+/* ---- Sample: Metropolis-Hastings over the columns (ces/sample.py) -------
+   MCMC.model_mh (ces/sample.py:121-196) runs ONE host chain; here every column of the handle's (p, J_local) layout is an
+   independent chain of it (no communication between chains).  Per step:
+       cesx_mh_propose   P = a U + b S xi                       (MCMC.random_walk / MCMC.pCN, :198-202)
+       (the caller's forward map G_P = G(P): cesx_forward_apply, or any (n x J_local) device array)
+       cesx_mh_accept    phi(P), the test log u < phi(U) - phi(P) (:188) and, for the accepted columns, U := P
+   with  RW:  a = 1,              b = 1       (S = delta chol(cov(enka.Ustar)) or delta I, :122-126)
+         pCN: a = sqrt(1 - beta^2), b = sqrt(beta)  (S = chol(prior.cov), :127-129; the reference's sqrt(beta), :202)
+   phi(u) = 1/2 (g - y)^T Gamma^{-1} (g - y) + 1/2 (u - mu)^T Sigma^{-1} (u - mu)   (:141-152 / :170-180; the prior term for
+   RW only -- pCN is prior invariant, :143-145; the log-density's constant cancels in the test).  y, Gamma, mu, Sigma are those
+   of cesx_set_problem: a dense Gamma is whitened away as in the ensemble update (G_P whitened into the engine's buffer, y~),
+   a dense Sigma is scored through w = L_Sigma^{-1} (u - mu), one more triangular p x p x J product per step.  phi and the
+   test run in fp64 in a fixed summation order: runs are bit-reproducible.
+   Noise (xi_dev / logu_dev NULL): Philox4x32-10 keyed like cesx_draw_noise, but in a counter domain of its own -- the step
+   word of every MH draw is step_index | 2^31 (MH step indices must be < 2^31; the ensemble update's steps stay below 2^31), so
+   no MH block repeats a block of the ensemble update.  xi rows use the row-quad words 0 .. ceil(p/4) - 1 as cesx_draw_noise does;
+   the uniform of chain j is drawn from row-quad word 0xffffffff, which no xi row uses: u = (53 bits of (x, y) + 1/2) 2^-53.
+   Unlike the rest of the ABI, cesx_mh_accept WRITES U (the accepted columns).  A later cesx_set_problem drops the proposal
+   (cesx_mh_set_proposal again, then cesx_mh_start). */
+#define CESX_MH_RW   0
+#define CESX_MH_PCN  1
+/* The proposal: kind CESX_MH_RW | CESX_MH_PCN, S_host the p x p LOWER-triangular scale matrix (row-major fp64, computed by the
+   caller exactly as ces/sample.py:122-129 does; CESX_EINVAL when an entry above the diagonal is nonzero), beta the pCN
+   parameter (0 < beta <= 1; ignored for RW).  Needs the problem (cesx_set_problem). */
+int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S_host, double beta);
+/* phi of the current states U_dev (p x J_local) with their forward map G_dev (n x J_local) into engine-owned fp64 memory, and
+   the per-chain accept counters cleared.  (ces/sample.py:131-152; a resume that keeps the reference's phi of the start point
+   passes the start states here and the resumed states to the steps.) */
+int cesx_mh_start(cesx_handle h, const void* U_dev, const void* G_dev, void* stream);
+/* P_dev = a U_dev + b S xi (p x J_local, must not alias U_dev); xi_dev the injected N(0,1) block (p x J_local, standing in for
+   np.random.normal(0, 1, p) of :199 / :202), or NULL to draw it on device. */
+int cesx_mh_propose(cesx_handle h, uint64_t step_index, const void* U_dev, const void* xi_dev, void* P_dev, void* stream);
+/* phi(P) from P_dev and G_P_dev = G(P) (n x J_local), the test against logu_dev (J_local fp64 values of log u, standing in for
+   np.log(np.random.uniform()) of :188) or, NULL, the device uniform of step_index; accepted columns: U_dev := P_dev, phi
+   := phi(P), counter + 1. */
+int cesx_mh_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* P_dev, const void* G_P_dev,
+                   const double* logu_dev, void* stream);
+/* cesx_mh_accept calls since cesx_mh_start, the overall accept rate (accepted / (steps J_local)) and, per_chain_host != NULL,
+   the J_local counters.  Synchronises. */
+int cesx_mh_stats(cesx_handle h, unsigned long long* steps, double* rate, unsigned long long* per_chain_host);
+
 /* ---- host staging ------------------------------------------------------ */
 
 /* A COLUMN block of a row-major (rows, J) ensemble between pinned host memory and the device, asynchronously on
