@@ -438,6 +438,19 @@ struct Engine {
     void *d_mh_xi = nullptr;                        // fp64: [p][J] the step's noise block (update3_kernel reads segments from memory)
     double* d_mh_phi = nullptr;                     // [J] phi of the chains' current states
     unsigned long long* d_mh_cnt = nullptr;         // [J] accepted proposals per chain
+    // ---- GP emulator over the columns (cesx_gp_*, kernels_gp.hip) ----
+    int gp_n = 0, gp_Jt = 0, gp_Jp = 0;             // GPs, training points, training points rounded up to 16 (0: no emulator)
+    size_t gp_li_len = 0;                           // doubles of one GP's packed L^{-1} (gp_Jp/16 (gp_Jp/16 + 1)/2 blocks of 256)
+    double *d_gp_A = nullptr;                       // [n][p][p] the input maps A_i (lower triangular)
+    double *d_gp_c = nullptr;                       // [p] the input shift c
+    double *d_gp_Z = nullptr;                       // [n][Jt][p] the mapped training points
+    double *d_gp_par = nullptr;                     // [n][4] sigma^2, sn^2, mean bias, kernel family
+    double *d_gp_mw = nullptr;                      // [n][p] the affine mean's weights over z
+    double *d_gp_alpha = nullptr;                   // [n][Jp] alpha, zero padded
+    double *d_gp_Li = nullptr;                      // [n][gp_li_len] L^{-1} in v_mfma_f64_16x16x4 A-operand order
+    double *d_gp_ws = nullptr;                      // the K* panels of the launches that do not fit in LDS
+    size_t gp_ws_len = 0;
+    double *d_gp_LSi = nullptr;                     // [p][p] L_Sigma^{-1} of the problem (cesx_gp_start)
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -633,6 +646,12 @@ int launch_calibrate(Engine& e, double target_ms, double* tflops, double* clock_
 // kernels_mh.hip: phi of the states X (with their forward map G, whitened when Gamma is dense) of every chain; start: into
 // Engine::d_mh_phi, counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_mh_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s);
+// kernels_gp.hip: the GP means (and variances, var_out != nullptr) of the states X (p x J, engine dtype) into fp64 (gp_n x J)
+int launch_gp_predict(Engine& e, const void* X, double* mean, double* var, bool nugget, hipStream_t s);
+// kernels_gp.hip: phi of the states X from the GP rows (mode CESX_GP_GAMMA / _VAR / _GAMMA_VAR); start: into d_mh_phi,
+// counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
+int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double* mean, const double* var, void* U,
+                    const double* logu, unsigned step, hipStream_t s);
 
 // Event pair for one profiled launch (cesx_profile_*).  bound = false: the pair is RECORDED around the launch (two
 // marker packets: they delay the stream by ~6 us each and the interval includes that).  bound = true: the caller

@@ -427,7 +427,8 @@ void cesx_destroy(cesx_handle h) {
                     e.d_t1, e.d_t2, e.d_t3, e.d_t4, e.d_spec, e.d_ns_x[0][0], e.d_ns_x[0][1], e.d_ns_x[1][0], e.d_ns_x[1][1], e.d_ns_r[0], e.d_ns_r[1], e.d_ns_r[2],
                     e.d_ns_parts, e.d_ns_skip, e.d_mv, e.d_part, e.d_scal, e.d_absmax,
                     e.d_absmax_part, e.d_clk, e.d_cholflag, e.d_lag, e.d_A64, e.d_b64, e.d_lvec, e.d_Wq, e.d_ticket,
-                    e.d_mh_W, e.d_mh_Wf, e.d_mh_Li, e.d_mh_Li_f, e.d_mh_lb, e.d_mh_w, e.d_mh_xi, e.d_mh_phi, e.d_mh_cnt};
+                    e.d_mh_W, e.d_mh_Wf, e.d_mh_Li, e.d_mh_Li_f, e.d_mh_lb, e.d_mh_w, e.d_mh_xi, e.d_mh_phi, e.d_mh_cnt,
+                    e.d_gp_A, e.d_gp_c, e.d_gp_Z, e.d_gp_par, e.d_gp_mw, e.d_gp_alpha, e.d_gp_Li, e.d_gp_ws, e.d_gp_LSi};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     for (int w = 0; w < 2; ++w)
@@ -1065,6 +1066,104 @@ int cesx_mh_stats(cesx_handle h, unsigned long long* steps, double* rate, unsign
     *steps = e.mh_steps;
     *rate = e.mh_steps ? (double)sum / ((double)e.mh_steps * (double)e.J) : 0.0;
     if (per_chain) std::memcpy(per_chain, c.data(), (size_t)e.J * 8);
+    return CESX_OK;
+}
+
+// ---- Emulate: GP prediction and the GP sampler over the columns (ces/emulate.py, ces/sample.py:17-119; kernels_gp.hip) ----
+
+int cesx_gp_set(cesx_handle h, const cesx_gp_desc* d) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!d || d->struct_bytes != sizeof(cesx_gp_desc)) { e.err = "cesx_gp_set: bad cesx_gp_desc"; return CESX_EINVAL; }
+    if (!d->A || !d->c || !d->Z || !d->family || !d->par || !d->mw || !d->alpha || !d->Li) { e.err = "cesx_gp_set: null pointer"; return CESX_EINVAL; }
+    if (d->n_gp < 1 || d->J_t < 1) { e.err = "cesx_gp_set: n_gp and J_t must be >= 1"; return CESX_EINVAL; }
+    const int n = d->n_gp, Jt = d->J_t, p = e.p, Jp = (Jt + 15) / 16 * 16, NB = Jp / 16;
+    for (int i = 0; i < n; ++i)
+        if (d->family[i] < 0 || d->family[i] > 3) { e.err = "cesx_gp_set: unknown kernel family"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    CESX_HIP(hipDeviceSynchronize());          // (the old image may be read by launches still in flight)
+    double** bufs[] = {&e.d_gp_A, &e.d_gp_c, &e.d_gp_Z, &e.d_gp_par, &e.d_gp_mw, &e.d_gp_alpha, &e.d_gp_Li};
+    for (double** b : bufs) if (*b) { CESX_HIP(hipFree(*b)); *b = nullptr; }
+    e.gp_n = 0;
+    const size_t li_len = (size_t)NB * (NB + 1) / 2 * 256;
+    std::vector<double> par((size_t)n * 4), alpha((size_t)n * Jp, 0.0), Li((size_t)n * li_len, 0.0);
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) par[(size_t)i * 4 + k] = d->par[(size_t)i * 3 + k];
+        par[(size_t)i * 4 + 3] = (double)d->family[i];
+        for (int t = 0; t < Jt; ++t) alpha[(size_t)i * Jp + t] = d->alpha[(size_t)i * Jt + t];
+        // L^{-1} in the A-operand order of v_mfma_f64_16x16x4_f64: block row b, k-step k4, lane l holds
+        // L^{-1}[16 b + (l & 15)][4 k4 + (l >> 4)] (zero above the diagonal and past J_t)
+        const double* L = d->Li + (size_t)i * Jt * Jt;
+        double* o = Li.data() + (size_t)i * li_len;
+        for (int b = 0; b < NB; ++b)
+            for (int k4 = 0; k4 < (b + 1) * 4; ++k4)
+                for (int l = 0; l < 64; ++l) {
+                    const int row = 16 * b + (l & 15), col = 4 * k4 + (l >> 4);
+                    *o++ = row < Jt && col <= row ? L[(size_t)row * Jt + col] : 0.0;
+                }
+    }
+    TRY(dmalloc(e, &e.d_gp_A, (size_t)n * p * p * 8)); TRY(upload(e, e.d_gp_A, d->A, (size_t)n * p * p * 8));
+    TRY(dmalloc(e, &e.d_gp_c, (size_t)p * 8)); TRY(upload(e, e.d_gp_c, d->c, (size_t)p * 8));
+    TRY(dmalloc(e, &e.d_gp_Z, (size_t)n * Jt * p * 8)); TRY(upload(e, e.d_gp_Z, d->Z, (size_t)n * Jt * p * 8));
+    TRY(dmalloc(e, &e.d_gp_par, par.size() * 8)); TRY(upload(e, e.d_gp_par, par.data(), par.size() * 8));
+    TRY(dmalloc(e, &e.d_gp_mw, (size_t)n * p * 8)); TRY(upload(e, e.d_gp_mw, d->mw, (size_t)n * p * 8));
+    TRY(dmalloc(e, &e.d_gp_alpha, alpha.size() * 8)); TRY(upload(e, e.d_gp_alpha, alpha.data(), alpha.size() * 8));
+    TRY(dmalloc(e, &e.d_gp_Li, Li.size() * 8)); TRY(upload(e, e.d_gp_Li, Li.data(), Li.size() * 8));
+    e.gp_Jt = Jt; e.gp_Jp = Jp; e.gp_li_len = li_len;
+    e.gp_n = n;
+    return CESX_OK;
+}
+
+int cesx_gp_predict(cesx_handle h, const void* X, double* mean, double* var, int nugget, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!X || !mean) { e.err = "cesx_gp_predict: null pointer"; return CESX_EINVAL; }
+    if (e.gp_n < 1) { e.err = "cesx_gp_predict: cesx_gp_set has not been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    return launch_gp_predict(e, X, mean, var, nugget != 0, (hipStream_t)stream);
+}
+
+static int gp_check_mode(Engine& e, int mode, const double* mean, const double* var) {
+    if (mode != CESX_GP_GAMMA && mode != CESX_GP_VAR && mode != CESX_GP_GAMMA_VAR) { e.err = "cesx_gp: unknown likelihood mode"; return CESX_EINVAL; }
+    if (!mean || (mode != CESX_GP_GAMMA && !var)) { e.err = "cesx_gp: null pointer"; return CESX_EINVAL; }
+    if (mode != CESX_GP_GAMMA && e.whiten) { e.err = "cesx_gp: the variance modes need a diagonal Gamma"; return CESX_EINVAL; }
+    if (e.gp_n != e.n) { e.err = "cesx_gp: the emulator's n_gp differs from n_obs"; return CESX_EINVAL; }
+    return CESX_OK;
+}
+
+int cesx_gp_start(cesx_handle h, int mode, const void* U, const double* mean, const double* var, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U) { e.err = "cesx_gp_start: null pointer"; return CESX_EINVAL; }
+    if (e.mh_kind < 0 || !e.problem_set) { e.err = "cesx_gp_start: no proposal (cesx_mh_set_proposal after cesx_set_problem)"; return CESX_ESTATE; }
+    TRY(gp_check_mode(e, mode, mean, var));
+    SET_DEVICE(e);
+    FLUSH(e);
+    if (!e.diag_sigma) {
+        CESX_HIP(hipDeviceSynchronize());
+        if (!e.d_gp_LSi) TRY(dmalloc(e, &e.d_gp_LSi, (size_t)e.p * e.p * 8));
+        TRY(upload(e, e.d_gp_LSi, e.h_LSi.data(), (size_t)e.p * e.p * 8));
+    }
+    TRY(launch_gp_score(e, mode, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
+    e.mh_started = true;
+    e.mh_steps = 0;
+    return CESX_OK;
+}
+
+int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U, const void* P, const double* mean, const double* var,
+                   const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U || !P) { e.err = "cesx_gp_accept: null pointer"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_gp_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    if (e.mh_kind < 0 || !e.mh_started) { e.err = "cesx_gp_accept: cesx_gp_start has not been called"; return CESX_ESTATE; }
+    TRY(gp_check_mode(e, mode, mean, var));
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_gp_score(e, mode, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    ++e.mh_steps;
     return CESX_OK;
 }
 

@@ -1,0 +1,503 @@
+"""The Emulate stage without GPflow: ``ces/emulate.py`` (:11-105) restated, plus the exact GP regression it runs on.
+
+Drop-in functions (same signatures, kwargs, shapes and quirks as the reference):
+  ``predict_gps(enka, X, mute_bar=True, **kwargs)``   one independent GP per output; '' when ``enka`` has no ``gpmodels``;
+                                                      inputs scaled whenever ``enka`` has an attribute ``scaled``;
+                                                      ``nugget`` picks ``predict_y`` (True) or ``predict_f``; ``pca_tools``
+                                                      and ``separable`` branches kept.
+  ``scale_gppreds(gpmeans, gpvars, Gmean, Gstd)``     the log-normal back-transform of outputs 2..6.
+  ``scale_ensemble(enka, factor=2.)``                 sets ``scale['mean']`` and ``scale['cov']``, then raises
+                                                      ``AttributeError`` on ``enka.scale_cov``, as the reference does.
+
+The GP (the notebooks' ``emulate(enki)`` needs GPflow 1.x; this is its exact-GPR subset in numpy, fp64):
+  ``GPR(X, Y, kern, mean_function=None)`` with kernels ``RBF``, ``Matern12``, ``Matern32``, ``Matern52`` (``input_dim``,
+  ``ARD``, ``lengthscales``, ``variance``; defaults 1.0), mean functions ``Zero``, ``Constant``, ``Linear``, and
+  ``m.likelihood.variance`` (default 1.0).  ``predict_f`` / ``predict_y`` return ``(mean (N, 1), var (N, 1))``:
+      L = chol(K + sn2 I),  alpha = (K + sn2 I)^{-1} (y - m(X)),
+      mean = K*^T alpha + m(x*),  var = k(x*, x*) - ||L^{-1} k*||^2  (+ sn2 for predict_y),
+  with r from direct coordinate differences of the scaled inputs (r = 0 exactly at a training point).
+  ``ScipyOptimizer().minimize(m, maxiter=...)`` maximises the log marginal likelihood with L-BFGS-B and its analytic
+  gradient, the positive parameters through softplus with a 1e-6 floor (GPflow 1.x's default ``positive`` transform as far
+  as can be told without GPflow).  ``train_gps(enka, kernel='Matern32', ...)`` is the notebook's ``emulate(enki)``.
+
+Build-only: ``predict_gps(..., device=True)`` evaluates the GPs on the GPU (``cesx_gp_predict``, kernels_gp.hip).
+"""
+import numpy as np
+from scipy import optimize
+
+try:
+    from tqdm.autonotebook import tqdm
+except Exception:                      # pragma: no cover - tqdm is optional plumbing
+    class tqdm(object):
+        def __init__(self, it=None, **_kw):
+            self.it = it
+
+        def __iter__(self):
+            return iter(self.it)
+
+        @staticmethod
+        def write(s):
+            print(s)
+
+FLOOR = 1e-6                           # the positive transform's lower bound
+
+
+def _softplus(u):
+    return np.logaddexp(0.0, u)
+
+
+def _softplus_inv(t):
+    x = np.asarray(t, dtype=np.float64) - FLOOR
+    return np.where(x > 30.0, x, np.log(np.expm1(np.maximum(x, 1e-300))))
+
+
+def _sigmoid(u):
+    return 0.5 * (1.0 + np.tanh(0.5 * u))
+
+
+# -- kernels ----------------------------------------------------------------------------------------------------------
+class Stationary(object):
+    """k(x, x') = variance f(r), r^2 = sum_d ((x_d - x'_d) / l_d)^2 (one l for all d unless ARD)."""
+    family = None
+
+    def __init__(self, input_dim, variance=1.0, lengthscales=1.0, ARD=False, active_dims=None):
+        self.input_dim = int(input_dim)
+        self.ARD = bool(ARD)
+        self.variance = float(variance)
+        ls = np.asarray(lengthscales, dtype=np.float64)
+        if self.ARD:
+            ls = np.ones(self.input_dim) * ls
+        elif ls.size != 1:
+            raise ValueError("lengthscales: one value without ARD")
+        self.lengthscales = ls.reshape(-1) if self.ARD else float(ls)
+
+    def _ls(self):
+        return np.broadcast_to(np.asarray(self.lengthscales, dtype=np.float64), (self.input_dim,))
+
+    def _scaled_diff(self, X, X2):
+        ls = self._ls()
+        return X[:, None, :] / ls - X2[None, :, :] / ls        # (N, N2, d), direct differences
+
+    def K(self, X, X2=None):
+        X = np.asarray(X, dtype=np.float64)
+        X2 = X if X2 is None else np.asarray(X2, dtype=np.float64)
+        d = self._scaled_diff(X, X2)
+        return self.variance * self.f(np.sqrt((d * d).sum(axis=2)))
+
+    def Kdiag(self, X):
+        return np.full(np.asarray(X).shape[0], self.variance)
+
+    def grads(self, X):
+        """K and dK/d(variance), dK/d(lengthscales) (a list: one per lengthscale entry)."""
+        d = self._scaled_diff(X, X)
+        r = np.sqrt((d * d).sum(axis=2))
+        K = self.variance * self.f(r)
+        g = self.variance * self.dfr_over_r(r)               # dk/dr / r  (finite at r = 0)
+        ls = self._ls()
+        # dr/dl_d = -(diff_d / l_d)^2 / (l_d r)  ->  dk/dl_d = -g (diff_d / l_d)^2 / l_d
+        dl = [-g * d[:, :, q] ** 2 / ls[q] for q in range(self.input_dim)]
+        if not self.ARD:
+            dl = [sum(dl)]
+        return K, K / self.variance, dl
+
+
+class RBF(Stationary):
+    family = 0
+
+    @staticmethod
+    def f(r):
+        return np.exp(-0.5 * r * r)
+
+    @staticmethod
+    def dfr_over_r(r):
+        return -np.exp(-0.5 * r * r)
+
+
+class Matern12(Stationary):
+    family = 1
+
+    @staticmethod
+    def f(r):
+        return np.exp(-r)
+
+    @staticmethod
+    def dfr_over_r(r):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = -np.exp(-r) / r
+        return np.where(r > 0, out, 0.0)      # (its (diff / l)^2 factor is 0 where r is)
+
+
+class Matern32(Stationary):
+    family = 2
+
+    @staticmethod
+    def f(r):
+        s = np.sqrt(3.0) * r
+        return (1.0 + s) * np.exp(-s)
+
+    @staticmethod
+    def dfr_over_r(r):
+        return -3.0 * np.exp(-np.sqrt(3.0) * r)
+
+
+class Matern52(Stationary):
+    family = 3
+
+    @staticmethod
+    def f(r):
+        s = np.sqrt(5.0) * r
+        return (1.0 + s + s * s / 3.0) * np.exp(-s)
+
+    @staticmethod
+    def dfr_over_r(r):
+        s = np.sqrt(5.0) * r
+        return -(5.0 / 3.0) * (1.0 + s) * np.exp(-s)
+
+
+class kernels(object):                 # gp.kernels.Matern32(...) reads the same
+    RBF, Matern12, Matern32, Matern52 = RBF, Matern12, Matern32, Matern52
+
+
+# -- mean functions ---------------------------------------------------------------------------------------------------
+class Zero(object):
+    def __call__(self, X):
+        return np.zeros((np.asarray(X).shape[0], 1))
+
+    def params(self):
+        return []
+
+
+class Constant(object):
+    def __init__(self, c=None):
+        self.c = np.zeros(1) if c is None else np.asarray(c, dtype=np.float64).reshape(-1)
+
+    def __call__(self, X):
+        return np.ones((np.asarray(X).shape[0], 1)) * self.c
+
+    def params(self):
+        return ["c"]
+
+
+class Linear(object):
+    def __init__(self, A=None, b=None):
+        self.A = np.ones((1, 1)) if A is None else np.atleast_2d(np.asarray(A, dtype=np.float64))
+        self.b = np.zeros(1) if b is None else np.asarray(b, dtype=np.float64).reshape(-1)
+
+    def __call__(self, X):
+        return np.asarray(X, dtype=np.float64) @ self.A + self.b
+
+    def params(self):
+        return ["A", "b"]
+
+
+class mean_functions(object):
+    Zero, Constant, Linear = Zero, Constant, Linear
+
+
+class _Gaussian(object):
+    def __init__(self, variance=1.0):
+        self.variance = float(variance)
+
+
+# -- the model --------------------------------------------------------------------------------------------------------
+class GPR(object):
+    """Exact GP regression with a Gaussian likelihood (GPflow 1.x ``gp.models.GPR``)."""
+
+    def __init__(self, X, Y, kern, mean_function=None):
+        self.X = np.array(X, dtype=np.float64, ndmin=2)
+        self.Y = np.array(Y, dtype=np.float64, ndmin=2)
+        if self.Y.shape[0] != self.X.shape[0]:
+            self.Y = self.Y.reshape(self.X.shape[0], -1)
+        self.kern = kern
+        self.mean_function = Zero() if mean_function is None else mean_function
+        self.likelihood = _Gaussian()
+
+    def compile(self):                 # (GPflow 1.x's build step: nothing to do)
+        return self
+
+    def _factor(self):
+        K = self.kern.K(self.X) + self.likelihood.variance * np.eye(self.X.shape[0])
+        L = np.linalg.cholesky(K)
+        r = self.Y - self.mean_function(self.X)
+        alpha = np.linalg.solve(L.T, np.linalg.solve(L, r))
+        return L, alpha
+
+    def predict_f(self, Xnew):
+        Xnew = np.array(Xnew, dtype=np.float64, ndmin=2)
+        L, alpha = self._factor()
+        Ks = self.kern.K(self.X, Xnew)                                  # (J_t, N)
+        mean = Ks.T @ alpha + self.mean_function(Xnew)
+        W = np.linalg.solve(L, Ks)                                      # L^{-1} k*
+        var = self.kern.Kdiag(Xnew) - (W * W).sum(axis=0)
+        return mean, var.reshape(-1, 1)
+
+    def predict_y(self, Xnew):
+        mean, var = self.predict_f(Xnew)
+        return mean, var + self.likelihood.variance
+
+    def compute_log_likelihood(self):
+        return self.log_marginal_likelihood()
+
+    def log_marginal_likelihood(self):
+        L, alpha = self._factor()
+        r = self.Y - self.mean_function(self.X)
+        N = self.X.shape[0]
+        return float(-0.5 * (r * alpha).sum() - self.Y.shape[1] * np.log(np.diag(L)).sum()
+                     - 0.5 * N * self.Y.shape[1] * np.log(2 * np.pi))
+
+    # the free parameters: positive ones first (kernel variance, lengthscales, likelihood variance), then the mean's
+    def _get(self):
+        pos = np.concatenate([[self.kern.variance], np.atleast_1d(self.kern.lengthscales), [self.likelihood.variance]])
+        free = [np.asarray(getattr(self.mean_function, k), dtype=np.float64).ravel() for k in self.mean_function.params()]
+        return pos, (np.concatenate(free) if free else np.zeros(0))
+
+    def _set(self, pos, free):
+        self.kern.variance = float(pos[0])
+        nl = np.atleast_1d(self.kern.lengthscales).size
+        self.kern.lengthscales = np.array(pos[1:1 + nl]) if self.kern.ARD else float(pos[1])
+        self.likelihood.variance = float(pos[1 + nl])
+        o = 0
+        for k in self.mean_function.params():
+            cur = np.asarray(getattr(self.mean_function, k))
+            setattr(self.mean_function, k, np.array(free[o:o + cur.size]).reshape(cur.shape))
+            o += cur.size
+
+    def log_marginal_likelihood_and_grad(self):
+        """(lml, d lml / d[positive params..., mean params...]) at the current parameters."""
+        N = self.X.shape[0]
+        K, dvar, dls = self.kern.grads(self.X)
+        Ky = K + self.likelihood.variance * np.eye(N)
+        L = np.linalg.cholesky(Ky)
+        r = self.Y - self.mean_function(self.X)
+        alpha = np.linalg.solve(L.T, np.linalg.solve(L, r))
+        Li = np.linalg.solve(L, np.eye(N))
+        Kinv = Li.T @ Li
+        D = self.Y.shape[1]
+        lml = float(-0.5 * (r * alpha).sum() - D * np.log(np.diag(L)).sum() - 0.5 * N * D * np.log(2 * np.pi))
+        Q = alpha @ alpha.T - D * Kinv                 # d lml / dK = Q / 2
+        g = [0.5 * (Q * dvar).sum()] + [0.5 * (Q * d).sum() for d in dls] + [0.5 * np.trace(Q)]
+        mg = []
+        for k in self.mean_function.params():
+            if k == "c":
+                mg.append(alpha.sum(axis=0))
+            elif k == "A":
+                mg.append((self.X.T @ alpha).ravel())
+            elif k == "b":
+                mg.append(alpha.sum(axis=0))
+        return lml, np.concatenate([np.array(g)] + [np.ravel(v) for v in mg])
+
+
+class ScipyOptimizer(object):
+    """L-BFGS-B on minus the log marginal likelihood (GPflow 1.x ``gp.train.ScipyOptimizer``)."""
+
+    def __init__(self, method="L-BFGS-B", **kwargs):
+        self.method = method
+        self.kwargs = kwargs
+
+    def minimize(self, model, maxiter=1000, disp=False, **kwargs):
+        pos0, free0 = model._get()
+        npos = pos0.size
+        x0 = np.concatenate([_softplus_inv(pos0), free0])
+
+        def unpack(x):
+            return _softplus(x[:npos]) + FLOOR, x[npos:]
+
+        def fun(x):
+            pos, free = unpack(x)
+            model._set(pos, free)
+            try:
+                lml, g = model.log_marginal_likelihood_and_grad()
+            except np.linalg.LinAlgError:
+                return 1e300, np.zeros_like(x)
+            g = g.copy()
+            g[:npos] *= _sigmoid(x[:npos])
+            return -lml, -g
+
+        res = optimize.minimize(fun, x0, jac=True, method=self.method,
+                                options=dict(maxiter=int(maxiter), disp=disp), **self.kwargs)
+        model._set(*unpack(res.x))
+        self.result = res
+        return res
+
+
+class train(object):
+    ScipyOptimizer = ScipyOptimizer
+
+
+class models(object):
+    GPR = GPR
+
+
+_KERNELS = {"RBF": RBF, "Matern12": Matern12, "Matern32": Matern32, "Matern52": Matern52}
+
+
+def train_gps(enka, kernel="Matern32", ARD=True, mean_function=None, maxiter=1000, **kwargs):
+    """The notebooks' ``emulate(enki)``: one GPR per row of ``enka.Gstar[:n_obs]``, all on ``enka.Ustar.T`` (scaled by
+    ``enka.scale`` when ``enka`` has ``scaled``), fitted by ``ScipyOptimizer``; stored in (and returned as)
+    ``enka.gpmodels``.  ``mean_function``: None (zero), 'Constant', 'Linear', or a callable making one per output."""
+    X = np.asarray(enka.Ustar, dtype=np.float64).T
+    if hasattr(enka, "scaled"):
+        X = np.linalg.solve(enka.scale["cov"], X.T - enka.scale["mean"]).T
+    Kern = _KERNELS[kernel] if isinstance(kernel, str) else kernel
+    enka.gpmodels = []
+    for y in np.asarray(enka.Gstar, dtype=np.float64)[range(enka.n_obs)]:
+        k = Kern(input_dim=enka.p, ARD=ARD)
+        if mean_function is None:
+            mf = None
+        elif mean_function == "Constant":
+            mf = Constant()
+        elif mean_function == "Linear":
+            mf = Linear(np.ones((enka.p, 1)))
+        else:
+            mf = mean_function()
+        m = GPR(X, y[:, np.newaxis], k, mean_function=mf)
+        ScipyOptimizer().minimize(m, maxiter=maxiter)
+        enka.gpmodels.append(m)
+    return enka.gpmodels
+
+
+# -- ces/emulate.py --------------------------------------------------------------------------------------------------
+def scale_ensemble(enka, factor=2.):
+    """ces/emulate.py:13-17, its AttributeError on ``enka.scale_cov`` included."""
+    enka.scale = {}
+    enka.scale['mean'] = enka.Ustar.mean(axis=1)[:, np.newaxis]
+    enka.scale['cov'] = factor * np.linalg.cholesky(np.cov(enka.Ustar))
+    enka.scale['X'] = np.linalg.solve(enka.scale_cov, enka.Ustar - enka.scale_mean)
+
+
+def predict_gps(enka, X, mute_bar=True, **kwargs):
+    """ces/emulate.py:19-80.  X: (n_points, d).  Build-only ``device=True``: the GPs on the GPU (module docstring)."""
+    try:
+        getattr(enka, 'gpmodels')
+    except AttributeError:
+        tqdm.write('There are no trained GP model(s) in object: %s' % enka)
+        return ''
+
+    if kwargs.get('gpmodels', None) is None:
+        gpmodels = enka.gpmodels
+    else:
+        gpmodels = kwargs.get('gpmodels', None)
+
+    if kwargs.get('device', False):
+        return _predict_gps_device(enka, X, gpmodels, kwargs)
+
+    if kwargs.get('separable', False):
+        gpmeans = np.empty(shape=(kwargs.get('model').n_obs, 1))
+        gpvars = np.empty(shape=(kwargs.get('model').n_obs, 1))
+    else:
+        gpmeans = np.empty(shape=(len(gpmodels), len(X)))
+        gpvars = np.empty(shape=(len(gpmodels), len(X)))
+
+    if kwargs.get('separable', False):
+        model = kwargs.get('model', None)
+        print(np.repeat(X, model.n_obs).reshape(-1, 1).shape)
+        print(model.obs_locs.T.shape)
+        gpmeans, gpvars = gpmodels[0].predict_y(np.hstack([np.repeat(X, model.n_obs).reshape(-1, 1), model.obs_locs.T]))
+        gpmeans, gpvars = gpmeans.flatten(), gpvars.flatten()
+    else:
+        for ii, model in tqdm(enumerate(gpmodels), desc='GP predictions', disable=mute_bar, position=0):
+            try:
+                getattr(enka, 'scaled')
+                Xs = np.linalg.solve(enka.scale['cov'], X.T - enka.scale['mean']).T
+            except AttributeError:
+                Xs = X
+            if kwargs.get('nugget', True):
+                mean_pred, var_pred = model.predict_y(Xs)
+            else:
+                mean_pred, var_pred = model.predict_f(Xs)
+
+            gpmeans[ii, :] = mean_pred.flatten()
+            gpvars[ii, :] = var_pred.flatten()
+
+        if kwargs.get('pca_tools', None) is not None:
+            pca_tools = kwargs.get('pca_tools')
+            gpmeans = pca_tools['VD_k'].dot(gpmeans) + pca_tools['mG']
+            gpvars = pca_tools['VD_k'].dot(np.diag(gpvars.flatten())).dot(pca_tools['VD_k'].T)
+
+    return [gpmeans, gpvars]
+
+
+def scale_gppreds(gpmeans, gpvars, Gmean, Gstd):
+    """ces/emulate.py:82-105."""
+    n_obs = len(gpmeans)
+    Gmeans = []
+    Gvars = []
+    for ii in range(len(gpmeans)):
+        if ii in range(2, 7):
+            mexp = np.exp(gpmeans[ii] * Gstd[ii] + Gmean[ii] + (Gstd[ii]**2 * gpvars[ii]) / 2)
+            vexp = (np.exp(Gstd[ii]**2 * gpvars[ii]) - 1.) * (mexp**2)
+        else:
+            mexp = gpmeans[ii] * Gstd[ii] + Gmean[ii]
+            vexp = Gstd[ii]**2 * gpvars[ii]
+        Gmeans.append(mexp)
+        Gvars.append(vexp)
+    return [np.asarray(Gmeans).reshape(n_obs, -1), np.asarray(Gvars).reshape(n_obs, -1)]
+
+
+# -- build-only: the GPs on the device --------------------------------------------------------------------------------
+def device_image(enka, gpmodels):
+    """What ``cesx_gp_set`` takes, in fp64: per GP the input map z = A_i (x - c) (A_i = diag(1/l_i) S^{-1}, S and c from
+    ``enka.scale`` when ``enka`` has ``scaled``, else I and 0), the mapped training points, the kernel family, sigma^2,
+    sn^2, the affine mean over z (weights, bias), alpha and L_i^{-1}.  Raises ValueError for models that are not this
+    package's GPR on shared training inputs."""
+    gpmodels = list(gpmodels)
+    if not gpmodels or not all(isinstance(m, GPR) and isinstance(m.kern, Stationary) for m in gpmodels):
+        raise ValueError("the device GP path takes this package's GPR models (ces_amd.emulate.GPR with an RBF / Matern "
+                         "kernel); run predict_gps / gp_mh on the host for other emulators")
+    X0 = gpmodels[0].X
+    p = X0.shape[1]
+    if hasattr(enka, "scaled"):
+        S = np.asarray(enka.scale["cov"], dtype=np.float64).reshape(p, p)
+        c = np.asarray(enka.scale["mean"], dtype=np.float64).reshape(p)
+        if np.any(np.triu(S, 1) != 0):
+            raise ValueError("the device GP path needs a lower-triangular enka.scale['cov']")
+        Si = np.linalg.solve(S, np.eye(p))
+        Si = np.tril(Si)
+    else:
+        Si, c = np.eye(p), np.zeros(p)
+    n = len(gpmodels)
+    Jt = X0.shape[0]
+    A = np.zeros((n, p, p))
+    Z = np.zeros((n, Jt, p))
+    fam = np.zeros(n, dtype=np.int32)
+    par = np.zeros((n, 3))                               # sigma^2, sn^2, mean bias
+    mw = np.zeros((n, p))
+    alpha = np.zeros((n, Jt))
+    Li = np.zeros((n, Jt, Jt))
+    for i, m in enumerate(gpmodels):
+        if m.X.shape != X0.shape or not np.array_equal(m.X, X0) or m.Y.shape[1] != 1:
+            raise ValueError("the device GP path needs every GP on the same training inputs with one output")
+        ls = m.kern._ls()
+        A[i] = Si / ls[:, None]
+        Z[i] = m.X / ls                                    # the host model's own scaled training points
+        fam[i] = m.kern.family
+        mf = m.mean_function
+        if isinstance(mf, Zero):
+            b, w = 0.0, np.zeros(p)
+        elif isinstance(mf, Constant):
+            b, w = float(mf.c.reshape(-1)[0]), np.zeros(p)
+        elif isinstance(mf, Linear):
+            b, w = float(np.asarray(mf.b).reshape(-1)[0]), np.asarray(mf.A, dtype=np.float64).reshape(p) * ls
+        else:
+            raise ValueError("the device GP path takes the Zero, Constant and Linear mean functions")
+        L, al = m._factor()
+        par[i] = (m.kern.variance, m.likelihood.variance, b)
+        mw[i] = w
+        alpha[i] = al.reshape(-1)
+        Li[i] = np.tril(np.linalg.solve(L, np.eye(Jt)))
+    return dict(n=n, Jt=Jt, p=p, A=A, c=c, Z=Z, family=fam, par=par, mw=mw, alpha=alpha, Li=Li)
+
+
+def _predict_gps_device(enka, X, gpmodels, kwargs):
+    if kwargs.get('separable', False) or kwargs.get('pca_tools', None) is not None:
+        raise ValueError("predict_gps(device=True): separable and pca_tools run on the host")
+    from . import engine as _engine
+    img = device_image(enka, gpmodels)
+    X = np.asarray(X, dtype=np.float64)
+    M, p = X.shape
+    eng = _engine.Engine(p, max(1, img["n"]), M, dtype=str(kwargs.get('engine_dtype', 'float64')),
+                         device=kwargs.get('device_index', 0))
+    eng.gp_set(img)
+    Xd = eng.to_device(np.ascontiguousarray(X.T), p, "gp_X")
+    mean, var = eng.gp_predict(Xd, nugget=kwargs.get('nugget', True), var=True)
+    return [mean.cpu().numpy(), var.cpu().numpy()]

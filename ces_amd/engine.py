@@ -30,7 +30,9 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_comm_stats", "cesx_allreduce_head", "cesx_allreduce_tail", "cesx_allreduce_whole", "cesx_allreduce_sum", "cesx_allreduce_max", "cesx_moments_uu_handover", "cesx_debug_gram_plan",
            "cesx_profile_clock", "cesx_calibrate_mfma", "cesx_profile_gap", "cesx_moments_rest_lineal", "cesx_copy_cols_async",
            "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count",
-           "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats")
+           "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats",
+           "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept")
+GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
 
 
 class Config(C.Structure):
@@ -51,6 +53,12 @@ class StepResult(C.Structure):
                 ("self_bias_data", C.c_double), ("bias_data", C.c_double), ("bias", C.c_double),
                 ("radspec", C.c_double), ("lag_bias_data", C.c_double), ("lag_self_bias_data", C.c_double),
                 ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GpDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_gp", C.c_int32), ("J_t", C.c_int32),
+                ("A", C.c_void_p), ("c", C.c_void_p), ("Z", C.c_void_p), ("family", C.c_void_p),
+                ("par", C.c_void_p), ("mw", C.c_void_p), ("alpha", C.c_void_p), ("Li", C.c_void_p)]
 
 
 class CesxError(RuntimeError):
@@ -166,6 +174,10 @@ def load_library(path=None):
     lib.cesx_mh_propose.argtypes = [vp, u64, vp, vp, vp, vp]
     lib.cesx_mh_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp]
     lib.cesx_mh_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), dp, C.POINTER(C.c_ulonglong)]
+    lib.cesx_gp_set.argtypes = [vp, C.POINTER(GpDesc)]
+    lib.cesx_gp_predict.argtypes = [vp, vp, vp, vp, i32, vp]
+    lib.cesx_gp_start.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.cesx_gp_accept.argtypes = [vp, i32, u64, vp, vp, vp, vp, vp, vp]
     if lib.cesx_abi_version() != ABI_VERSION:
         raise ImportError("libcesx.so ABI %d != binding ABI %d" % (lib.cesx_abi_version(), ABI_VERSION))
     if path == LIB_PATH:
@@ -819,6 +831,56 @@ class Engine:
         if per_chain:
             return int(steps.value), rate.value, buf
         return int(steps.value), rate.value
+
+    # -- GP emulator over the columns (include/cesx.h, cesx_gp_*; ces_amd/emulate.py and ces_amd/sample.py drive it) --
+    def gp_set(self, img):
+        """Install an emulator: ``img`` as ``ces_amd.emulate.device_image`` returns it (cesx_gp_set)."""
+        n, Jt, p = int(img["n"]), int(img["Jt"]), self.p
+        if int(img["p"]) != p:
+            raise ValueError("gp_set: the emulator's input dimension %d differs from p = %d" % (img["p"], p))
+        arr = {k: np.ascontiguousarray(np.asarray(img[k], dtype=np.float64))
+               for k in ("A", "c", "Z", "par", "mw", "alpha", "Li")}
+        fam = np.ascontiguousarray(np.asarray(img["family"], dtype=np.int32).reshape(n))
+        shapes = dict(A=(n, p, p), c=(p,), Z=(n, Jt, p), par=(n, 3), mw=(n, p), alpha=(n, Jt), Li=(n, Jt, Jt))
+        for k, s in shapes.items():
+            if arr[k].shape != s:
+                raise ValueError("gp_set: %s has shape %s, expected %s" % (k, arr[k].shape, s))
+        d = GpDesc(C.sizeof(GpDesc), n, Jt, *[arr[k].ctypes.data for k in ("A", "c", "Z")], fam.ctypes.data,
+                   *[arr[k].ctypes.data for k in ("par", "mw", "alpha", "Li")])
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_set(self._h, C.byref(d)))
+        self.gp_n = n
+
+    def gp_predict(self, X, nugget=True, var=True, out=None):
+        """(mean, var) float64 device tensors (n_gp, J) of the installed GPs at the columns of X (cesx_gp_predict);
+        var=False: the mean-only mode, var is None.  ``out``: a (mean, var) pair to write into."""
+        mean, v = out if out is not None else (None, None)
+        if mean is None:
+            mean = torch.empty((self.gp_n, self.J), dtype=torch.float64, device=self.device)
+        if var and v is None:
+            v = torch.empty((self.gp_n, self.J), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_predict(self._h, X.data_ptr(), mean.data_ptr(), v.data_ptr() if var else None,
+                                                 1 if nugget else 0, self._stream()))
+        self._keep_gp = (X, mean, v)
+        return mean, (v if var else None)
+
+    def gp_start(self, mode, U, mean, var=None):
+        """phi of the current states U from their GP rows in likelihood mode ``mode`` (GP_MODES); counters cleared."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_start(self._h, GP_MODES[mode], U.data_ptr(), mean.data_ptr(),
+                                               None if var is None else var.data_ptr(), self._stream()))
+        self._keep_gp_s = (U, mean, var)
+
+    def gp_accept(self, mode, step_index, U, P, mean, var=None, logu=None):
+        """phi(P) from its GP rows, the test log u < phi(U) - phi(P), U := P on the accepted columns (cesx_gp_accept)."""
+        if logu is not None:
+            assert logu.dtype == torch.float64 and logu.numel() == self.J and logu.is_contiguous()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_accept(self._h, GP_MODES[mode], int(step_index), U.data_ptr(), P.data_ptr(),
+                                                mean.data_ptr(), None if var is None else var.data_ptr(),
+                                                None if logu is None else logu.data_ptr(), self._stream()))
+        self._keep_gp_a = (U, P, mean, var, logu)
 
     def profile_enable(self, on=True):
         """on: False / True, 2 = bind only the events cesx_profile_gap needs, 3 / 4 = the update / the moments

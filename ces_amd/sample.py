@@ -1,15 +1,20 @@
-"""The Sample stage's true-model sampler: a drop-in ``MCMC`` class for ``ces/sample.py`` (:12-202).
+"""The Sample stage: a drop-in ``MCMC`` class for ``ces/sample.py`` (:12-202).
 
 Same class name, constructor, attributes, method names, signatures and kwargs as the reference, so a caller switches
-with ``from ces_amd import sample`` instead of ``from ces import sample``.  ``model_mh`` without build-only options is
-the reference itself, restated in numpy on the host (one chain).  ``gp_mh`` needs a trained GP emulator (GPflow) and
-raises ``ImportError`` -- the reference module fails the same way, earlier (its ``import gpflow``, :8).
+with ``from ces_amd import sample`` instead of ``from ces import sample``.  ``model_mh`` and ``gp_mh`` without build-only
+options are the reference itself, restated in numpy on the host (one chain).  ``gp_mh`` samples the emulated posterior
+of ``ces_amd.emulate`` (or of any objects with ``predict_y`` / ``predict_f`` passed as ``gpmodels``); with no emulator at
+all it raises ``ImportError`` naming GPflow, as the reference module does without it.
 
-Build-only extras of ``model_mh`` (not in the reference):
-  kwarg ``chains=M``     run M independent chains on the GPU (libcesx, ``cesx_mh_*``): one chain per column of the
-                         engine's (p, M) layout, the proposal an update launch, the forward map ``model.forward_device``,
-                         the accept step ``mh_accept_kernel``.  Needs a model with ``forward_device`` (``ces_amd.utils.lineal``)
-                         and a prior with ``.mean`` / ``.cov`` (a frozen ``scipy.stats.multivariate_normal``).
+Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
+  kwarg ``chains=M``     run M independent chains on the GPU (libcesx, ``cesx_mh_*`` / ``cesx_gp_*``): one chain per column
+                         of the engine's (p, M) layout, the proposal an update launch, then for model_mh the forward map
+                         ``model.forward_device`` and ``mh_accept_kernel``, for gp_mh the batched GP prediction
+                         ``gp_predict_kernel`` (fp64, MFMA) and ``gp_score_kernel``.  model_mh needs a model with
+                         ``forward_device`` (``ces_amd.utils.lineal``); gp_mh needs this package's ``emulate.GPR`` models,
+                         one per output, and keeps ``pca_tools``, ``separable`` and ``noise_compounded`` with a dense
+                         Gamma on the host (ValueError).  Both need a prior with ``.mean`` / ``.cov`` (a frozen
+                         ``scipy.stats.multivariate_normal``).
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -42,10 +47,84 @@ class MCMC(object):
         self.trace_stride = 1
 
     def gp_mh(self, enka, n_mcmc, prior, delta=1., enka_scaling=True, **kwargs):
-        """GP-based random-walk MH (ces/sample.py:17-119): needs a trained GPflow emulator (ces/emulate.py), which this
-        package does not build."""
-        raise ImportError("MCMC.gp_mh needs GPflow (a trained GP emulator, ces/emulate.py), which is not installed; "
-                          "ces/sample.py fails the same way when it imports gpflow (:8)")
+        """GP-based random-walk / pCN Metropolis-Hastings on the emulated posterior (ces/sample.py:17-119).
+
+        Without build-only kwargs this is the reference, restated on the host with its quirks:
+          * scales ``delta * chol(cov(enka.Ustar))`` (``enka_scaling``, no reshape) or ``delta * I`` (:23-26); pCN uses
+            the SAME scales with ``sqrt(beta)`` (:72-73), and ``prior.logpdf`` is subtracted for RW and pCN alike (:57 / :96);
+          * a resume (``self.samples`` set) takes ``samples[-1]`` BEFORE phi is computed: phi is that of the resumed
+            state, unlike model_mh (:31-39);
+          * Sigma (:48-55 / :87-94): Gamma None -> diag(gvars) plus 1/2 sum log gvars; ``noise_compounded`` without
+            ``pca_tools`` -> Gamma + diag(gvars) plus 1/2 sum log eigvals(Sigma); with ``pca_tools`` -> Gamma + gvars;
+            otherwise Gamma;
+          * per step ``np.random.normal(0, 1, p)`` then ``np.random.uniform()``; an unknown ``update`` leaves the
+            proposal unbound (``UnboundLocalError``).
+        The emulator is ``kwargs['gpmodels']`` or ``enka.gpmodels`` (any objects with predict_y / predict_f); with
+        neither the sampler raises ImportError naming GPflow, as the reference's own module does without it.
+        ``chains=M`` (build-only) runs M chains on the device (module docstring).
+        """
+        if kwargs.get("gpmodels", None) is None and not hasattr(enka, "gpmodels"):
+            raise ImportError("MCMC.gp_mh needs a trained GP emulator: pass gpmodels= or train enka.gpmodels with "
+                              "ces_amd.emulate.train_gps (the reference builds it with GPflow, ces/emulate.py, which is "
+                              "not installed; ces/sample.py fails when it imports gpflow, :8)")
+        if kwargs.get("chains", None) is not None:
+            return self._gp_mh_device(enka, n_mcmc, prior, delta, enka_scaling, kwargs)
+        from . import emulate
+        if enka_scaling:
+            scales = delta * np.linalg.cholesky(np.cov(enka.Ustar))
+        else:
+            scales = delta * np.eye(enka.p)
+
+        current = enka.Ustar.mean(axis=1)
+        y = self.y_obs.reshape(-1, 1)
+
+        try:                                              # resume (:31-39): before phi
+            getattr(self, "samples")
+            samples = list(self.samples.T)
+            current = samples[-1]
+            accept = 0
+        except AttributeError:
+            samples = []
+            samples.append(current.flatten())
+            accept = 0.
+
+        def score(u):
+            gmean, gvars = emulate.predict_gps(enka, u.reshape(1, -1),
+                                               gpmodels=kwargs.get("gpmodels", None),
+                                               nugget=kwargs.get("nugget", True),
+                                               pca_tools=kwargs.get("pca_tools", None))
+            yG = gmean - y
+            if kwargs.get("Gamma", None) is None:
+                Sigma = np.diag(gvars.flatten())
+            elif kwargs.get("noise_compounded", False) and kwargs.get("pca_tools", None) is None:
+                Sigma = kwargs.get("Gamma") + np.diag(gvars.flatten())
+            elif kwargs.get("pca_tools", None) is not None:
+                Sigma = kwargs.get("Gamma") + gvars
+            else:
+                Sigma = kwargs.get("Gamma")
+            phi = (yG * np.linalg.solve(2 * Sigma, yG)).sum()
+            phi -= prior.logpdf(u.flatten())
+            if kwargs.get("Gamma", None) is None:
+                phi += .5 * np.log(gvars).sum()
+            elif kwargs.get("noise_compounded", False):
+                phi += .5 * np.log(np.linalg.eigvals(Sigma)).sum()
+            return phi
+
+        phi_current = score(current)
+        for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
+            if kwargs.get("update", None) is None:
+                proposal = self.random_walk(current, scales, enka.p)
+            elif kwargs.get("update", None) == "pCN":
+                proposal = self.pCN(current, scales, enka.p, beta=kwargs.get("beta", 0.5))
+            phi_proposal = score(proposal)
+            if np.log(np.random.uniform()) < phi_current - phi_proposal:
+                current = np.copy(proposal)
+                phi_current = np.copy(phi_proposal)
+                accept += 1.
+            samples.append(current)
+
+        self.samples = np.array(samples).T
+        self.accept = accept / n_mcmc
 
     def model_mh(self, model, n_mcmc, prior, enka, Gamma, delta=1., enka_scaling=True, **kwargs):
         """Random-walk / pCN Metropolis-Hastings on the true forward model (ces/sample.py:121-196).
@@ -223,6 +302,113 @@ class MCMC(object):
             eng.mh_propose(step, U, xi=xi_t, out=P)
             fwd(P, GP)
             eng.mh_accept(step, U, P, GP, logu=logu_t)
+            if (k + 1) % stride == 0 or k + 1 == n_mcmc:
+                kept.append(eng.to_host(U))
+        steps, rate, per = eng.mh_stats(per_chain=True)
+
+        new = np.stack(kept, axis=1) if kept else np.zeros((p, 0, M))      # (p, n_new, M)
+        if M == 1:
+            new = new[:, :, 0]
+        self.samples = new if prev is None else np.concatenate([prev, new], axis=1)
+        self.accept = rate
+        self.accept_chains = per.astype(np.float64) / max(1, n_mcmc)
+        self.samples_device = U
+        self._mh_next_step = base + n_mcmc
+
+    def _gp_mh_device(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
+        import torch
+        from . import emulate
+        M = kwargs["chains"]
+        if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or M < 1:
+            raise ValueError("chains must be an integer >= 1, got %r" % (M,))
+        M = int(M)
+        host = "; run gp_mh without chains= (the host path)"
+        if kwargs.get("pca_tools", None) is not None or kwargs.get("separable", False):
+            raise ValueError("chains=: pca_tools and separable need a per-chain n x n factorisation or one point at a "
+                             "time" + host)
+        if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
+            raise ValueError("chains=: the prior must expose .mean and .cov (a frozen scipy.stats.multivariate_normal does)")
+        update = kwargs.get("update", None)
+        if update not in (None, "pCN"):
+            raise ValueError("chains=: unknown update %r (None or 'pCN')" % (update,))
+        if self.noise not in ("numpy", "device"):
+            raise ValueError("noise must be 'numpy' or 'device', got %r" % (self.noise,))
+        p, n = enka.p, enka.n_obs
+        gpmodels = kwargs.get("gpmodels", None)
+        gpmodels = enka.gpmodels if gpmodels is None else gpmodels
+        if len(gpmodels) != n:
+            raise ValueError("chains=: %d GPs for n_obs = %d" % (len(gpmodels), n) + host)
+        Gamma = kwargs.get("Gamma", None)
+        if Gamma is None:                                 # Sigma = diag(gvars) (:48-49)
+            mode, G = "var", np.eye(n)
+        else:
+            G = np.asarray(Gamma, dtype=np.float64).reshape(n, n)
+            if kwargs.get("noise_compounded", False):     # Sigma = Gamma + diag(gvars) (:50-51)
+                if np.any(G != np.diag(np.diag(G))):
+                    raise ValueError("chains=: noise_compounded with a dense Gamma needs a per-chain n x n "
+                                     "factorisation" + host)
+                mode = "gamma_var"
+            else:                                         # Sigma = Gamma (:54-55): the mean alone
+                mode = "gamma"
+        try:
+            img = emulate.device_image(enka, gpmodels)
+        except ValueError as exc:
+            raise ValueError("chains=: %s" % exc)
+        if enka_scaling:                                  # (:23-26; pCN takes the same scales)
+            scales = delta * np.linalg.cholesky(np.cov(enka.Ustar))
+        else:
+            scales = delta * np.eye(p)
+        start = kwargs.get("start", "mean")
+        if start == "mean":
+            U0 = np.repeat(np.asarray(enka.Ustar, dtype=np.float64).mean(axis=1).reshape(p, 1), M, axis=1)
+        elif start == "ensemble":
+            if M > enka.Ustar.shape[1]:
+                raise ValueError("start='ensemble' needs chains <= J = %d, got %d" % (enka.Ustar.shape[1], M))
+            U0 = np.array(enka.Ustar[:, :M], dtype=np.float64)
+        else:
+            raise ValueError("start must be 'mean' or 'ensemble', got %r" % (start,))
+        stride = max(1, int(self.trace_stride))
+        mu = np.asarray(prior.mean, dtype=np.float64).reshape(p)
+        cov = np.asarray(prior.cov, dtype=np.float64).reshape(p, p)
+
+        eng = self._mh_engine(p, n, M)
+        eng.set_problem(np.asarray(self.y_obs, dtype=np.float64).reshape(n), G, mu, cov, mu)
+        eng.mh_set_proposal(update, scales, kwargs.get("beta", 0.5))
+        eng.gp_set(img)
+        nugget, want_var = kwargs.get("nugget", True), mode != "gamma"
+        rows = lambda: torch.empty((n, M), dtype=torch.float64, device=eng.device)    # noqa: E731
+        mean_u, mean_p = rows(), rows()
+        var_u, var_p = (rows(), rows()) if want_var else (None, None)
+
+        resume = hasattr(self, "samples")
+        if resume:                                        # (:31-39: phi of the resumed states)
+            prev = np.asarray(self.samples)
+            if (M == 1 and prev.ndim != 2) or (M > 1 and (prev.ndim != 3 or prev.shape[2] != M)) or prev.shape[0] != p:
+                raise ValueError("resume: self.samples %s does not hold %d chain(s) of dimension %d" % (prev.shape, M, p))
+            last = prev[:, -1] if M == 1 else prev[:, -1, :]
+            U = eng.to_device(np.ascontiguousarray(last.reshape(p, M)), p, "mh_U").clone()
+            base = int(getattr(self, "_mh_next_step", 0))
+            kept = []
+        else:
+            prev = None
+            U = eng.to_device(U0, p, "mh_U").clone()
+            base = 0
+            kept = [U0.copy()]
+        P = eng.empty(p)
+        eng.gp_predict(U, nugget=nugget, var=want_var, out=(mean_u, var_u))
+        eng.gp_start(mode, U, mean_u, var_u)
+
+        for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
+            step = base + k
+            xi_t = logu_t = None
+            if self.noise == "numpy":
+                xi = np.random.normal(0, 1, [p, M])       # :199 / :202
+                logu = np.log(np.random.uniform(size=M))  # :98
+                xi_t = eng.to_device(xi, p, "mh_xi")
+                logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
+            eng.mh_propose(step, U, xi=xi_t, out=P)
+            eng.gp_predict(P, nugget=nugget, var=want_var, out=(mean_p, var_p))
+            eng.gp_accept(mode, step, U, P, mean_p, var_p, logu=logu_t)
             if (k + 1) % stride == 0 or k + 1 == n_mcmc:
                 kept.append(eng.to_host(U))
         steps, rate, per = eng.mh_stats(per_chain=True)

@@ -410,6 +410,48 @@ int cesx_mh_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* 
    the J_local counters.  Synchronises. */
 int cesx_mh_stats(cesx_handle h, unsigned long long* steps, double* rate, unsigned long long* per_chain_host);
 
+/* ---- Emulate: GP prediction and the GP sampler over the columns (ces/emulate.py, ces/sample.py:17-119) --
+   One exact GP per output, trained on the host (ces_amd/emulate.py); the engine holds its own fp64 image of them and
+   evaluates them for every column at once.  GP i maps an input x to z = A_i (x - c) (A_i = diag(1/l_i) S^{-1} lower
+   triangular: ARD lengthscales and the enka.scale scaling in one map) and predicts
+       mean_i(x) = sum_t alpha_it k_i(z, Z_it) + w_i^T z + b_i,
+       var_i(x)  = sigma_i^2 - || L_i^{-1} k_i(z, Z_i.) ||^2   (+ sn_i^2 with the nugget: GPflow's predict_y),
+   k_i(z, z') = sigma_i^2 f(|z - z'|), f of family 0 RBF exp(-r^2/2), 1 Matern12, 2 Matern32, 3 Matern52.
+   All GP arithmetic is fp64 whatever the engine dtype; the outputs are fp64 (n_gp x J_local) rows.  Sums run in a fixed
+   order: runs are bit-reproducible. */
+typedef struct {
+    uint32_t struct_bytes;    /* sizeof(cesx_gp_desc) */
+    int32_t n_gp, J_t;        /* GPs, training points (the input dimension is the handle's p) */
+    const double* A;          /* [n_gp][p][p] lower-triangular input maps, row-major */
+    const double* c;          /* [p] the input shift */
+    const double* Z;          /* [n_gp][J_t][p] the mapped training points */
+    const int32_t* family;    /* [n_gp] kernel family 0..3 */
+    const double* par;        /* [n_gp][3] sigma^2, sn^2 (likelihood variance), mean bias b */
+    const double* mw;         /* [n_gp][p] mean weights w over z */
+    const double* alpha;      /* [n_gp][J_t] (K + sn^2 I)^{-1} (y - m(X)) */
+    const double* Li;         /* [n_gp][J_t][J_t] L^{-1}, L = chol(K + sn^2 I), row-major (only the lower triangle is read) */
+} cesx_gp_desc;
+/* Copies the emulator (host fp64) into engine-owned memory; replaces an earlier one. */
+int cesx_gp_set(cesx_handle h, const cesx_gp_desc* desc);
+/* mean_dev (and var_dev, unless NULL: the mean-only mode) = the n_gp GP rows (fp64, n_gp x J_local) at the columns of X_dev
+   (p x J_local, engine dtype); nugget != 0 adds sn^2 to the variance. */
+int cesx_gp_predict(cesx_handle h, const void* X_dev, double* mean_dev, double* var_dev, int nugget, void* stream);
+/* MCMC.gp_mh over the columns: the proposal is cesx_mh_propose's (cesx_mh_set_proposal with the gp_mh scales; pCN takes the
+   same scales), the GP rows of the proposal come from cesx_gp_predict (n_gp == n_obs), and
+       phi(u) = 1/2 (m - y)^T Sigma^{-1} (m - y) [+ 1/2 log det Sigma] + 1/2 (u - mu)^T Sigma_prior^{-1} (u - mu)
+   with the prior term for RW AND pCN (ces/sample.py:57 / :96), y, mu, Sigma_prior of cesx_set_problem and
+       CESX_GP_GAMMA      Sigma = Gamma of cesx_set_problem (mean rows only; a dense Gamma whitened), no log det term
+       CESX_GP_VAR        Sigma = diag(var), 1/2 sum log var                (Gamma None; cesx_set_problem's Gamma diagonal)
+       CESX_GP_GAMMA_VAR  Sigma = diag(Gamma) + diag(var), 1/2 sum log(..)  (noise_compounded, diagonal Gamma)
+   A non-positive variance makes phi NaN (or inf - inf) and the test rejects, as numpy's comparison does.  The start, the
+   test, the device uniform, the counters and cesx_mh_stats are those of cesx_mh_start / cesx_mh_accept. */
+#define CESX_GP_GAMMA      0
+#define CESX_GP_VAR        1
+#define CESX_GP_GAMMA_VAR  2
+int cesx_gp_start(cesx_handle h, int mode, const void* U_dev, const double* mean_dev, const double* var_dev, void* stream);
+int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev, const void* P_dev, const double* mean_dev,
+                   const double* var_dev, const double* logu_dev, void* stream);
+
 /* ---- host staging ------------------------------------------------------ */
 
 /* A COLUMN block of a row-major (rows, J) ensemble between pinned host memory and the device, asynchronously on
