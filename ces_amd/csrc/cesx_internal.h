@@ -451,6 +451,19 @@ struct Engine {
     double *d_gp_ws = nullptr;                      // the K* panels of the launches that do not fit in LDS
     size_t gp_ws_len = 0;
     double *d_gp_LSi = nullptr;                     // [p][p] L_Sigma^{-1} of the problem (cesx_gp_start)
+    // ---- GP training: batched likelihood and gradient (cesx_gpfit_*, kernels_gpfit.hip) ----
+    int gf_n = 0, gf_Jt = 0, gf_Jp = 0;             // GPs, training points, training points rounded up to 16 (gf_n 0: no fit problem)
+    int gf_family = 0, gf_ard = 0, gf_mean = 0;     // kernel family, ARD, mean kind (CESX_GPFIT_MEAN_*): one of each per problem
+    int gf_nl = 0, gf_ntheta = 0, gf_ntile = 0;     // lengthscales (p or 1), parameters per GP, 64 x 64 tiles of the lower triangle
+    double *d_gf_X = nullptr, *d_gf_Y = nullptr;    // [Jt][p], [n][Jt]
+    double *d_gf_Xs = nullptr;                      // [n][Jp][p] X / l of the last evaluation
+    double *d_gf_r = nullptr, *d_gf_t = nullptr, *d_gf_alpha = nullptr;   // [n][Jp]: y - m(X), L^{-1} r, alpha
+    double *d_gf_A = nullptr, *d_gf_W = nullptr, *d_gf_Ki = nullptr;      // [n][Jp][Jp]: Ky -> L, L^{-T}, K^{-1}
+    double *d_gf_Ld = nullptr;                      // [n][Jp][16] the diagonal blocks of L (Ky's stay in d_gf_A: every workgroup of a launch reads them)
+    double *d_gf_part = nullptr;                    // [n][gf_ntile][gf_nl + 2] the gradient pass's partial sums
+    double *d_gf_theta = nullptr, *d_gf_out = nullptr;                    // [n][ntheta], [n][2 + ntheta] of the evaluation in flight
+    int *d_gf_idx = nullptr, *d_gf_status = nullptr;                      // [n]
+    std::vector<double> h_gf_out;
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -652,6 +665,10 @@ int launch_gp_predict(Engine& e, const void* X, double* mean, double* var, bool 
 // counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double* mean, const double* var, void* U,
                     const double* logu, unsigned step, hipStream_t s);
+
+// kernels_gpfit.hip: lml, gradient and status of the GPs d_gf_idx[0 .. n_active) at d_gf_theta into d_gf_out
+int launch_gpfit_eval(Engine& e, int n_active, hipStream_t s);
+int gpfit_tiles(int Jp);                            // 64 x 64 tiles of the lower triangle of a Jp x Jp matrix
 
 // Event pair for one profiled launch (cesx_profile_*).  bound = false: the pair is RECORDED around the launch (two
 // marker packets: they delay the stream by ~6 us each and the interval includes that).  bound = true: the caller

@@ -428,7 +428,9 @@ void cesx_destroy(cesx_handle h) {
                     e.d_ns_parts, e.d_ns_skip, e.d_mv, e.d_part, e.d_scal, e.d_absmax,
                     e.d_absmax_part, e.d_clk, e.d_cholflag, e.d_lag, e.d_A64, e.d_b64, e.d_lvec, e.d_Wq, e.d_ticket,
                     e.d_mh_W, e.d_mh_Wf, e.d_mh_Li, e.d_mh_Li_f, e.d_mh_lb, e.d_mh_w, e.d_mh_xi, e.d_mh_phi, e.d_mh_cnt,
-                    e.d_gp_A, e.d_gp_c, e.d_gp_Z, e.d_gp_par, e.d_gp_mw, e.d_gp_alpha, e.d_gp_Li, e.d_gp_ws, e.d_gp_LSi};
+                    e.d_gp_A, e.d_gp_c, e.d_gp_Z, e.d_gp_par, e.d_gp_mw, e.d_gp_alpha, e.d_gp_Li, e.d_gp_ws, e.d_gp_LSi,
+                    e.d_gf_X, e.d_gf_Y, e.d_gf_Xs, e.d_gf_r, e.d_gf_t, e.d_gf_alpha, e.d_gf_A, e.d_gf_W, e.d_gf_Ki, e.d_gf_Ld, e.d_gf_part,
+                    e.d_gf_theta, e.d_gf_out, e.d_gf_idx, e.d_gf_status};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     for (int w = 0; w < 2; ++w)
@@ -1364,6 +1366,110 @@ int cesx_debug_dense(cesx_handle h, double* ubar, double* gbar, double* C, doubl
         }
     }
     if (M) CESX_HIP(hipMemcpy(M, e.d_M, p * p * 8, hipMemcpyDeviceToHost));
+    return CESX_OK;
+}
+
+
+// ---- Emulate: training the GPs, batched likelihood and gradient (ces_amd/emulate.py train_gps(device=True); kernels_gpfit.hip) ----
+
+static int gpfit_free(Engine& e) {
+    e.gf_n = 0;
+    void** bufs[] = {(void**)&e.d_gf_X, (void**)&e.d_gf_Y, (void**)&e.d_gf_Xs, (void**)&e.d_gf_r, (void**)&e.d_gf_t, (void**)&e.d_gf_alpha,
+                     (void**)&e.d_gf_A, (void**)&e.d_gf_W, (void**)&e.d_gf_Ki, (void**)&e.d_gf_Ld, (void**)&e.d_gf_part, (void**)&e.d_gf_theta,
+                     (void**)&e.d_gf_out, (void**)&e.d_gf_idx, (void**)&e.d_gf_status};
+    for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
+    return CESX_OK;
+}
+
+static int gpfit_alloc(Engine& e, const cesx_gpfit_desc* d, int Jp, int nl, int ntheta, int ntile) {
+    const size_t n = (size_t)d->n_gp, Jt = (size_t)d->J_t, p = (size_t)e.p, J2 = (size_t)Jp * Jp;
+    TRY(dmalloc(e, &e.d_gf_X, Jt * p * 8)); TRY(upload(e, e.d_gf_X, d->X, Jt * p * 8));
+    TRY(dmalloc(e, &e.d_gf_Y, n * Jt * 8)); TRY(upload(e, e.d_gf_Y, d->Y, n * Jt * 8));
+    TRY(dmalloc(e, &e.d_gf_Xs, n * Jp * p * 8));
+    TRY(dmalloc(e, &e.d_gf_r, n * Jp * 8)); TRY(dmalloc(e, &e.d_gf_t, n * Jp * 8)); TRY(dmalloc(e, &e.d_gf_alpha, n * Jp * 8));
+    TRY(dmalloc(e, &e.d_gf_A, n * J2 * 8)); TRY(dmalloc(e, &e.d_gf_W, n * J2 * 8)); TRY(dmalloc(e, &e.d_gf_Ki, n * J2 * 8));
+    TRY(dmalloc(e, &e.d_gf_Ld, n * Jp * 16 * 8));
+    TRY(dmalloc(e, &e.d_gf_part, n * ntile * (size_t)(nl + 2) * 8));
+    TRY(dmalloc(e, &e.d_gf_theta, n * ntheta * 8)); TRY(dmalloc(e, &e.d_gf_out, n * (size_t)(2 + ntheta) * 8));
+    TRY(dmalloc(e, &e.d_gf_idx, n * 4)); TRY(dmalloc(e, &e.d_gf_status, n * 4));
+    return CESX_OK;
+}
+
+int cesx_gpfit_set(cesx_handle h, const cesx_gpfit_desc* d) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    e.gf_n = 0;                                // whatever fails below, the handle is left without a fit problem
+    if (!d || d->struct_bytes != sizeof(cesx_gpfit_desc)) { e.err = "cesx_gpfit_set: bad cesx_gpfit_desc"; return CESX_EINVAL; }
+    if (!d->X || !d->Y) { e.err = "cesx_gpfit_set: null pointer"; return CESX_EINVAL; }
+    if (d->n_gp < 1 || d->n_gp > 65535 || d->J_t < 1 || d->J_t > 16384) { e.err = "cesx_gpfit_set: 1 <= n_gp <= 65535 and 1 <= J_t <= 16384"; return CESX_EINVAL; }
+    if (d->family < 0 || d->family > 3) { e.err = "cesx_gpfit_set: unknown kernel family"; return CESX_EINVAL; }
+    if (d->mean < CESX_GPFIT_MEAN_ZERO || d->mean > CESX_GPFIT_MEAN_LINEAR) { e.err = "cesx_gpfit_set: unknown mean kind"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    CESX_HIP(hipDeviceSynchronize());          // (an evaluation of the old problem may still be in flight)
+    gpfit_free(e);
+    const int Jp = (d->J_t + 15) / 16 * 16, nl = d->ard ? e.p : 1;
+    const int ntheta = nl + 2 + (d->mean == CESX_GPFIT_MEAN_ZERO ? 0 : d->mean == CESX_GPFIT_MEAN_CONSTANT ? 1 : e.p + 1);
+    const int ntile = gpfit_tiles(Jp);
+    const int rc = gpfit_alloc(e, d, Jp, nl, ntheta, ntile);
+    if (rc != CESX_OK) { gpfit_free(e); return rc; }          // nothing is committed before everything is
+    e.gf_Jt = d->J_t; e.gf_Jp = Jp; e.gf_family = d->family; e.gf_ard = d->ard ? 1 : 0; e.gf_mean = d->mean;
+    e.gf_nl = nl; e.gf_ntheta = ntheta; e.gf_ntile = ntile;
+    e.h_gf_out.assign((size_t)d->n_gp * (2 + ntheta), 0.0);
+    e.gf_n = d->n_gp;
+    return CESX_OK;
+}
+
+int cesx_gpfit_ntheta(cesx_handle h) {
+    if (!h) return -1;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    return e.gf_n > 0 ? e.gf_ntheta : -1;
+}
+
+int cesx_gpfit_eval(cesx_handle h, int n_active, const int32_t* idx, const double* theta, double* lml, double* grad,
+                    int32_t* status, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (e.gf_n < 1) { e.err = "cesx_gpfit_eval: cesx_gpfit_set has not been called"; return CESX_ESTATE; }
+    if (!idx || !theta || !lml || !grad || !status) { e.err = "cesx_gpfit_eval: null pointer"; return CESX_EINVAL; }
+    if (n_active < 1 || n_active > e.gf_n) { e.err = "cesx_gpfit_eval: 1 <= n_active <= n_gp"; return CESX_EINVAL; }
+    {
+        std::vector<char> seen((size_t)e.gf_n, 0);          // (two entries for one GP would share its workspace)
+        for (int i = 0; i < n_active; ++i) {
+            if (idx[i] < 0 || idx[i] >= e.gf_n || seen[(size_t)idx[i]]) { e.err = "cesx_gpfit_eval: idx out of range or repeated"; return CESX_EINVAL; }
+            seen[(size_t)idx[i]] = 1;
+        }
+    }
+    SET_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nt = (size_t)e.gf_ntheta, no = 2 + nt;
+    CESX_HIP(hipMemcpyAsync(e.d_gf_idx, idx, (size_t)n_active * 4, hipMemcpyHostToDevice, s));
+    CESX_HIP(hipMemcpyAsync(e.d_gf_theta, theta, (size_t)n_active * nt * 8, hipMemcpyHostToDevice, s));
+    TRY(launch_gpfit_eval(e, n_active, s));
+    CESX_HIP(hipMemcpyAsync(e.h_gf_out.data(), e.d_gf_out, (size_t)n_active * no * 8, hipMemcpyDeviceToHost, s));
+    CESX_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < n_active; ++i) {
+        const double* o = e.h_gf_out.data() + (size_t)i * no;
+        lml[i] = o[0];
+        status[i] = o[1] == 0.0 ? CESX_OK : CESX_ENOTPD;
+        std::memcpy(grad + (size_t)i * nt, o + 2, nt * 8);
+    }
+    return CESX_OK;
+}
+
+int cesx_gpfit_factors(cesx_handle h, int i, double* alpha, double* Li) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (e.gf_n < 1) { e.err = "cesx_gpfit_factors: cesx_gpfit_set has not been called"; return CESX_ESTATE; }
+    if (i < 0 || i >= e.gf_n || !alpha || !Li) { e.err = "cesx_gpfit_factors: bad GP index or null pointer"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    const size_t Jt = (size_t)e.gf_Jt, Jp = (size_t)e.gf_Jp;
+    std::vector<double> W(Jp * Jp);
+    CESX_HIP(hipDeviceSynchronize());
+    CESX_HIP(hipMemcpy(alpha, e.d_gf_alpha + (size_t)i * Jp, Jt * 8, hipMemcpyDeviceToHost));
+    CESX_HIP(hipMemcpy(W.data(), e.d_gf_W + (size_t)i * Jp * Jp, Jp * Jp * 8, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < Jt; ++r)                         // L^{-1} = W^T: the engine keeps the upper-triangular L^{-T}
+        for (size_t c = 0; c < Jt; ++c) Li[r * Jt + c] = c <= r ? W[c * Jp + r] : 0.0;
     return CESX_OK;
 }
 

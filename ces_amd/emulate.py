@@ -20,8 +20,13 @@ The GP (the notebooks' ``emulate(enki)`` needs GPflow 1.x; this is its exact-GPR
   gradient, the positive parameters through softplus with a 1e-6 floor (GPflow 1.x's default ``positive`` transform as far
   as can be told without GPflow).  ``train_gps(enka, kernel='Matern32', ...)`` is the notebook's ``emulate(enki)``.
 
-Build-only: ``predict_gps(..., device=True)`` evaluates the GPs on the GPU (``cesx_gp_predict``, kernels_gp.hip).
+Build-only: ``predict_gps(..., device=True)`` evaluates the GPs on the GPU (``cesx_gp_predict``, kernels_gp.hip);
+``train_gps(..., device=True)`` fits all emulators at once, the same ``ScipyOptimizer`` per GP, the likelihood and its
+gradient of every GP in one batched GPU evaluation per optimiser step (``fit_lockstep``, ``cesx_gpfit_eval``,
+kernels_gpfit.hip).
 """
+import threading
+
 import numpy as np
 from scipy import optimize
 
@@ -331,28 +336,190 @@ class models(object):
 _KERNELS = {"RBF": RBF, "Matern12": Matern12, "Matern32": Matern32, "Matern52": Matern52}
 
 
+def _make_mean(mean_function, p):
+    if mean_function is None:
+        return None
+    if mean_function == "Constant":
+        return Constant()
+    if mean_function == "Linear":
+        return Linear(np.ones((p, 1)))
+    return mean_function()
+
+
 def train_gps(enka, kernel="Matern32", ARD=True, mean_function=None, maxiter=1000, **kwargs):
     """The notebooks' ``emulate(enki)``: one GPR per row of ``enka.Gstar[:n_obs]``, all on ``enka.Ustar.T`` (scaled by
     ``enka.scale`` when ``enka`` has ``scaled``), fitted by ``ScipyOptimizer``; stored in (and returned as)
-    ``enka.gpmodels``.  ``mean_function``: None (zero), 'Constant', 'Linear', or a callable making one per output."""
+    ``enka.gpmodels``.  ``mean_function``: None (zero), 'Constant', 'Linear', or a callable making one per output.
+    Build-only ``device=True`` (``device_index=0``, ``engine_dtype``): the same fit, every GP's optimiser in lockstep and
+    the likelihood and gradient of all of them in one GPU evaluation per step (``_train_gps_device``)."""
+    device = bool(kwargs.get("device", False))
+    if device:
+        unknown = sorted(set(kwargs) - {"device", "device_index", "engine_dtype"})
+        if unknown:
+            raise TypeError("train_gps(device=True): unknown keyword arguments %s" % ", ".join(unknown))
+        Kern = _KERNELS.get(kernel) if isinstance(kernel, str) else kernel
+        if not (isinstance(Kern, type) and Kern in _KERNELS.values()):
+            raise ValueError("train_gps(device=True) takes the RBF / Matern12 / Matern32 / Matern52 kernels of this package; "
+                             "run train_gps on the host (device=False) for other kernels")
+    else:
+        Kern = _KERNELS[kernel] if isinstance(kernel, str) else kernel
     X = np.asarray(enka.Ustar, dtype=np.float64).T
     if hasattr(enka, "scaled"):
         X = np.linalg.solve(enka.scale["cov"], X.T - enka.scale["mean"]).T
-    Kern = _KERNELS[kernel] if isinstance(kernel, str) else kernel
+    if device:
+        return _train_gps_device(enka, X, Kern, ARD, mean_function, maxiter, kwargs)
     enka.gpmodels = []
     for y in np.asarray(enka.Gstar, dtype=np.float64)[range(enka.n_obs)]:
         k = Kern(input_dim=enka.p, ARD=ARD)
-        if mean_function is None:
-            mf = None
-        elif mean_function == "Constant":
-            mf = Constant()
-        elif mean_function == "Linear":
-            mf = Linear(np.ones((enka.p, 1)))
-        else:
-            mf = mean_function()
-        m = GPR(X, y[:, np.newaxis], k, mean_function=mf)
+        m = GPR(X, y[:, np.newaxis], k, mean_function=_make_mean(mean_function, enka.p))
         ScipyOptimizer().minimize(m, maxiter=maxiter)
         enka.gpmodels.append(m)
+    return enka.gpmodels
+
+
+# -- build-only: all emulators fitted at once ---------------------------------------------------------------------------
+class _FitAborted(Exception):
+    """Raised inside a parked optimiser thread when ``fit_lockstep`` gives up (its ``evaluate`` raised)."""
+
+
+class _LockstepProxy(object):
+    """What ``ScipyOptimizer.minimize`` sees of one model inside ``fit_lockstep``: ``_get`` / ``_set`` are the model's,
+    ``log_marginal_likelihood_and_grad`` hands the current parameters to the calling thread and waits for its answer."""
+
+    def __init__(self, hub, i, model):
+        self._hub, self._i, self._model = hub, i, model
+
+    def _get(self):
+        return self._model._get()
+
+    def _set(self, pos, free):
+        self._model._set(pos, free)
+
+    def log_marginal_likelihood_and_grad(self):
+        pos, free = self._model._get()
+        lml, grad, status = self._hub.request(self._i, np.concatenate([pos, free]))
+        if status != 0:                       # what the host's Cholesky raises; ScipyOptimizer turns it into (1e300, 0)
+            raise np.linalg.LinAlgError("Matrix is not positive definite")
+        return float(lml), np.array(grad, dtype=np.float64)
+
+
+class _LockstepHub(object):
+    def __init__(self, n):
+        self.cond = threading.Condition()
+        self.pending, self.answers = {}, {}
+        self.live, self.aborted = n, False
+
+    def request(self, i, theta):              # (optimiser threads)
+        with self.cond:
+            self.pending[i] = theta
+            self.cond.notify_all()
+            while i not in self.answers and not self.aborted:
+                self.cond.wait()
+            if i not in self.answers:
+                raise _FitAborted()
+            return self.answers.pop(i)
+
+    def finished(self):                       # (optimiser threads, on their way out)
+        with self.cond:
+            self.live -= 1
+            self.cond.notify_all()
+
+
+def fit_lockstep(models, evaluate, maxiter=1000):
+    """Fit every model of ``models`` with the unchanged ``ScipyOptimizer.minimize``, each optimiser in a thread of its own,
+    their likelihood evaluations batched: an optimiser that asks for ``log_marginal_likelihood_and_grad`` parks; once every
+    optimiser still running has parked, the CALLING thread makes one
+        ``evaluate(indices, thetas) -> (lml, grad, status)``
+    call (``indices``: ascending model numbers, ``thetas`` (k, n_theta): their natural parameters in ``GPR._get()`` order,
+    which the models themselves already hold; ``status`` nonzero: not positive definite, which the optimiser sees as the
+    host path's ``LinAlgError``) and releases them.  Only the calling thread ever runs ``evaluate``.  Each optimiser sees
+    exactly the sequence of values a sequential fit would, so with an ``evaluate`` that computes what the model's own
+    method does the fitted parameters and ``nfev`` are bit-identical to sequential fits; the number of batched calls is the
+    largest ``nfev``.  An exception of ``evaluate`` (or of an optimiser) ends every thread and is re-raised here.
+    Returns the ``ScipyOptimizer`` of every model (``.result``: scipy's ``OptimizeResult``)."""
+    models = list(models)
+    n = len(models)
+    hub = _LockstepHub(n)
+    opts = [ScipyOptimizer() for _ in models]
+    errors = [None] * n
+
+    def work(i):
+        try:
+            opts[i].minimize(_LockstepProxy(hub, i, models[i]), maxiter=maxiter)
+        except _FitAborted:
+            pass
+        except BaseException as exc:          # noqa: B902 - handed to the caller below
+            errors[i] = exc
+        finally:
+            hub.finished()
+
+    threads = [threading.Thread(target=work, args=(i,), name="fit_lockstep-%d" % i, daemon=True) for i in range(n)]
+    for t in threads:
+        t.start()
+    failure = None
+    try:
+        while True:
+            with hub.cond:
+                while hub.live > 0 and len(hub.pending) < hub.live:
+                    hub.cond.wait()
+                if hub.live == 0 or any(e is not None for e in errors):
+                    break
+                idx = sorted(hub.pending)
+                thetas = np.array([hub.pending[i] for i in idx])
+                hub.pending.clear()
+            lml, grad, status = evaluate(np.array(idx, dtype=np.int32), thetas)
+            with hub.cond:
+                for k, i in enumerate(idx):
+                    hub.answers[i] = (lml[k], grad[k], int(status[k]))
+                hub.cond.notify_all()
+    except BaseException as exc:              # noqa: B902 - re-raised once the threads have ended
+        failure = exc
+    finally:
+        with hub.cond:
+            hub.aborted = True
+            hub.cond.notify_all()
+        for t in threads:
+            t.join()
+    if failure is None:
+        failure = next((e for e in errors if e is not None), None)
+    if failure is not None:
+        raise failure
+    return opts
+
+
+def _theta_of(m):
+    pos, free = m._get()
+    return np.concatenate([pos, free])
+
+
+def _train_gps_device(enka, X, Kern, ARD, mean_function, maxiter, kwargs):
+    models = []
+    for y in np.asarray(enka.Gstar, dtype=np.float64)[range(enka.n_obs)]:
+        models.append(GPR(X, y[:, np.newaxis], Kern(input_dim=enka.p, ARD=ARD), mean_function=_make_mean(mean_function, enka.p)))
+    kinds = {Zero: "zero", Constant: "constant", Linear: "linear"}
+    mk = set(type(m.mean_function) for m in models)
+    if len(mk) != 1 or next(iter(mk)) not in kinds or any(type(m.kern) is not Kern for m in models):
+        raise ValueError("train_gps(device=True) takes the Zero, Constant and Linear mean functions (one kind for all "
+                         "outputs); run train_gps on the host (device=False) for other mean functions")
+    for m in models:
+        if isinstance(m.mean_function, Linear) and np.asarray(m.mean_function.A).shape != (enka.p, 1):
+            raise ValueError("train_gps(device=True): a Linear mean needs A of shape (p, 1); run train_gps on the host otherwise")
+    from . import engine as _engine
+    eng = _engine.Engine(enka.p, 1, 1, dtype=str(kwargs.get("engine_dtype", "float64")), device=kwargs.get("device_index", 0))
+    eng.gpfit_set(X, np.stack([m.Y[:, 0] for m in models]), Kern.family, ARD, kinds[next(iter(mk))])
+    try:
+        opts = fit_lockstep(models, eng.gpfit_eval, maxiter=maxiter)
+        # the factors of the fitted parameters stay with the models: device_image takes them while the parameters stand
+        thetas = np.array([_theta_of(m) for m in models])
+        _, _, status = eng.gpfit_eval(np.arange(len(models), dtype=np.int32), thetas)
+        for i, m in enumerate(models):
+            m.optimizer = opts[i]
+            if status[i] == 0:
+                alpha, Li = eng.gpfit_factors(i)
+                m._device_factors = (thetas[i].copy(), alpha, Li, m.X.copy(), m.Y.copy())
+    finally:
+        eng.close()                           # (three J_t^2 fp64 images per GP: not left to the garbage collector)
+    enka.gpmodels = models
     return enka.gpmodels
 
 
@@ -480,11 +647,17 @@ def device_image(enka, gpmodels):
             b, w = float(np.asarray(mf.b).reshape(-1)[0]), np.asarray(mf.A, dtype=np.float64).reshape(p) * ls
         else:
             raise ValueError("the device GP path takes the Zero, Constant and Linear mean functions")
-        L, al = m._factor()
         par[i] = (m.kern.variance, m.likelihood.variance, b)
         mw[i] = w
-        alpha[i] = al.reshape(-1)
-        Li[i] = np.tril(np.linalg.solve(L, np.eye(Jt)))
+        # (theta, alpha, L^{-1}, X, Y) of a device fit: taken while the parameters AND the training data are what they were
+        kept = getattr(m, "_device_factors", None)
+        if (kept is not None and np.array_equal(kept[0], _theta_of(m)) and np.array_equal(kept[3], m.X)
+                and np.array_equal(kept[4], m.Y)):
+            alpha[i], Li[i] = kept[1], kept[2]
+        else:
+            L, al = m._factor()
+            alpha[i] = al.reshape(-1)
+            Li[i] = np.tril(np.linalg.solve(L, np.eye(Jt)))
     return dict(n=n, Jt=Jt, p=p, A=A, c=c, Z=Z, family=fam, par=par, mw=mw, alpha=alpha, Li=Li)
 
 

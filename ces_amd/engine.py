@@ -18,7 +18,7 @@ OK, EINVAL, ENOTPD, EHIP, ESTATE, EUNSUPPORTED, ENOCONV = 0, 1, 2, 3, 4, 5, 6
 F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
-ABI_VERSION = 1
+ABI_VERSION = 2
 MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
@@ -31,7 +31,9 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_profile_clock", "cesx_calibrate_mfma", "cesx_profile_gap", "cesx_moments_rest_lineal", "cesx_copy_cols_async",
            "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count",
            "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats",
-           "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept")
+           "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept",
+           "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors")
+GPFIT_MEANS = {"zero": 0, "constant": 1, "linear": 2}   # CESX_GPFIT_MEAN_*
 GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
 
 
@@ -59,6 +61,11 @@ class GpDesc(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("n_gp", C.c_int32), ("J_t", C.c_int32),
                 ("A", C.c_void_p), ("c", C.c_void_p), ("Z", C.c_void_p), ("family", C.c_void_p),
                 ("par", C.c_void_p), ("mw", C.c_void_p), ("alpha", C.c_void_p), ("Li", C.c_void_p)]
+
+
+class GpFitDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_gp", C.c_int32), ("J_t", C.c_int32), ("family", C.c_int32),
+                ("ard", C.c_int32), ("mean", C.c_int32), ("X", C.c_void_p), ("Y", C.c_void_p)]
 
 
 class CesxError(RuntimeError):
@@ -178,6 +185,10 @@ def load_library(path=None):
     lib.cesx_gp_predict.argtypes = [vp, vp, vp, vp, i32, vp]
     lib.cesx_gp_start.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.cesx_gp_accept.argtypes = [vp, i32, u64, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gpfit_set.argtypes = [vp, C.POINTER(GpFitDesc)]
+    lib.cesx_gpfit_ntheta.argtypes = [vp]
+    lib.cesx_gpfit_eval.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gpfit_factors.argtypes = [vp, i32, vp, vp]
     if lib.cesx_abi_version() != ABI_VERSION:
         raise ImportError("libcesx.so ABI %d != binding ABI %d" % (lib.cesx_abi_version(), ABI_VERSION))
     if path == LIB_PATH:
@@ -238,6 +249,10 @@ class Engine:
         if rc != OK:
             raise CesxError(rc, self.lib.cesx_last_error(None).decode())
         self._problem = None
+
+    def close(self):
+        """Destroy the handle and free its device memory now (what garbage collection would do later)."""
+        self.__del__()
 
     def __del__(self):
         pool = self.__dict__.pop("_out_pool", None)
@@ -881,6 +896,52 @@ class Engine:
                                                 mean.data_ptr(), None if var is None else var.data_ptr(),
                                                 None if logu is None else logu.data_ptr(), self._stream()))
         self._keep_gp_a = (U, P, mean, var, logu)
+
+    # -- GP training: the batched likelihood and gradient (include/cesx.h, cesx_gpfit_*; ces_amd/emulate.py drives it) --
+    def gpfit_set(self, X, Y, family, ard=True, mean="zero"):
+        """Install a fit problem: training inputs X (J_t, p) shared by the GPs, targets Y (n_gp, J_t), kernel family 0..3,
+        ARD, mean kind 'zero' / 'constant' / 'linear' (cesx_gpfit_set).  Returns the parameters per GP."""
+        X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
+        Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64))
+        if X.ndim != 2 or X.shape[1] != self.p:
+            raise ValueError("gpfit_set: X has shape %s, expected (J_t, %d)" % (X.shape, self.p))
+        if Y.ndim != 2 or Y.shape[1] != X.shape[0]:
+            raise ValueError("gpfit_set: Y has shape %s, expected (n_gp, %d)" % (Y.shape, X.shape[0]))
+        if mean not in GPFIT_MEANS:
+            raise ValueError("gpfit_set: unknown mean kind %r" % (mean,))
+        d = GpFitDesc(C.sizeof(GpFitDesc), Y.shape[0], X.shape[0], int(family), 1 if ard else 0, GPFIT_MEANS[mean],
+                      X.ctypes.data, Y.ctypes.data)
+        self.gpfit_n = self.gpfit_ntheta = 0
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gpfit_set(self._h, C.byref(d)))
+        self.gpfit_n, self.gpfit_Jt = int(Y.shape[0]), int(X.shape[0])
+        self.gpfit_ntheta = int(self.lib.cesx_gpfit_ntheta(self._h))
+        return self.gpfit_ntheta
+
+    def gpfit_eval(self, idx, theta):
+        """(lml (k,), grad (k, n_theta), status (k,) int32: OK or ENOTPD) of the GPs ``idx`` at the natural parameters
+        ``theta`` (k, n_theta) in ``GPR._get()`` order, one batched evaluation (cesx_gpfit_eval)."""
+        if not getattr(self, "gpfit_n", 0):
+            raise CesxError(ESTATE, "gpfit_eval: gpfit_set has not been called")
+        idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+        theta = np.ascontiguousarray(np.asarray(theta, dtype=np.float64))
+        k, nt = idx.size, self.gpfit_ntheta
+        if theta.shape != (k, nt):
+            raise ValueError("gpfit_eval: theta has shape %s, expected %s" % (theta.shape, (k, nt)))
+        lml, grad, status = np.empty(k), np.empty((k, nt)), np.empty(k, dtype=np.int32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gpfit_eval(self._h, k, idx.ctypes.data, theta.ctypes.data, lml.ctypes.data,
+                                                 grad.ctypes.data, status.ctypes.data, self._stream()))
+        return lml, grad, status
+
+    def gpfit_factors(self, i):
+        """(alpha (J_t,), L^{-1} (J_t, J_t)) of GP ``i`` as of its last evaluation, on the host (cesx_gpfit_factors)."""
+        if not getattr(self, "gpfit_n", 0):
+            raise CesxError(ESTATE, "gpfit_factors: gpfit_set has not been called")
+        alpha, Li = np.empty(self.gpfit_Jt), np.empty((self.gpfit_Jt, self.gpfit_Jt))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gpfit_factors(self._h, int(i), alpha.ctypes.data, Li.ctypes.data))
+        return alpha, Li
 
     def profile_enable(self, on=True):
         """on: False / True, 2 = bind only the events cesx_profile_gap needs, 3 / 4 = the update / the moments

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CESX_ABI_VERSION 1
+#define CESX_ABI_VERSION 2
 
 /* status codes */
 #define CESX_OK            0
@@ -451,6 +451,42 @@ int cesx_gp_predict(cesx_handle h, const void* X_dev, double* mean_dev, double* 
 int cesx_gp_start(cesx_handle h, int mode, const void* U_dev, const double* mean_dev, const double* var_dev, void* stream);
 int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev, const void* P_dev, const double* mean_dev,
                    const double* var_dev, const double* logu_dev, void* stream);
+
+/* ---- Emulate: training the GPs on device (ces_amd/emulate.py train_gps(device=True)) --------------------
+   The log marginal likelihood of n_gp exact GPs on SHARED training inputs X and its gradient, all GPs of a call in the same
+   launches (their number depends on J_t, not on n_gp).  GP i has the natural parameters, in GPR._get() order,
+       theta_i = (sigma^2, l_1..l_p (ard != 0) or one l, sn^2, then the mean's: none / c / A_1..A_p, b),
+   Ky = sigma^2 f(|x_a / l - x_b / l|) + sn^2 I (f of `family` as for cesx_gp_set; r from direct differences of the scaled
+   inputs, 0 on the diagonal), L = chol(Ky), alpha = L^{-T} L^{-1} (y_i - m(X)),
+       lml = -1/2 r^T alpha - sum log L_aa - 1/2 J_t log 2 pi,     d lml / d theta as GPR.log_marginal_likelihood_and_grad().
+   All arithmetic fp64 whatever the engine dtype; every sum runs in a fixed order: two calls are bit-identical.  The
+   positive transform of the optimiser stays with the caller. */
+#define CESX_GPFIT_MEAN_ZERO      0
+#define CESX_GPFIT_MEAN_CONSTANT  1
+#define CESX_GPFIT_MEAN_LINEAR    2
+typedef struct {
+    uint32_t struct_bytes;    /* sizeof(cesx_gpfit_desc) */
+    int32_t n_gp, J_t;        /* GPs, training points (the input dimension is the handle's p) */
+    int32_t family;           /* kernel family 0..3, one for the whole problem */
+    int32_t ard;              /* != 0: p lengthscales per GP, else one */
+    int32_t mean;             /* CESX_GPFIT_MEAN_* */
+    const double* X;          /* [J_t][p] training inputs, row-major */
+    const double* Y;          /* [n_gp][J_t] targets */
+} cesx_gpfit_desc;
+/* Copies the problem (host fp64) and allocates ALL the workspace of an evaluation (per GP three J_t^2 fp64 images: L,
+   L^{-T}, K^{-1}, padded to a multiple of 16; cesx_gpfit_eval allocates nothing).  Replaces an earlier fit problem; a call
+   that fails (a bad argument included) leaves the handle WITHOUT one and frees what it had allocated. */
+int cesx_gpfit_set(cesx_handle h, const cesx_gpfit_desc* desc);
+/* Parameters per GP of the installed fit problem (-1: none). */
+int cesx_gpfit_ntheta(cesx_handle h);
+/* The GPs idx[0 .. n_active) (distinct) at theta [n_active][n_theta]: lml [n_active], grad [n_active][n_theta] and
+   status [n_active] = CESX_OK or CESX_ENOTPD (a pivot of that GP's factorisation was not > 0: its lml and grad mean nothing,
+   the other GPs of the call are unaffected).  Host pointers; synchronises `stream`. */
+int cesx_gpfit_eval(cesx_handle h, int n_active, const int32_t* idx, const double* theta, double* lml, double* grad,
+                    int32_t* status, void* stream);
+/* alpha [J_t] and L^{-1} [J_t][J_t] (row-major, zero above the diagonal: what cesx_gp_desc takes) of GP i AS OF ITS LAST
+   EVALUATION, to the host.  Synchronises. */
+int cesx_gpfit_factors(cesx_handle h, int i, double* alpha, double* Li);
 
 /* ---- host staging ------------------------------------------------------ */
 
