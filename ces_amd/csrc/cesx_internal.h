@@ -111,6 +111,44 @@ __host__ __device__ __forceinline__ uint4x philox4x32_10(uint32_t c0, uint32_t c
     return {c0, c1, c2, c3};
 }
 
+// ---- the Metropolis test of the chain samplers (mh_accept_kernel, gp_score_kernel): one copy, because the two stages and
+// oracle/philox.py / oracle/stage_ref.py have to agree on it bit for bit ----
+
+// log of the uniform of global chain gj at step word `step`: row-quad word 0xffffffff, which no xi row uses (include/cesx.h)
+__device__ __forceinline__ double mh_log_uniform(unsigned long long gj, unsigned step, unsigned seed_lo, unsigned seed_hi) {
+    const uint4x r = philox4x32_10((uint32_t)gj, (uint32_t)(gj >> 32), 0xffffffffu, step, seed_lo, seed_hi);
+    const unsigned long long m53 = ((unsigned long long)(r.x >> 5) << 26) | (unsigned long long)(r.y >> 6);
+    return log(((double)m53 + 0.5) * 1.1102230246251565404e-16);      // 2^-53
+}
+
+// The chains' state as a score kernel sees it: the tail of MhArgs and GpScoreArgs, filled by mh_chains (below Engine)
+struct MhChains {
+    long long j_offset;
+    double* phi; unsigned long long* cnt;
+    const double* logu;                    // nullptr: the device uniform of `step`
+    unsigned seed_lo, seed_hi, step;
+    int start;                             // 1: phi := phi(X), counters cleared, no test
+};
+
+// Chain j with phi(X_j) = ph.  start: the chain's phi and counter are set.  Otherwise the test
+// log u < phi(U_j) - ph (ces/sample.py:188-191, :98-101), phi and the counter follow; true: the chain takes X_j.
+// (c by value: both kernels then compile to the instructions they had with the test written out in each; through a
+// reference mh_accept_kernel comes out in another block order.)
+__device__ __forceinline__ bool mh_test(const MhChains c, long long j, double ph) {
+    if (c.start) {
+        c.phi[j] = ph;
+        c.cnt[j] = 0ull;
+        return false;
+    }
+    const double lu = c.logu ? c.logu[j] : mh_log_uniform((unsigned long long)(c.j_offset + j), c.step, c.seed_lo, c.seed_hi);
+    if (lu < c.phi[j] - ph) {
+        c.phi[j] = ph;
+        c.cnt[j] += 1ull;
+        return true;
+    }
+    return false;
+}
+
 // Box-Muller radius sqrt(-2 ln u), u in [2^-25, 1): the bare v_log_f32 / v_sqrt_f32 (1 ulp each; no denormal scaling,
 // no Newton step around the square root -- the library forms cost 14 % of the noise draw's vector instructions, and the
 // draw is paid for in full wherever it runs: round 4).  Shared by normal4 and the in-kernel draw of kernels_update2.hip.
@@ -450,7 +488,7 @@ struct Engine {
     double *d_gp_Li = nullptr;                      // [n][gp_li_len] L^{-1} in v_mfma_f64_16x16x4 A-operand order
     double *d_gp_ws = nullptr;                      // the K* panels of the launches that do not fit in LDS
     size_t gp_ws_len = 0;
-    double *d_gp_LSi = nullptr;                     // [p][p] L_Sigma^{-1} of the problem (cesx_gp_start)
+    double *d_gp_LSi = nullptr;                     // [p][p] L_Sigma^{-1} of a dense Sigma, fp64 (cesx_mh_set_proposal)
     // ---- GP training: batched likelihood and gradient (cesx_gpfit_*, kernels_gpfit.hip) ----
     int gf_n = 0, gf_Jt = 0, gf_Jp = 0;             // GPs, training points, training points rounded up to 16 (gf_n 0: no fit problem)
     int gf_family = 0, gf_ard = 0, gf_mean = 0;     // kernel family, ARD, mean kind (CESX_GPFIT_MEAN_*): one of each per problem
@@ -656,6 +694,10 @@ int launch_noise(Engine& e, uint64_t step_index, void* xi, hipStream_t s);
 int launch_stage_forward(Engine& e, const void* A, const void* b, hipStream_t s);   // A, b -> d_Wfwd, d_Wfwd_f, d_bfwd
 int launch_moments_lineal(Engine& e, double* mom, hipStream_t s);                   // G part of the moments from the head + the installed linear map
 int launch_calibrate(Engine& e, double target_ms, double* tflops, double* clock_ghz, hipStream_t s);   // kernels_calib.hip
+// the chains' state of a score launch (launch_mh_score, launch_gp_score)
+inline MhChains mh_chains(const Engine& e, bool start, const double* logu, unsigned step) {
+    return {e.cfg.j_offset, e.d_mh_phi, e.d_mh_cnt, logu, (unsigned)e.cfg.seed, (unsigned)(e.cfg.seed >> 32), step, start ? 1 : 0};
+}
 // kernels_mh.hip: phi of the states X (with their forward map G, whitened when Gamma is dense) of every chain; start: into
 // Engine::d_mh_phi, counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_mh_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s);

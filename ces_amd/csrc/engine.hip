@@ -987,6 +987,10 @@ int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) 
     TRY(mh_upload_tri(e, bS.data(), &e.d_mh_W, &e.d_mh_Wf));
     e.mh_dense_prior = kind == CESX_MH_RW && !e.diag_sigma;
     char* t;
+    if (!e.diag_sigma) {                       // gp_score_kernel's fp64 L_Sigma^{-1} (RW and pCN: ces/sample.py:57 / :96)
+        if (!e.d_gp_LSi) TRY(dmalloc(e, &e.d_gp_LSi, (size_t)p * p * 8));
+        TRY(upload(e, e.d_gp_LSi, e.h_LSi.data(), (size_t)p * p * 8));
+    }
     if (e.mh_dense_prior) {
         TRY(mh_upload_tri(e, e.h_LSi.data(), &e.d_mh_Li, &e.d_mh_Li_f));
         std::vector<double> lb(e.rpad, 0.0);
@@ -1143,11 +1147,6 @@ int cesx_gp_start(cesx_handle h, int mode, const void* U, const double* mean, co
     TRY(gp_check_mode(e, mode, mean, var));
     SET_DEVICE(e);
     FLUSH(e);
-    if (!e.diag_sigma) {
-        CESX_HIP(hipDeviceSynchronize());
-        if (!e.d_gp_LSi) TRY(dmalloc(e, &e.d_gp_LSi, (size_t)e.p * e.p * 8));
-        TRY(upload(e, e.d_gp_LSi, e.h_LSi.data(), (size_t)e.p * e.p * 8));
-    }
     TRY(launch_gp_score(e, mode, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
     e.mh_started = true;
     e.mh_steps = 0;

@@ -14,7 +14,7 @@
 // not fit in LDS (Jp + p > 608) lives in a global workspace per workgroup slot and the grid strides over the tiles.
 //
 // gp_score_kernel: one thread per chain, phi from the fp64 GP rows in the likelihood mode of include/cesx.h, the prior term
-// for RW and pCN alike (ces/sample.py subtracts prior.logpdf for both), the test and the copy U := P of the accepted columns.
+// for RW and pCN alike (ces/sample.py subtracts prior.logpdf for both), the test (mh_test, cesx_internal.h: mh_accept_kernel's) and the copy U := P of the accepted columns.
 #include "cesx_internal.h"
 
 namespace cesx {
@@ -181,11 +181,7 @@ struct GpScoreArgs {
     int mode;
     const T* X; const double *mu, *sw, *LSi; int p;      // prior: diagonal (sw) or dense (LSi = L_Sigma^{-1})
     T* U;
-    long long j_offset;
-    double* phi; unsigned long long* cnt;
-    const double* logu;
-    unsigned seed_lo, seed_hi, step;
-    int start;
+    MhChains c;                            // (last: the tail it shares with MhArgs)
 };
 
 constexpr int GPS_THREADS = 256;
@@ -225,27 +221,8 @@ void gp_score_kernel(const GpScoreArgs<T> a) {
     } else {
         for (int r = 0; r < p; ++r) { const double d = (double)a.X[(size_t)r * a.M + j] - a.mu[r]; s = fma(a.sw[r], d * d, s); }
     }
-    const double ph = 0.5 * s;
-    if (a.start) {
-        a.phi[j] = ph;
-        a.cnt[j] = 0ull;
-        return;
-    }
-    double lu;
-    if (a.logu) {
-        lu = a.logu[j];
-    } else {
-        // the uniform of chain j as mh_accept_kernel draws it (include/cesx.h)
-        const unsigned long long gj = (unsigned long long)(a.j_offset + j);
-        const uint4x r = philox4x32_10((uint32_t)gj, (uint32_t)(gj >> 32), 0xffffffffu, a.step, a.seed_lo, a.seed_hi);
-        const unsigned long long m53 = ((unsigned long long)(r.x >> 5) << 26) | (unsigned long long)(r.y >> 6);
-        lu = log(((double)m53 + 0.5) * 1.1102230246251565404e-16);      // 2^-53
-    }
-    if (lu < a.phi[j] - ph) {
-        a.phi[j] = ph;
-        a.cnt[j] += 1ull;
+    if (mh_test(a.c, j, 0.5 * s))
         for (int r = 0; r < p; ++r) a.U[(size_t)r * a.M + j] = a.X[(size_t)r * a.M + j];
-    }
 }
 
 template <typename T>
@@ -256,10 +233,7 @@ static int gp_score_t(Engine& e, int mode, bool start, const void* X, const doub
     a.y = e.d_y; a.gw = e.d_gw; a.gam = e.d_Gamma; a.Lg = e.whiten ? e.d_Wh : nullptr;
     a.mode = mode;
     a.X = (const T*)X; a.mu = e.d_mu; a.sw = e.d_sw; a.LSi = e.diag_sigma ? nullptr : e.d_gp_LSi; a.p = e.p;
-    a.U = (T*)U; a.j_offset = e.cfg.j_offset;
-    a.phi = e.d_mh_phi; a.cnt = e.d_mh_cnt; a.logu = logu;
-    a.seed_lo = (unsigned)e.cfg.seed; a.seed_hi = (unsigned)(e.cfg.seed >> 32); a.step = step;
-    a.start = start ? 1 : 0;
+    a.U = (T*)U; a.c = mh_chains(e, start, logu, step);
     hipLaunchKernelGGL((gp_score_kernel<T>), dim3((unsigned)((e.J + GPS_THREADS - 1) / GPS_THREADS)), dim3(GPS_THREADS), 0, s, a);
     CESX_HIP(hipGetLastError());
     return CESX_OK;

@@ -5,6 +5,8 @@
 //     phi(x) = 1/2 sum_i gw_i (g_i - y_i)^2  +  1/2 sum_r sw_r (x_r - mu_r)^2                  (:141-152 / :170-180)
 //     accept  log u < phi(U) - phi(P)   ->   U := P, phi := phi(P), counter + 1                (:188-191)
 //
+// The test itself, with the uniform of the chain, is mh_test (cesx_internal.h), which gp_score_kernel shares.
+//
 // (the prior rows: the state itself with mu, 1 / Sigma_rr for a diagonal Sigma; w = L_Sigma^{-1} (x - mu) with unit
 // weights for a dense one; none for pCN.)  V chains per lane (one 16-byte load: 4 floats / 2 doubles; a wave reads 1 KiB
 // of a row per instruction) and the rows of a column split over the MH_NW waves of a workgroup (row r to wave r % MH_NW),
@@ -27,11 +29,8 @@ struct MhArgs {
     const T* G; const double* y; const double* gw; int n;      // data rows
     const T* X; const double* mu; const double* sw; int nx;    // prior rows (mu / sw nullptr: 0 / 1; nx = 0: no prior term)
     const T* P; T* U; int p;                                   // accept: accepted columns of P copied into U
-    long long J, j_offset;
-    double* phi; unsigned long long* cnt;
-    const double* logu;                                        // nullptr: the device uniform of `step`
-    unsigned seed_lo, seed_hi, step;
-    int start;                                                 // 1: phi := phi(X), counters cleared, no test
+    long long J;
+    MhChains c;                                                // (last: the tail it shares with GpScoreArgs)
 };
 
 // V consecutive values of one row from column j0 on, in fp64 (VEC: j0 + V <= J and 16-byte aligned)
@@ -95,32 +94,12 @@ void mh_accept_kernel(const MhArgs<T> a) {
                 double t = 0.0;
 #pragma unroll
                 for (int w = 0; w < MH_NW; ++w) t += part[w][lane * V + e];
-                const double ph = 0.5 * t;
-                if (a.start) {
-                    a.phi[j] = ph;
-                    a.cnt[j] = 0ull;
-                } else {
-                    double lu;
-                    if (a.logu) {
-                        lu = a.logu[j];
-                    } else {
-                        // the uniform of chain j: row-quad word 0xffffffff, which no xi row uses (include/cesx.h)
-                        const unsigned long long gj = (unsigned long long)(a.j_offset + j);
-                        const uint4x r = philox4x32_10((uint32_t)gj, (uint32_t)(gj >> 32), 0xffffffffu, a.step, a.seed_lo, a.seed_hi);
-                        const unsigned long long m53 = ((unsigned long long)(r.x >> 5) << 26) | (unsigned long long)(r.y >> 6);
-                        lu = log(((double)m53 + 0.5) * 1.1102230246251565404e-16);      // 2^-53
-                    }
-                    if (lu < a.phi[j] - ph) {
-                        acc = 1;
-                        a.phi[j] = ph;
-                        a.cnt[j] += 1ull;
-                    }
-                }
+                acc = mh_test(a.c, j, 0.5 * t);
             }
             take[lane * V + e] = acc;
         }
     }
-    if (a.start) return;
+    if (a.c.start) return;
     __syncthreads();
     // the accepted columns: U := P (every wave its rows)
     int tk[V];
@@ -154,10 +133,7 @@ static int mh_score_t(Engine& e, bool start, const void* X, const void* G, void*
     a.sw = rw && !e.mh_dense_prior ? e.d_sw : nullptr;
     a.nx = rw ? e.p : 0;
     a.P = (const T*)X; a.U = (T*)U; a.p = e.p;
-    a.J = e.J; a.j_offset = e.cfg.j_offset;
-    a.phi = e.d_mh_phi; a.cnt = e.d_mh_cnt; a.logu = logu;
-    a.seed_lo = (unsigned)e.cfg.seed; a.seed_hi = (unsigned)(e.cfg.seed >> 32); a.step = step;
-    a.start = start ? 1 : 0;
+    a.J = e.J; a.c = mh_chains(e, start, logu, step);
     auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     const bool vec = e.J % V == 0 && al16(a.G) && al16(a.X) && (start || (al16(a.P) && al16(a.U)));
     const dim3 grid((unsigned)((e.J + BN - 1) / BN));

@@ -220,17 +220,24 @@ class MCMC(object):
             self._mh_key = key
         return self._mh_eng
 
-    def _model_mh_device(self, model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, kwargs):
+    def _mh_device(self, enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi):
+        """M = kwargs['chains'] chains on the engine: what ``model_mh(chains=)`` and ``gp_mh(chains=)`` have in common.
+
+        Gamma                    the data covariance handed to ``set_problem``
+        scales_of(update)        the proposal scales S (p, p), formed once ``prior`` and ``update`` have been checked
+        bind(eng, M)             runs after ``mh_set_proposal``; returns ``score_start(U)`` (phi of the states U into the
+                                 engine, counters cleared) and ``score_accept(step, U, P, logu)`` (phi of P, the test, U := P
+                                 where it passes)
+        resume_keeps_start_phi   the reference's model_mh scores the START point before it looks for ``self.samples`` and
+                                 keeps that phi for the resumed states (ces/sample.py:131-163); its gp_mh scores the resumed
+                                 states (:31-39).  True: the first, for ``noise='numpy'`` (``noise='device'`` re-scores the
+                                 resumed states either way: the exact resume of model_mh's docstring)
+        """
         import torch
-        from .utils import hook_takes_out
         M = kwargs["chains"]
         if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or M < 1:
             raise ValueError("chains must be an integer >= 1, got %r" % (M,))
         M = int(M)
-        if getattr(model, "type", None) == "pde" or not hasattr(model, "forward_device"):
-            raise ValueError("chains=: the device path evaluates the forward map on the GPU through model.forward_device, "
-                             "which %r does not offer ('pde' models keep their forward map on the host); run model_mh "
-                             "without chains=" % (model,))
         if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
             raise ValueError("chains=: the prior must expose .mean and .cov (a frozen scipy.stats.multivariate_normal does)")
         update = kwargs.get("update", None)
@@ -239,13 +246,7 @@ class MCMC(object):
         if self.noise not in ("numpy", "device"):
             raise ValueError("noise must be 'numpy' or 'device', got %r" % (self.noise,))
         p, n = enka.p, enka.n_obs
-        # the scales exactly as the reference forms them (:122-129)
-        if enka_scaling:
-            scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(p, p))
-        else:
-            scales = delta * np.eye(p)
-        if update == "pCN":
-            scales = np.linalg.cholesky(prior.cov)
+        scales = scales_of(update)
         start = kwargs.get("start", "mean")
         if start == "mean":
             U0 = np.repeat(np.asarray(enka.Ustar, dtype=np.float64).mean(axis=1).reshape(p, 1), M, axis=1)
@@ -262,46 +263,34 @@ class MCMC(object):
         eng = self._mh_engine(p, n, M)
         eng.set_problem(np.asarray(self.y_obs, dtype=np.float64).reshape(n), Gamma, mu, cov, mu)
         eng.mh_set_proposal(update, scales, kwargs.get("beta", 0.5))
-        takes_out = hook_takes_out(model.forward_device)
+        score_start, score_accept = bind(eng, M)
+        P = eng.empty(p)
 
-        def fwd(u, out):
-            if takes_out:
-                return model.forward_device(eng, u, out=out)
-            out.copy_(model.forward_device(eng, u))
-            return out
-
-        U = eng.to_device(U0, p, "mh_U").clone()
-        G, P, GP = eng.empty(n), eng.empty(p), eng.empty(n)
-        fwd(U, G)
-        eng.mh_start(U, G)                                # phi of the start states (:131-152)
         resume = hasattr(self, "samples")
+        prev, base, kept = None, 0, [U0.copy()]
+        if not resume or resume_keeps_start_phi:
+            U = eng.to_device(U0, p, "mh_U").clone()
+            score_start(U)
         if resume:
             prev = np.asarray(self.samples)
             if (M == 1 and prev.ndim != 2) or (M > 1 and (prev.ndim != 3 or prev.shape[2] != M)) or prev.shape[0] != p:
                 raise ValueError("resume: self.samples %s does not hold %d chain(s) of dimension %d" % (prev.shape, M, p))
             last = prev[:, -1] if M == 1 else prev[:, -1, :]
             U = eng.to_device(np.ascontiguousarray(last.reshape(p, M)), p, "mh_U").clone()
-            if self.noise == "device":                    # exact resume: phi of the resumed states
-                fwd(U, G)
-                eng.mh_start(U, G)
-            base = int(getattr(self, "_mh_next_step", 0))
-            kept = []
-        else:
-            prev = None
-            base = 0
-            kept = [U0.copy()]
+            if not resume_keeps_start_phi or self.noise == "device":
+                score_start(U)
+            base, kept = int(getattr(self, "_mh_next_step", 0)), []
 
         for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
             step = base + k
             xi_t = logu_t = None
-            if self.noise == "numpy":
+            if self.noise == "numpy":                     # the reference's draws in the reference's order
                 xi = np.random.normal(0, 1, [p, M])       # :199 / :202
-                logu = np.log(np.random.uniform(size=M))  # :188
+                logu = np.log(np.random.uniform(size=M))  # :188 / :98
                 xi_t = eng.to_device(xi, p, "mh_xi")
                 logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
             eng.mh_propose(step, U, xi=xi_t, out=P)
-            fwd(P, GP)
-            eng.mh_accept(step, U, P, GP, logu=logu_t)
+            score_accept(step, U, P, logu_t)
             if (k + 1) % stride == 0 or k + 1 == n_mcmc:
                 kept.append(eng.to_host(U))
         steps, rate, per = eng.mh_stats(per_chain=True)
@@ -315,24 +304,49 @@ class MCMC(object):
         self.samples_device = U
         self._mh_next_step = base + n_mcmc
 
+    def _model_mh_device(self, model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, kwargs):
+        from .utils import hook_takes_out
+        if getattr(model, "type", None) == "pde" or not hasattr(model, "forward_device"):
+            raise ValueError("chains=: the device path evaluates the forward map on the GPU through model.forward_device, "
+                             "which %r does not offer ('pde' models keep their forward map on the host); run model_mh "
+                             "without chains=" % (model,))
+        p, n = enka.p, enka.n_obs
+
+        def scales_of(update):                            # exactly as the reference forms them (:122-129)
+            if enka_scaling:
+                scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(p, p))
+            else:
+                scales = delta * np.eye(p)
+            return np.linalg.cholesky(prior.cov) if update == "pCN" else scales
+
+        def bind(eng, M):
+            takes_out = hook_takes_out(model.forward_device)
+            G, GP = eng.empty(n), eng.empty(n)
+
+            def fwd(u, out):
+                if takes_out:
+                    return model.forward_device(eng, u, out=out)
+                out.copy_(model.forward_device(eng, u))
+                return out
+
+            def score_start(U):
+                fwd(U, G)
+                eng.mh_start(U, G)
+
+            def score_accept(step, U, P, logu):
+                fwd(P, GP)
+                eng.mh_accept(step, U, P, GP, logu=logu)
+            return score_start, score_accept
+
+        self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi=True)
+
     def _gp_mh_device(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
         import torch
         from . import emulate
-        M = kwargs["chains"]
-        if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or M < 1:
-            raise ValueError("chains must be an integer >= 1, got %r" % (M,))
-        M = int(M)
         host = "; run gp_mh without chains= (the host path)"
         if kwargs.get("pca_tools", None) is not None or kwargs.get("separable", False):
             raise ValueError("chains=: pca_tools and separable need a per-chain n x n factorisation or one point at a "
                              "time" + host)
-        if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
-            raise ValueError("chains=: the prior must expose .mean and .cov (a frozen scipy.stats.multivariate_normal does)")
-        update = kwargs.get("update", None)
-        if update not in (None, "pCN"):
-            raise ValueError("chains=: unknown update %r (None or 'pCN')" % (update,))
-        if self.noise not in ("numpy", "device"):
-            raise ValueError("noise must be 'numpy' or 'device', got %r" % (self.noise,))
         p, n = enka.p, enka.n_obs
         gpmodels = kwargs.get("gpmodels", None)
         gpmodels = enka.gpmodels if gpmodels is None else gpmodels
@@ -354,70 +368,24 @@ class MCMC(object):
             img = emulate.device_image(enka, gpmodels)
         except ValueError as exc:
             raise ValueError("chains=: %s" % exc)
-        if enka_scaling:                                  # (:23-26; pCN takes the same scales)
-            scales = delta * np.linalg.cholesky(np.cov(enka.Ustar))
-        else:
-            scales = delta * np.eye(p)
-        start = kwargs.get("start", "mean")
-        if start == "mean":
-            U0 = np.repeat(np.asarray(enka.Ustar, dtype=np.float64).mean(axis=1).reshape(p, 1), M, axis=1)
-        elif start == "ensemble":
-            if M > enka.Ustar.shape[1]:
-                raise ValueError("start='ensemble' needs chains <= J = %d, got %d" % (enka.Ustar.shape[1], M))
-            U0 = np.array(enka.Ustar[:, :M], dtype=np.float64)
-        else:
-            raise ValueError("start must be 'mean' or 'ensemble', got %r" % (start,))
-        stride = max(1, int(self.trace_stride))
-        mu = np.asarray(prior.mean, dtype=np.float64).reshape(p)
-        cov = np.asarray(prior.cov, dtype=np.float64).reshape(p, p)
 
-        eng = self._mh_engine(p, n, M)
-        eng.set_problem(np.asarray(self.y_obs, dtype=np.float64).reshape(n), G, mu, cov, mu)
-        eng.mh_set_proposal(update, scales, kwargs.get("beta", 0.5))
-        eng.gp_set(img)
-        nugget, want_var = kwargs.get("nugget", True), mode != "gamma"
-        rows = lambda: torch.empty((n, M), dtype=torch.float64, device=eng.device)    # noqa: E731
-        mean_u, mean_p = rows(), rows()
-        var_u, var_p = (rows(), rows()) if want_var else (None, None)
+        def scales_of(update):                            # (:23-26; pCN takes the same scales)
+            return delta * np.linalg.cholesky(np.cov(enka.Ustar)) if enka_scaling else delta * np.eye(p)
 
-        resume = hasattr(self, "samples")
-        if resume:                                        # (:31-39: phi of the resumed states)
-            prev = np.asarray(self.samples)
-            if (M == 1 and prev.ndim != 2) or (M > 1 and (prev.ndim != 3 or prev.shape[2] != M)) or prev.shape[0] != p:
-                raise ValueError("resume: self.samples %s does not hold %d chain(s) of dimension %d" % (prev.shape, M, p))
-            last = prev[:, -1] if M == 1 else prev[:, -1, :]
-            U = eng.to_device(np.ascontiguousarray(last.reshape(p, M)), p, "mh_U").clone()
-            base = int(getattr(self, "_mh_next_step", 0))
-            kept = []
-        else:
-            prev = None
-            U = eng.to_device(U0, p, "mh_U").clone()
-            base = 0
-            kept = [U0.copy()]
-        P = eng.empty(p)
-        eng.gp_predict(U, nugget=nugget, var=want_var, out=(mean_u, var_u))
-        eng.gp_start(mode, U, mean_u, var_u)
+        def bind(eng, M):
+            eng.gp_set(img)
+            nugget, want_var = kwargs.get("nugget", True), mode != "gamma"
+            rows = lambda: torch.empty((n, M), dtype=torch.float64, device=eng.device)    # noqa: E731
+            mean_u, mean_p = rows(), rows()
+            var_u, var_p = (rows(), rows()) if want_var else (None, None)
 
-        for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
-            step = base + k
-            xi_t = logu_t = None
-            if self.noise == "numpy":
-                xi = np.random.normal(0, 1, [p, M])       # :199 / :202
-                logu = np.log(np.random.uniform(size=M))  # :98
-                xi_t = eng.to_device(xi, p, "mh_xi")
-                logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
-            eng.mh_propose(step, U, xi=xi_t, out=P)
-            eng.gp_predict(P, nugget=nugget, var=want_var, out=(mean_p, var_p))
-            eng.gp_accept(mode, step, U, P, mean_p, var_p, logu=logu_t)
-            if (k + 1) % stride == 0 or k + 1 == n_mcmc:
-                kept.append(eng.to_host(U))
-        steps, rate, per = eng.mh_stats(per_chain=True)
+            def score_start(U):
+                eng.gp_predict(U, nugget=nugget, var=want_var, out=(mean_u, var_u))
+                eng.gp_start(mode, U, mean_u, var_u)
 
-        new = np.stack(kept, axis=1) if kept else np.zeros((p, 0, M))      # (p, n_new, M)
-        if M == 1:
-            new = new[:, :, 0]
-        self.samples = new if prev is None else np.concatenate([prev, new], axis=1)
-        self.accept = rate
-        self.accept_chains = per.astype(np.float64) / max(1, n_mcmc)
-        self.samples_device = U
-        self._mh_next_step = base + n_mcmc
+            def score_accept(step, U, P, logu):
+                eng.gp_predict(P, nugget=nugget, var=want_var, out=(mean_p, var_p))
+                eng.gp_accept(mode, step, U, P, mean_p, var_p, logu=logu)
+            return score_start, score_accept
+
+        self._mh_device(enka, n_mcmc, prior, kwargs, G, scales_of, bind, resume_keeps_start_phi=False)
