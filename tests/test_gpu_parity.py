@@ -923,9 +923,12 @@ def test_update_through_the_cholesky_factor(eng_mod, monkeypatch, p, n, J):
     """K3 through the Cholesky factor (kernels_update4.hip; fp32, diagonal Sigma, 224 < p <= 256): C Sigma^{-1} (U - mu) =
     L (L^T Sigma^{-1} U) - C Sigma^{-1} mu with C = L L^T as factored (ces/calibrate.py:476-478, :484-488).  Against the pinned
     oracle with an injected block (ragged p, n and J included: the last 32-row block, the last G tile and the last workgroup
-    are partial), against the dense hk-free form (CESX_CHAIN=0) to fp32 rounding, a non-zero prior mean (the C Sigma^{-1} mu
-    term lives in the bias), the factor cesx_debug_dense reports after a step that kept it in the image only, and the block
-    the engine draws itself when none was injected or drawn ahead."""
+    are partial), against the dense hk-free form (CESX_CHAIN=0) to fp32 rounding, the factor cesx_debug_dense reports after a
+    step that kept it in the image only, and the block the engine draws itself when none was injected or drawn ahead.
+    The prior mean is non-zero here, but with Sigma ~ 100 its term C Sigma^{-1} mu moves U_next by ~3e-7 of its scale: neither
+    bar of this test (1e-3 and 2e-5 of max|U|) can see it, nor the prior term as a whole.  What holds the prior, mu and alpha
+    terms, and every row block and k-tile of the chained image, is the elementwise bar of tests/test_gpu_calibrate_edges.py
+    (test_update4_kernel_and_its_neighbours, the 'prior' problem family)."""
     from oracle import ces_numpy as oc
     d = _synthetic(p, n, J, seed=p + n + J + 1)
     rng = np.random.default_rng(5)

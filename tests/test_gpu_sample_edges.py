@@ -22,6 +22,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import rel_err  # noqa: E402
+from edge_helpers import guarded, guards_intact, put, same_bits  # noqa: E402,F401
 from test_gpu_mcmc import _problem  # noqa: E402
 
 from oracle import stage_ref as sr  # noqa: E402
@@ -29,8 +30,6 @@ from oracle import stage_ref as sr  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 STEPS = 20
-GUARD = 64                       # elements of sentinel before and after every guarded buffer (a multiple of 16 bytes)
-SENTINEL = -777.25
 ENSEMBLE_BAR = {"float64": 1e-6, "float32": 1e-3}
 WORST = {}                       # per part: chain-steps left out, chain-steps, worst ratio of an error to its bar
 
@@ -41,33 +40,6 @@ def eng_mod():
     from ces_amd import engine
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return engine
-
-
-def guarded(eng, rows, shift=0):
-    """A (rows, J) view ``shift`` elements into a larger buffer: GUARD + shift sentinels before it, GUARD after."""
-    import torch
-    flat = torch.full((GUARD + shift + rows * eng.J + GUARD,), SENTINEL, dtype=eng.torch_dtype, device=eng.device)
-    view = flat[GUARD + shift:GUARD + shift + rows * eng.J].view(rows, eng.J)
-    assert view.is_contiguous() and (view.data_ptr() % 16 == 0) == (shift == 0)
-    return flat, view
-
-
-def guards_intact(flat, view):
-    head = (view.data_ptr() - flat.data_ptr()) // flat.element_size()
-    g = flat.cpu().numpy()
-    return bool(np.all(g[:head] == SENTINEL) and np.all(g[head + view.numel():] == SENTINEL))
-
-
-def put(view, a):
-    import torch
-    view.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(view.device))
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.dtype == b.dtype and a.shape == b.shape
-    u = np.uint32 if a.dtype == np.float32 else np.uint64
-    return a.view(u) == b.view(u)
 
 
 def note(part, ref=None, ratio=None):
