@@ -1,6 +1,7 @@
 // Internal declarations shared by the HIP translation units of libcesx.so.
 // gfx950 (MI355X / CDNA4) only.
 #pragma once
+#include <array>
 #include <cstddef>
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -261,6 +262,12 @@ struct GramPart {
     int *d_type_hdr = nullptr, *d_rows = nullptr, *d_wblk = nullptr, *d_blk_rc = nullptr, *d_row_own = nullptr;
     void* d_slabs = nullptr;            // per type [slices][blocks of the type][tile*tile] engine dtype
     double* d_rowsum_part = nullptr;    // [row-sum slots][p+n]
+    // the plan's flattened tables: allocated, uploaded and freed from this one list (gram_part_alloc / gram_part_free)
+    struct Table { int** dev; const std::vector<int>* host; };
+    std::array<Table, 5> tables() {
+        return {{{&d_type_hdr, &plan.type_hdr}, {&d_rows, &plan.rows}, {&d_wblk, &plan.wblk}, {&d_blk_rc, &plan.blk_rc},
+                 {&d_row_own, &plan.row_own}}};
+    }
 };
 
 // ---------------------------------------------------------------------------
@@ -354,7 +361,7 @@ struct Engine {
     bool fuse_center_auto = true;     // no CESX_FUSE_CENTER given: fused where the step takes the hk-free form AND the second Gram launch is
                                       // short (Engine::gram_b_short: small ensembles -- the side chain is then the step's critical path and
                                       // the host's launches its floor; C4 0.0790 -> 0.0728 ms/step, round 4), not at C2 (see below)
-    bool gram_b_short = false;        // the second Gram launch's MFMA time is below ~60 us (cesx_create)
+    bool gram_b_short = false;        // the second Gram launch's MFMA time is below ~60 us (plan_gram_parts)
     bool fuse_center_ok = false;      // CESX_FUSE_CENTER=1 switches that on (round 4: also with the hk-free form -- the tail launch then forms C, M, ubar
                                       // and the trace / bias sums itself; measured 0.3988 against 0.3952 ms/step at C2: the side chain ends 15 us
                                       // earlier, the noise draw behind it meets the end of the second Gram launch, and the tail launch is longer).  Measured at C2 (round 3, row sums staged through LDS): the factorisation
@@ -431,7 +438,7 @@ struct Engine {
     void* d_W = nullptr;           // [rpad][ktot]
     void* d_Wf = nullptr;          // the same matrix in the fragment-major order of kernels_update2.hip (fp32) / kernels_update3.hip (fp64)
     bool update_v2 = true;         // fp32 K3 through the LDS-DMA kernel (CESX_UPDATE_V1=1 switches back)
-    int  center_u_wgs = 256;       // workgroups of the U-only centring on the side stream (see cesx_create)
+    int  center_u_wgs = 256;       // workgroups of the U-only centring on the side stream (see plan_gram_parts)
     bool gram_v2 = true;           // K1 through the LDS-DMA kernel when the shapes allow (CESX_GRAM_V1=1 switches back)
     int num_cus = 256;
     void* d_bias = nullptr;        // [rpad]
@@ -566,10 +573,32 @@ struct Engine {
 // ---------------------------------------------------------------------------
 int launch_colsum(Engine& e, const void* U, const void* G, double* sums, hipStream_t s);
 int launch_set_shift(Engine& e, const double* sums, hipStream_t s);
-int launch_gram(Engine& e, int part, const void* U, const void* G, double* mom, hipStream_t s, bool no_reduce = false);   // part 0 / 1
-int launch_gram_reduce(Engine& e, int part, double* mom, hipStream_t s, hipEvent_t stop = nullptr, const MetricFin* fin = nullptr);   // the fp64 slab reduce of that launch (stop: bound to its completion)
-// kernels_gram2.hip (LDS-DMA Gram): CESX_OK, an error, or -1 when the launch does not qualify (caller falls back)
-int launch_gram2(Engine& e, int part, const void* U, const void* G, hipStream_t s);
+// ---- K1: the moments launches (kernels_gram.hip, kernels_gram2.hip) ----
+// The plans of both launches of this engine (Engine::gp[.].plan), with center_u_wgs and gram_b_short; needs p, n, J, Jg, the
+// dtype and num_cus, no device.  CESX_EINVAL (Engine::err) when a plan does not fit in LDS.
+int plan_gram_parts(Engine& e);
+int gram_part_alloc(Engine& e, GramPart& gp);      // the plan's tables (uploaded), its slabs and row-sum slots (zeroed)
+void gram_part_free(GramPart& gp);
+// One moments launch: the Gram kernel of a part and the fp64 reduce of its slabs into `mom`; call sites name the fields they use.
+struct GramLaunch {
+    int part = 0;                     // 0: the U x U blocks, 1: the rest
+    const void *U = nullptr, *G = nullptr;
+    double* mom = nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t bound_stop = nullptr;  // != nullptr: bound to the reduce kernel's own completion signal (no marker packet behind it)
+    MetricFin fin{};                  // fin.part != nullptr: the previous update's metric finalisation rides on the reduce launch
+};
+enum class GramKernel {
+    None,                                     // the part has no block (the reduce still runs)
+    Gram2, Gram2Imm, Gram2Sg, Gram2SgImm,     // gram2_kernel<T, sg, imm>: the LDS-DMA kernel
+    Gram1Aligned, Gram1Scalar                 // gram_kernel<T, aligned>: the register-staged kernel
+};
+// the kernel launch_moments runs for this part of these arrays
+GramKernel pick_gram_kernel(const Engine& e, int part, const void* U, const void* G);
+int launch_moments(Engine& e, const GramLaunch& L);
+// kernels_gram2.hip: the staged rows gram2_kernel takes, and (imm) whether its ds_read offsets reach both slots
+bool gram2_rows_ok(int nrows, bool* imm);
+int launch_gram2(Engine& e, const GramLaunch& L, GramKernel k);      // k: one of the Gram2 arms
 // upd_ok: an update kernel takes the hk-free image of this step (pick_update_kernel)
 int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int phase, hipStream_t s, bool upd_ok = false);
 // whether launch_dense (phase 0) writes the hk-free image for this step when an update kernel takes it
@@ -685,7 +714,8 @@ int launch_metric_final(Engine& e, const double* mom, bool publish, hipStream_t 
 MetricFin metric_fin_args(Engine& e, const double* mom, bool publish);     // (publish: takes the next sequence number; mom == nullptr: the engine's own copy d_lag)
 int launch_publish(Engine& e, hipStream_t s);
 int launch_absmax_final(Engine& e, int nparts, double* absmax_out, hipStream_t s);
-int potrf_ld(int n);
+constexpr int PNB = 32;    // leading dimensions of Cholesky factors are rounded up to this
+inline int potrf_ld(int n) { return (n + PNB - 1) / PNB * PNB; }
 int gram_nbw(int dtype);
 int gram_tile(int dtype);
 int gram_kt(int dtype);
@@ -749,6 +779,13 @@ void set_global_error(const std::string& msg);
         }                                                                           \
     } while (0)
 
+// zeroed device memory (never an empty allocation)
+template <typename P> int dmalloc(Engine& e, P** ptr, size_t bytes) {
+    CESX_HIP(hipMalloc(reinterpret_cast<void**>(ptr), bytes ? bytes : 8));
+    CESX_HIP(hipMemset(*ptr, 0, bytes ? bytes : 8));
+    return CESX_OK;
+}
+
 // the argument fields every update kernel but update4_kernel shares (UpdArgs<T>, Upd2Args, Upd3Args)
 template <typename T, typename A>
 inline void pack_update_common(A& a, const Engine& e, const UpdateLaunch& L, const UpdateSegs& g) {
@@ -778,6 +815,26 @@ int launch_update_bound(Engine& e, K kern, dim3 grid, int lds, A& a, int prof_wh
         a.clk = (prof.a && prof.b) ? e.d_clk : nullptr;
         if (prof.on()) hipExtLaunchKernelGGL(kern, grid, dim3(256), (unsigned)lds, s, prof.a, prof.b, 0, a);
         else hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
+    }
+    CESX_HIP(hipGetLastError());
+    return CESX_OK;
+}
+
+// One launch of a Gram kernel over the workgroups of the part's plan (gram_kernel and gram2_kernel take the same arguments).
+// bound: the profiling events are tied to the kernel's own start / end (ProfScope); otherwise they are recorded around it.
+template <typename T, typename K>
+int launch_gram_kernel(Engine& e, const GramLaunch& L, K kern, int threads, int lds, bool bound) {
+    GramPart& gp = e.gp[L.part];
+    const dim3 grid(gp.plan.total_wgs), block(threads);
+    CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    {
+        ProfScope prof(e, (e.profile_gap_only && L.part == 0) ? -1 : 0, L.s, bound);      // (gap-only: the second launch's stop, nothing else)
+        auto launch = [&](auto... args) {
+            if (bound && prof.on()) hipExtLaunchKernelGGL(kern, grid, block, (unsigned)lds, L.s, prof.a, prof.b, 0, args...);
+            else hipLaunchKernelGGL(kern, grid, block, lds, L.s, args...);
+        };
+        launch((const T*)L.U, (const T*)L.G, (const T*)e.d_shiftT, e.p, e.n, (long long)e.J, (const int*)gp.d_type_hdr, gp.plan.ntypes,
+               (const int*)gp.d_rows, (const int*)gp.d_wblk, (T*)gp.d_slabs, gp.d_rowsum_part);
     }
     CESX_HIP(hipGetLastError());
     return CESX_OK;

@@ -60,11 +60,6 @@ bool is_diagonal(int n, const double* A) {
     return true;
 }
 
-template <typename P> int dmalloc(Engine& e, P** ptr, size_t bytes) {
-    CESX_HIP(hipMalloc(reinterpret_cast<void**>(ptr), bytes ? bytes : 8));
-    CESX_HIP(hipMemset(*ptr, 0, bytes ? bytes : 8));
-    return CESX_OK;
-}
 int upload(Engine& e, void* dst, const void* src, size_t bytes) {
     CESX_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
     return CESX_OK;
@@ -269,48 +264,8 @@ static int create_impl(const cesx_config* cfg, cesx_handle* out) {
     const size_t pp = (size_t)p * p, pn = (size_t)p * n, nn = (size_t)n * n;
     const size_t mm = (size_t)potrf_ld(mx) * potrf_ld(mx);     // temporaries also hold padded Cholesky factors
 
-    // gram plans: part 0 = blocks among the first ceil(p / tile) block rows (U x U: all that
-    // chol(C) needs), part 1 = the rest.  Part 1 is sized to leave a few CUs free, because the
-    // single-workgroup Cholesky runs beside it on the side stream.
     e.ml = MomLayout{p, n};
-    {
-        const int tile = gram_tile(cfg->dtype), kt = gram_kt(cfg->dtype);
-        const int pbU = (p + tile - 1) / tile;
-        const long long ntiles = (e.J + kt - 1) / kt;
-        for (int part = 0; part < 2; ++part) {
-            GramPart& gp = e.gp[part];
-            const int min_types = 1;
-            // part 1: 7 workgroups per shader engine (8 CUs), so that the Cholesky always finds a free CU
-            // Part 1 runs beside what the side stream carries, and a kernel on another stream is only placed
-            // while it needs no more whole CUs than are free (tools/place_probe.hip: beside 248 one-per-CU
-            // workgroups a kernel of <= 8 workgroups starts at once, one of 16 waits for the whole launch).
-            //   * one device, p <= 256: the side stream runs the U-only centring (8 workgroups), the one-workgroup
-            //     chol(C) and then the noise block -> 1 CU in 32 stays free (248 workgroups on MI355X);
-            //   * sharded ensembles (RCCL's all-reduce kernels run there too) and p > 256 (blocked Cholesky: TRSM /
-            //     GEMM launches of tens of workgroups) -> 1 CU in 8 stays free (224).
-            const bool slim_side = e.J == e.Jg && potrf_ld(p) <= 256;
-            e.center_u_wgs = slim_side ? 8 : 256;       // (16 x 1024 threads do NOT get placed on the 8 free CUs: measured)
-            const int budget = part == 0 ? e.num_cus : e.num_cus - (slim_side ? e.num_cus / 32 : e.num_cus / 8);
-            gp.plan = make_gram_plan(P, tile, gram_nbw(cfg->dtype), gram_max_stage_rows(), part + 1, pbU, min_types,
-                                     budget, ntiles);
-            // fp32, second launch, two types by capacity: three lighter ones.  The planner's cost model prices the tiles, not
-            // the partial slabs a launch leaves behind -- written in a burst behind the last tile and read back by the reduce
-            // (~22 us of the step for 51 MB at C2).  Three types (32 / 48 / 20 blocks over 82 / 114 / 52 slices) leave 37 MB
-            // at 25 % more row traffic and a 4 % worse balance: 0.3944 -> 0.3924 ms/step (tools/ab_env.py, round 4); four
-            // types 0.3990, two types for the U x U launch 0.4015 against 0.3956.
-            if (part == 1 && cfg->dtype == CESX_F32 && gp.plan.ntypes == 2)
-                gp.plan = make_gram_plan(P, tile, gram_nbw(cfg->dtype), gram_max_stage_rows(), part + 1, pbU, 3, budget, ntiles);
-            if (gp.plan.max_rb * tile > gram_max_stage_rows()) { e.err = "gram plan exceeds LDS"; return fail(CESX_EINVAL); }
-        }
-    }
-    {
-        // MFMA cycles of the second Gram launch's busiest SIMD, roughly: blocks x tiles x MFMAs per block and tile x 64 / SIMDs
-        const GramPlan& pb = e.gp[1].plan;
-        const int kt = gram_kt(cfg->dtype);
-        const double cyc = (double)pb.nblocks * (double)((e.J + kt - 1) / kt) * (cfg->dtype == CESX_F32 ? 16.0 : 4.0) * 64.0 /
-                           (4.0 * std::max(1, e.num_cus));
-        e.gram_b_short = cyc < 60e-6 * 2.3e9;
-    }
+    if ((rc = plan_gram_parts(e))) return fail(rc);      // (kernels_gram.hip)
     e.colsum_slices = (int)std::min<long long>(16, (e.J + 1023) / 1024);
     if (e.colsum_slices < 1) e.colsum_slices = 1;
     e.kp = (p + 15) / 16 * 16; e.kn = (n + 15) / 16 * 16; e.ktot = 2 * e.kp + e.kn;
@@ -328,10 +283,6 @@ static int create_impl(const cesx_config* cfg, cesx_handle* out) {
         DM(t, n * e.esz); e.d_yT = t;
         DM(t, n * e.esz); e.d_gwT = t;
         DM(t, (size_t)e.kn * 4 * e.esz); e.d_rowc = t;
-        for (int part = 0; part < 2; ++part) {
-            const GramPlan& pl = e.gp[part].plan;
-            DM(t, (size_t)std::max(pl.total_slabs, 1) * pl.tile * pl.tile * e.esz); e.gp[part].d_slabs = t;
-        }
         DM(t, (size_t)e.rpad * e.ktot * e.esz); e.d_W = t;
         DM(t, (size_t)e.rpad * e.ktot * e.esz); e.d_Wf = t;
         DM(t, (size_t)e.rpad * e.esz); e.d_bias = t;
@@ -342,18 +293,8 @@ static int create_impl(const cesx_config* cfg, cesx_handle* out) {
         DM(t, (size_t)e.rpad * e.kp * e.esz); e.d_Wfwd_f = t;
         DM(t, (size_t)e.rpad * e.esz); e.d_bfwd = t;
     }
-    for (int part = 0; part < 2; ++part) {
-        GramPart& gp = e.gp[part];
-        const GramPlan& pl = gp.plan;
-        DM(gp.d_type_hdr, pl.type_hdr.size() * 4); DM(gp.d_rows, pl.rows.size() * 4);
-        DM(gp.d_wblk, pl.wblk.size() * 4); DM(gp.d_blk_rc, pl.blk_rc.size() * 4); DM(gp.d_row_own, pl.row_own.size() * 4);
-        if ((rc = upload(e, gp.d_type_hdr, pl.type_hdr.data(), pl.type_hdr.size() * 4))) return fail(rc);
-        if ((rc = upload(e, gp.d_rows, pl.rows.data(), pl.rows.size() * 4))) return fail(rc);
-        if ((rc = upload(e, gp.d_wblk, pl.wblk.data(), pl.wblk.size() * 4))) return fail(rc);
-        if ((rc = upload(e, gp.d_blk_rc, pl.blk_rc.data(), pl.blk_rc.size() * 4))) return fail(rc);
-        if ((rc = upload(e, gp.d_row_own, pl.row_own.data(), pl.row_own.size() * 4))) return fail(rc);
-        DM(gp.d_rowsum_part, (size_t)pl.total_rs * P * 8);
-    }
+    for (GramPart& gp : e.gp)
+        if ((rc = gram_part_alloc(e, gp))) return fail(rc);
     DM(e.d_metric_part, ((size_t)((e.J + 31) / 32) + 8) * 2 * 8);
     DM(e.d_metric_sums, 2 * 8);
     DM(e.d_colsum_part, (size_t)P * e.colsum_slices * 8);
@@ -421,8 +362,7 @@ void cesx_destroy(cesx_handle h) {
                     e.d_bias, e.d_Wfwd, e.d_Wfwd_f, e.d_bfwd, e.d_metric_part, e.d_metric_sums,
                     e.d_rowc,
                     e.d_colsum_part, e.d_mom,
-                    e.gp[0].d_type_hdr, e.gp[0].d_rows, e.gp[0].d_wblk, e.gp[0].d_blk_rc, e.gp[0].d_row_own, e.gp[0].d_slabs, e.gp[0].d_rowsum_part,
-                    e.gp[1].d_type_hdr, e.gp[1].d_rows, e.gp[1].d_wblk, e.gp[1].d_blk_rc, e.gp[1].d_row_own, e.gp[1].d_slabs, e.gp[1].d_rowsum_part, e.d_sums, e.d_ubar, e.d_gbar, e.d_m, e.d_dg,
+                    e.d_sums, e.d_ubar, e.d_gbar, e.d_m, e.d_dg,
                     e.d_C, e.d_L, e.d_Cug, e.d_See, e.d_Srr, e.d_K, e.d_Kp, e.d_M, e.d_P, e.d_PK,
                     e.d_t1, e.d_t2, e.d_t3, e.d_t4, e.d_spec, e.d_ns_x[0][0], e.d_ns_x[0][1], e.d_ns_x[1][0], e.d_ns_x[1][1], e.d_ns_r[0], e.d_ns_r[1], e.d_ns_r[2],
                     e.d_ns_parts, e.d_ns_skip, e.d_mv, e.d_part, e.d_scal, e.d_absmax,
@@ -433,6 +373,7 @@ void cesx_destroy(cesx_handle h) {
                     e.d_gf_theta, e.d_gf_out, e.d_gf_idx, e.d_gf_status};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
+    for (GramPart& gp : e.gp) gram_part_free(gp);
     for (int w = 0; w < 2; ++w)
         for (auto& pr : e.prof_ev[w]) { if (pr.first) (void)hipEventDestroy(pr.first); if (pr.second) (void)hipEventDestroy(pr.second); }
     for (auto ev : e.prof_pool) (void)hipEventDestroy(ev);
@@ -570,15 +511,48 @@ static int moments_check(Engine& e, const void* U, const void* G, double* mom) {
     return CESX_OK;
 }
 
-int cesx_moments_uu(cesx_handle h, const void* U, const void* G, double* mom, void* stream) {
+// The first half of a step (cesx_moments_uu*): the U x U launch and its reduce on the caller's stream, then
+//   Plain:        nothing;
+//   Handover:     the side stream is made to wait for the reduce -- the hand-over event (ev_a) bound to the reduce kernel's own
+//                 completion signal, no marker packet in front of whatever the caller's stream runs next -- and, when the
+//                 previous update's metric finalisation is still pending on this stream, that too as the reduce launch's
+//                 first workgroup;
+//   HandoverChol: the same and the factorisation behind it (nothing can sit between the reduce and the hand-over).
+// A caller already on the side stream has nothing to hand over: its own ordering applies.
+enum class UuThen { Plain, Handover, HandoverChol };
+static int moments_uu(cesx_handle h, const void* U, const void* G, double* mom, void* stream, UuThen then, int update = 0) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
     TRY(moments_check(e, U, G, mom));
+    if (update < 0 || update > 2) { e.err = "cesx_moments_uu_chol: bad argument"; return CESX_EINVAL; }
     SET_DEVICE(e);
-    FLUSH(e);
+    hipStream_t s = (hipStream_t)stream;
+    const bool hand = then != UuThen::Plain && s != e.side;
     ++e.prof_step;
-    WHITEN_UU(e, G, stream);
-    return launch_gram(e, 0, U, G, mom, (hipStream_t)stream);
+    if (!hand || e.met_stream != s) FLUSH(e);      // (a hand-over on the deferred finalisation's own stream carries it)
+    WHITEN_UU(e, G, s);
+    GramLaunch L{.part = 0, .U = U, .G = G, .mom = mom, .s = s};
+    if (hand) {
+        L.bound_stop = e.ev_a;
+        if (e.met_deferred) {
+            L.fin = metric_fin_args(e, nullptr, true);
+            L.fin.N = (double)e.Jg;
+            e.met_deferred = false;
+        }
+    }
+    TRY(launch_moments(e, L));
+    if (hand) CESX_HIP(hipStreamWaitEvent(e.side, e.ev_a, 0));
+    return then == UuThen::HandoverChol ? launch_chol_async(e, update, mom, s, hand) : CESX_OK;
+}
+
+int cesx_moments_uu(cesx_handle h, const void* U, const void* G, double* mom, void* stream) {
+    return moments_uu(h, U, G, mom, stream, UuThen::Plain);
+}
+int cesx_moments_uu_handover(cesx_handle h, const void* U, const void* G, double* mom, void* stream) {
+    return moments_uu(h, U, G, mom, stream, UuThen::Handover);
+}
+int cesx_moments_uu_chol(cesx_handle h, int update, const void* U, const void* G, double* mom, void* stream) {
+    return moments_uu(h, U, G, mom, stream, UuThen::HandoverChol, update);
 }
 
 int cesx_chol_async(cesx_handle h, int update, const double* mom, void* stream) {
@@ -591,66 +565,6 @@ int cesx_chol_async(cesx_handle h, int update, const double* mom, void* stream) 
     return launch_chol_async(e, update, mom, (hipStream_t)stream);
 }
 
-// U x U launch + its reduce with the hand-over event (ev_a) bound to the reduce kernel's own completion signal -- no
-// marker packet in front of whatever the caller's stream runs next -- and, when the previous update's metric
-// finalisation is still pending on this stream, that too as the reduce launch's first workgroup.  The side stream
-// is made to wait for ev_a.
-static int moments_uu_handover(Engine& e, const void* U, const void* G, double* mom, hipStream_t s) {
-    ++e.prof_step;
-    if (e.met_deferred && e.met_stream != s) FLUSH(e);
-    WHITEN_UU(e, G, s);
-    TRY(launch_gram(e, 0, U, G, mom, s, true));
-    if (e.met_deferred) {
-        MetricFin f = metric_fin_args(e, nullptr, true);
-        f.N = (double)e.Jg;
-        e.met_deferred = false;
-        TRY(launch_gram_reduce(e, 0, mom, s, e.ev_a, &f));
-    } else {
-        TRY(launch_gram_reduce(e, 0, mom, s, e.ev_a, nullptr));
-    }
-    CESX_HIP(hipStreamWaitEvent(e.side, e.ev_a, 0));
-    return CESX_OK;
-}
-
-int cesx_moments_uu_handover(cesx_handle h, const void* U, const void* G, double* mom, void* stream) {
-    if (!h) return CESX_EINVAL;
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    TRY(moments_check(e, U, G, mom));
-    SET_DEVICE(e);
-    hipStream_t s = (hipStream_t)stream;
-    if (s == e.side) {      // nothing to hand over: the caller's own ordering applies
-        FLUSH(e);
-        ++e.prof_step;
-        WHITEN_UU(e, G, s);
-        TRY(launch_gram(e, 0, U, G, mom, s));
-        if (s != e.side) {
-            CESX_HIP(hipEventRecord(e.ev_a, s));
-            CESX_HIP(hipStreamWaitEvent(e.side, e.ev_a, 0));
-        }
-        return CESX_OK;
-    }
-    return moments_uu_handover(e, U, G, mom, s);
-}
-
-int cesx_moments_uu_chol(cesx_handle h, int update, const void* U, const void* G, double* mom, void* stream) {
-    if (!h) return CESX_EINVAL;
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    TRY(moments_check(e, U, G, mom));
-    if (update < 0 || update > 2) { e.err = "cesx_moments_uu_chol: bad argument"; return CESX_EINVAL; }
-    SET_DEVICE(e);
-    hipStream_t s = (hipStream_t)stream;
-    if (s == e.side) {
-        FLUSH(e);
-        ++e.prof_step;
-        WHITEN_UU(e, G, s);
-        TRY(launch_gram(e, 0, U, G, mom, s));
-        return launch_chol_async(e, update, mom, s);
-    }
-    // nothing can sit between the reduce of the U x U launch and the hand-over to the side stream
-    TRY(moments_uu_handover(e, U, G, mom, s));
-    return launch_chol_async(e, update, mom, s, true);
-}
-
 int cesx_moments_rest(cesx_handle h, const void* U, const void* G, double* mom, void* stream) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
@@ -660,7 +574,7 @@ int cesx_moments_rest(cesx_handle h, const void* U, const void* G, double* mom, 
     // (the reduce kernel of this launch also copies this shard's data-metric sums of the PREVIOUS
     //  apply to the tail of the buffer: they ride on this step's all-reduce)
     WHITEN(e, G, stream, true);
-    return launch_gram(e, 1, U, G, mom, (hipStream_t)stream);
+    return launch_moments(e, GramLaunch{.part = 1, .U = U, .G = G, .mom = mom, .s = (hipStream_t)stream});
 }
 
 int cesx_moments_rest_lineal(cesx_handle h, double* mom, void* stream) {

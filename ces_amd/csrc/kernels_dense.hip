@@ -15,7 +15,6 @@
 namespace cesx {
 
 constexpr int NPB = 256;         // partial-sum blocks (engine.hip sizes d_part for 256)
-int potrf_ld(int n);
 constexpr int DT = 256;
 
 __device__ __forceinline__ double dblock_sum(double v, double* red) {
@@ -336,7 +335,6 @@ void matvec_kernel(int rows, int cols, const double* __restrict__ A, const doubl
 // Two barriers per panel.  A : n x n (lower part read); Lp : np x np, leading
 // dimension np, entries above the diagonal are left undefined.
 // ---------------------------------------------------------------------------
-constexpr int PNB = 32;    // leading dimensions of Cholesky factors are rounded up to this
 constexpr int PRT = 512;
 constexpr int QNB = 8;
 using d4_t = double __attribute__((ext_vector_type(4)));
@@ -1605,7 +1603,6 @@ __global__ void pad_copy_kernel(int n, int np, const double* __restrict__ A, dou
 
 // Cholesky factor of the n x n SPD matrix A into Lp (leading dimension
 // potrf_ld(n) = n rounded up to 32; entries above the diagonal are undefined).
-int potrf_ld(int n) { return (n + PNB - 1) / PNB * PNB; }
 
 static int potrf_reg_any(Engine& e, hipStream_t s, int n, int np, const PotrfLaunch& f) {
     const int T = np / 16, ntile = T * (T + 1) / 2, slots = (ntile + 7) / 8;

@@ -390,6 +390,27 @@ static double gram_tile_cost(int tile, int blocks, int row_blocks) {
     return 1.055 * mfma_cyc * (double)((blocks + 3) / 4) + 450.0 + 3.0 * (double)(row_blocks * tile) + addr;
 }
 
+using Block = std::pair<int, int>;               // (R, C) of a tile x tile output block, C <= R
+using Types = std::vector<std::vector<Block>>;   // the blocks of every workgroup type
+
+// the blocks of the lower triangle a plan covers: id[R * nbr + C] = position of block (R, C) in their row-major list, or -1
+using BlockIds = std::vector<int>;
+
+// the block rows a type with the blocks b[0 .. nb) stages, ascending
+static std::vector<int> staged_rows(const Block* b, int nb) {
+    std::vector<int> rows;
+    for (int q = 0; q < nb; ++q) { rows.push_back(b[q].first); rows.push_back(b[q].second); }
+    std::sort(rows.begin(), rows.end());
+    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+    return rows;
+}
+// ... how many they are, and the cycles one J tile costs a workgroup of that type
+static double type_cost(int tile, const Block* b, int nb, int* nrows = nullptr) {
+    const int rows = (int)staged_rows(b, nb).size();
+    if (nrows) *nrows = rows;
+    return gram_tile_cost(tile, nb, rows);
+}
+
 // Slices per type that level the launch: whole tiles per slice, the busiest workgroup (tiles x cost per tile) as
 // light as the workgroup budget allows.  Returns that workgroup's cycles.
 static double gram_level_slices(const std::vector<double>& w, int budget, long long ntiles, std::vector<int>& nsl) {
@@ -423,252 +444,220 @@ static double gram_level_slices(const std::vector<double>& w, int budget, long l
     return worst;
 }
 
-GramPlan make_gram_plan(int P, int tile, int nbw, int max_rows_lds, int subset, int pbU, int min_types,
-                        int wg_budget, long long ntiles) {
-    GramPlan pl;
-    pl.tile = tile;
-    pl.nbw = nbw;
-    pl.nbr = (P + tile - 1) / tile;
-    const int cap = GRAM_WAVES * nbw;
-    auto wanted = [&](int R, int C) {
-        const bool uu = R < pbU && C < pbU;
-        return subset == 0 || (subset == 1 ? uu : !uu);
-    };
-    pl.own_lo = subset == 2 ? std::min(pbU, pl.nbr) : 0;
-    pl.own_hi = subset == 1 ? std::min(pbU, pl.nbr) : pl.nbr;
-    std::vector<std::vector<std::pair<int, int>>> types;   // blocks (R, C) per type
-    if (pl.nbr * tile <= max_rows_lds) {
-        // all rows fit in LDS: chop the lower triangle, listed row by row OR column by column, into runs.  Which
-        // listing is the better one depends on the subset: the second launch's blocks (G x U, then G x G) cut by
-        // COLUMNS give types that stage 14 + 10 block rows at C2 (U columns 0-5 | U columns 6-7 and G x G), cut by
-        // rows 13 + 16 -- fewer rows to fetch, to shift and to sum, and no type needs all 16 (the LDS-DMA kernel
-        // then keeps its fragment addresses in registers, kernels_gram2.hip IMM).
-        std::vector<std::pair<int, int>> all_rm, all_cm;
-        for (int R = 0; R < pl.nbr; ++R)
-            for (int C = 0; C <= R; ++C)
-                if (wanted(R, C)) all_rm.push_back({R, C});
-        for (int C = 0; C < pl.nbr; ++C)
-            for (int R = C; R < pl.nbr; ++R)
-                if (wanted(R, C)) all_cm.push_back({R, C});
-        const int nb_all = (int)all_rm.size();
-        const int nt = std::max(std::max(1, min_types), (nb_all + cap - 1) / cap);
-        // equal runs, rounded to multiples of 4 blocks: the 4 SIMDs of a workgroup then carry the same
-        // number of blocks (the barrier of every J tile waits for the busiest SIMD); the last type
-        // takes what is left
-        int per = std::max(1, (nb_all + nt - 1) / nt);
-        if (per > 4) per = std::min(cap / 4 * 4, (per + 3) / 4 * 4);
-        std::vector<int> sizes0;
-        for (int lo = 0; lo < nb_all; lo += per) sizes0.push_back(std::min(nb_all - lo, per));
-        // ... unless another split of the same number of runs packs the launch better: tiles per slice are whole
-        // numbers (at C2 two row-major runs of 52 + 48 blocks over 248 workgroups end at 16 and 18 tiles per slice,
-        // the second 7 % above the mean; 44 + 56 end at 19 and 15, level).  Two- and three-run plans are searched in
-        // steps of 4 blocks with the cost model below, over both listings.
-        // a candidate = (listing, run sizes): its levelled launch time (busiest workgroup) and the block rows all its
-        // workgroups stage per tile (what the launch fetches, shifts and sums); the lightest within 1 % of the fastest wins
-        struct Cand { const std::vector<std::pair<int, int>>* all; std::vector<int> sz; double cost, rows; };
-        auto eval = [&](const std::vector<std::pair<int, int>>& all, const std::vector<int>& sz) {
-            std::vector<double> w;
-            std::vector<int> nrw;
-            int lo = 0;
-            for (int n_ : sz) {
-                std::set<int> rws;
-                for (int q = lo; q < lo + n_; ++q) { rws.insert(all[q].first); rws.insert(all[q].second); }
-                w.push_back(gram_tile_cost(tile, n_, (int)rws.size()));
-                nrw.push_back((int)rws.size());
-                lo += n_;
-            }
-            std::vector<int> ns;
-            Cand c{&all, sz, 0.0, 0.0};
-            c.cost = gram_level_slices(w, std::max(wg_budget, (int)sz.size()), ntiles, ns);
-            for (size_t t = 0; t < sz.size(); ++t) c.rows += (double)nrw[t] * ns[t];
-            return c;
-        };
-        // (fp64: equal runs.  The cost model was fitted to the tiles, not to what a workgroup does once per launch: for C2 in
-        //  fp64 the search cut the U x U launch's 136 blocks into 8 + 128 -- 228 workgroups of 18 tiles with 256 KB of slabs
-        //  each -- where 68 + 68 runs the two Gram launches in 0.362 instead of 0.408 ms, round 4)
-        const bool search = sizes0.size() >= 2 && sizes0.size() <= 3 && tile == 32;
-        std::vector<Cand> cands;
-        cands.push_back(eval(all_rm, sizes0));
-        for (const auto* all : {&all_rm, &all_cm}) {
-            if (all == &all_cm && sizes0.size() < 2) break;
-            if (all == &all_cm) cands.push_back(eval(*all, sizes0));
-            if (!search) continue;
-            std::vector<int> cand(sizes0.size());
-            for (int a = 4; a <= std::min(cap, nb_all - 4); a += 4) {
-                if (sizes0.size() == 2) {
-                    cand = {a, nb_all - a};
-                    if (cand[1] > cap) continue;
-                    cands.push_back(eval(*all, cand));
-                } else {
-                    for (int b = 4; b <= std::min(cap, nb_all - a - 4); b += 4) {
-                        cand = {a, b, nb_all - a - b};
-                        if (cand[2] > cap) continue;
-                        cands.push_back(eval(*all, cand));
-                    }
-                }
-            }
-        }
-        size_t pick = 0;
-        {
-            double best = cands[0].cost;
-            for (const Cand& c : cands) best = std::min(best, c.cost);
-            // (the equal-runs row-major plan stays unless something is clearly better: 0.5 % as before, and then the
-            //  lightest of the candidates within 1 % of the fastest)
-            if (best < cands[0].cost * 0.995) {
-                double rows = 1e300;
-                for (size_t i = 0; i < cands.size(); ++i)
-                    if (cands[i].cost <= best * 1.01 && cands[i].rows < rows) { rows = cands[i].rows; pick = i; }
-            }
-        }
-        const std::vector<std::pair<int, int>>* best_all = cands[pick].all;
-        const std::vector<int> sizes = cands[pick].sz;
-        size_t lo = 0;
-        for (int n_ : sizes) {
-            std::vector<std::pair<int, int>> v(best_all->begin() + lo, best_all->begin() + lo + n_);
-            types.push_back(v);
+// All rows fit in LDS: chop the lower triangle, listed row by row OR column by column, into runs.  Which
+// listing is the better one depends on the subset: the second launch's blocks (G x U, then G x G) cut by
+// COLUMNS give types that stage 14 + 10 block rows at C2 (U columns 0-5 | U columns 6-7 and G x G), cut by
+// rows 13 + 16 -- fewer rows to fetch, to shift and to sum, and no type needs all 16 (the LDS-DMA kernel
+// then keeps its fragment addresses in registers, kernels_gram2.hip IMM).
+static Types search_runs(int tile, int nbr, const BlockIds& id, int cap, int min_types, int wg_budget, long long ntiles) {
+    std::vector<Block> all_rm;
+    for (int R = 0; R < nbr; ++R)
+        for (int C = 0; C <= R; ++C)
+            if (id[(size_t)R * nbr + C] >= 0) all_rm.push_back({R, C});
+    std::vector<Block> all_cm = all_rm;      // (column by column: rows ascending within a column)
+    std::stable_sort(all_cm.begin(), all_cm.end(), [](const Block& a, const Block& b) { return a.second < b.second; });
+    const int nb_all = (int)all_rm.size();
+    const int nt = std::max(std::max(1, min_types), (nb_all + cap - 1) / cap);
+    // equal runs, rounded to multiples of 4 blocks: the 4 SIMDs of a workgroup then carry the same
+    // number of blocks (the barrier of every J tile waits for the busiest SIMD); the last type
+    // takes what is left
+    int per = std::max(1, (nb_all + nt - 1) / nt);
+    if (per > 4) per = std::min(cap / 4 * 4, (per + 3) / 4 * 4);
+    std::vector<int> sizes0;
+    for (int lo = 0; lo < nb_all; lo += per) sizes0.push_back(std::min(nb_all - lo, per));
+    // ... unless another split of the same number of runs packs the launch better: tiles per slice are whole
+    // numbers (at C2 two row-major runs of 52 + 48 blocks over 248 workgroups end at 16 and 18 tiles per slice,
+    // the second 7 % above the mean; 44 + 56 end at 19 and 15, level).  Two- and three-run plans are searched in
+    // steps of 4 blocks with the cost model above, over both listings.
+    // a candidate = (listing, run sizes): its levelled launch time (busiest workgroup) and the block rows all its
+    // workgroups stage per tile (what the launch fetches, shifts and sums); the lightest within 1 % of the fastest wins
+    struct Cand { const std::vector<Block>* all; std::vector<int> sz; double cost, rows; };
+    auto eval = [&](const std::vector<Block>& all, const std::vector<int>& sz) {
+        std::vector<double> w;
+        std::vector<int> nrw;
+        int lo = 0;
+        for (int n_ : sz) {
+            nrw.push_back(0);
+            w.push_back(type_cost(tile, all.data() + lo, n_, &nrw.back()));
             lo += n_;
         }
-    } else {
-        // rectangles a x b of blocks with (a + b) * tile rows staged.  Which a x b: every shape that fits the wave
-        // capacity and LDS is laid over the triangle and priced with the cost model (levelled busiest workgroup, then the
-        // rows the launch stages).  Round 4: the near-square 11 x 11 that sqrt(capacity) gives leaves C5's second launch
-        // (64 block rows) with 18 types, three of them 11-block leftovers -- busiest SIMD 12 % above the mean and 343 staged
-        // block rows; 16 x 8 divides the 64 rows evenly: 14 types, 3 % above the mean, 288 block rows.
-        auto build = [&](int a, int b) {
-            std::vector<std::vector<std::pair<int, int>>> ts;
-            for (int R0 = 0; R0 < pl.nbr; R0 += a)
-                for (int C0 = 0; C0 <= R0 + a - 1 && C0 < pl.nbr; C0 += b) {
-                    std::vector<std::pair<int, int>> v;
-                    for (int R = R0; R < std::min(R0 + a, pl.nbr); ++R)
-                        for (int C = C0; C < std::min(C0 + b, pl.nbr); ++C)
-                            if (C <= R && wanted(R, C)) v.push_back({R, C});
-                    if (!v.empty()) ts.push_back(v);
+        std::vector<int> ns;
+        Cand c{&all, sz, 0.0, 0.0};
+        c.cost = gram_level_slices(w, std::max(wg_budget, (int)sz.size()), ntiles, ns);
+        for (size_t t = 0; t < sz.size(); ++t) c.rows += (double)nrw[t] * ns[t];
+        return c;
+    };
+    // (fp64: equal runs.  The cost model was fitted to the tiles, not to what a workgroup does once per launch: for C2 in
+    //  fp64 the search cut the U x U launch's 136 blocks into 8 + 128 -- 228 workgroups of 18 tiles with 256 KB of slabs
+    //  each -- where 68 + 68 runs the two Gram launches in 0.362 instead of 0.408 ms, round 4)
+    const bool search = sizes0.size() >= 2 && sizes0.size() <= 3 && tile == 32;
+    std::vector<Cand> cands;
+    cands.push_back(eval(all_rm, sizes0));
+    for (const auto* all : {&all_rm, &all_cm}) {
+        if (all == &all_cm && sizes0.size() < 2) break;
+        if (all == &all_cm) cands.push_back(eval(*all, sizes0));
+        if (!search) continue;
+        std::vector<int> cand(sizes0.size());
+        for (int a = 4; a <= std::min(cap, nb_all - 4); a += 4) {
+            if (sizes0.size() == 2) {
+                cand = {a, nb_all - a};
+                if (cand[1] > cap) continue;
+                cands.push_back(eval(*all, cand));
+            } else {
+                for (int b = 4; b <= std::min(cap, nb_all - a - 4); b += 4) {
+                    cand = {a, b, nb_all - a - b};
+                    if (cand[2] > cap) continue;
+                    cands.push_back(eval(*all, cand));
                 }
-            return ts;
-        };
-        int a0 = std::max(1, (int)std::floor(std::sqrt((double)cap)));
-        int b0 = std::max(1, cap / a0);
-        while ((a0 + b0) * tile > max_rows_lds && (a0 > 1 || b0 > 1)) {
-            if (a0 >= b0) --a0; else --b0;
-        }
-        int best_a = a0, best_b = b0;
-        {
-            double best_cost = 1e300, best_rows = 1e300;
-            for (int a = 1; a <= std::min(cap, pl.nbr); ++a) {
-                const int b = std::min(cap / a, pl.nbr);
-                if (b < 1 || (a + b) * tile > max_rows_lds) continue;
-                if (a * b * 2 < cap) continue;                      // (half-empty workgroups: not worth pricing)
-                const auto ts = build(a, b);
-                std::vector<double> w;
-                double rows = 0.0;
-                for (const auto& v : ts) {
-                    std::set<int> rws;
-                    for (auto& rc : v) { rws.insert(rc.first); rws.insert(rc.second); }
-                    w.push_back(gram_tile_cost(tile, (int)v.size(), (int)rws.size()));
-                    rows += (double)rws.size();
-                }
-                if ((int)ts.size() > wg_budget) continue;
-                std::vector<int> ns;
-                const double cost = gram_level_slices(w, std::max(wg_budget, (int)ts.size()), ntiles, ns);
-                // (the near-square default stays unless something is clearly better; then the lightest within 1 % of the fastest)
-                const bool better = cost < best_cost * 0.99 || (cost <= best_cost * 1.01 && rows < best_rows);
-                if (better) { best_cost = std::min(best_cost, cost); best_rows = rows; best_a = a; best_b = b; }
             }
         }
-        types = build(best_a, best_b);
     }
-    pl.ntypes = (int)types.size();
-    pl.max_rb = 0;
-    // Slices per type, proportional to the cycles one J tile costs a workgroup of that type: the
-    // MFMAs of its busiest SIMD (blocks / 4 SIMDs, 64 cycles per MFMA, tile-width / k MFMAs per
-    // block) plus the part that does not shrink with the block count -- staging the type's rows
-    // (16 B per lane-store, ~80 B/clk/CU) and the barrier.  Largest-remainder rounding within the
-    // workgroup budget; never more slices than J tiles.
-    std::vector<int> nsl(pl.ntypes, 1);
-    std::vector<double> w(pl.ntypes);
+    // (the equal-runs row-major plan stays unless something is clearly better: 0.5 % as before, and then the
+    //  lightest of the candidates within 1 % of the fastest)
+    size_t pick = 0;
+    double best = cands[0].cost;
+    for (const Cand& c : cands) best = std::min(best, c.cost);
+    if (best < cands[0].cost * 0.995) {
+        double rows = 1e300;
+        for (size_t i = 0; i < cands.size(); ++i)
+            if (cands[i].cost <= best * 1.01 && cands[i].rows < rows) { rows = cands[i].rows; pick = i; }
+    }
+    Types types;
+    auto lo = cands[pick].all->begin();
+    for (int n_ : cands[pick].sz) {
+        types.emplace_back(lo, lo + n_);
+        lo += n_;
+    }
+    return types;
+}
+
+// The rows do not fit: rectangles a x b of blocks with (a + b) * tile rows staged.  Which a x b: every shape that fits the
+// wave capacity and LDS is laid over the triangle and priced with the cost model (levelled busiest workgroup, then the
+// rows the launch stages).  Round 4: the near-square 11 x 11 that sqrt(capacity) gives leaves C5's second launch
+// (64 block rows) with 18 types, three of them 11-block leftovers -- busiest SIMD 12 % above the mean and 343 staged
+// block rows; 16 x 8 divides the 64 rows evenly: 14 types, 3 % above the mean, 288 block rows.
+static Types search_rectangles(int tile, int nbr, const BlockIds& id, int cap, int max_rows_lds, int wg_budget, long long ntiles) {
+    auto build = [&](int a, int b) {
+        Types ts;
+        for (int R0 = 0; R0 < nbr; R0 += a)
+            for (int C0 = 0; C0 <= R0 + a - 1 && C0 < nbr; C0 += b) {
+                std::vector<Block> v;
+                for (int R = R0; R < std::min(R0 + a, nbr); ++R)
+                    for (int C = C0; C < std::min(C0 + b, nbr); ++C)
+                        if (C <= R && id[(size_t)R * nbr + C] >= 0) v.push_back({R, C});
+                if (!v.empty()) ts.push_back(v);
+            }
+        return ts;
+    };
+    int a0 = std::max(1, (int)std::floor(std::sqrt((double)cap)));
+    int b0 = std::max(1, cap / a0);
+    while ((a0 + b0) * tile > max_rows_lds && (a0 > 1 || b0 > 1)) {
+        if (a0 >= b0) --a0; else --b0;
+    }
+    int best_a = a0, best_b = b0;
+    double best_cost = 1e300, best_rows = 1e300;
+    for (int a = 1; a <= std::min(cap, nbr); ++a) {
+        const int b = std::min(cap / a, nbr);
+        if (b < 1 || (a + b) * tile > max_rows_lds) continue;
+        if (a * b * 2 < cap) continue;                      // (half-empty workgroups: not worth pricing)
+        const Types ts = build(a, b);
+        if ((int)ts.size() > wg_budget) continue;
+        std::vector<double> w;
+        double rows = 0.0;
+        for (const auto& v : ts) {
+            int nrows;
+            w.push_back(type_cost(tile, v.data(), (int)v.size(), &nrows));
+            rows += (double)nrows;
+        }
+        std::vector<int> ns;
+        const double cost = gram_level_slices(w, std::max(wg_budget, (int)ts.size()), ntiles, ns);
+        // (the near-square default stays unless something is clearly better; then the lightest within 1 % of the fastest --
+        //  judged shape by shape against the best so far, not as search_runs does over all candidates at once: the two
+        //  rules pick differently, and the plans are kept)
+        const bool better = cost < best_cost * 0.99 || (cost <= best_cost * 1.01 && rows < best_rows);
+        if (better) { best_cost = std::min(best_cost, cost); best_rows = rows; best_a = a; best_b = b; }
+    }
+    return build(best_a, best_b);
+}
+
+// Slices (workgroups) per type.  level: whole tiles per slice, levelled (gram_level_slices) -- few types with many slices
+// each, and (round 4) the rectangles of a triangle that does not fit LDS: the proportional rule below rounds 17.5 slices
+// down to 16 for eight types at once.
+// Otherwise proportional to the cycles one J tile costs a workgroup of that type: the MFMAs of its busiest SIMD
+// (blocks / 4 SIMDs, 64 cycles per MFMA, tile-width / k MFMAs per block) plus the part that does not shrink with the
+// block count -- staging the type's rows (16 B per lane-store, ~80 B/clk/CU) and the barrier.  Largest-remainder rounding
+// within the workgroup budget; never more slices than J tiles.
+static std::vector<int> slice_types(int tile, const Types& types, bool level, int wg_budget, long long ntiles) {
+    const int ntypes = (int)types.size();
+    const int budget = std::max(wg_budget, ntypes);
+    std::vector<int> nsl(ntypes, 1);
+    std::vector<double> w(ntypes);
     double total = 0.0;
-    for (int t = 0; t < pl.ntypes; ++t) {
-        std::set<int> rws;
-        for (auto& rc : types[t]) { rws.insert(rc.first); rws.insert(rc.second); }
-        w[t] = gram_tile_cost(tile, (int)types[t].size(), (int)rws.size());
-        total += w[t];
+    for (int t = 0; t < ntypes; ++t) total += w[t] = type_cost(tile, types[t].data(), (int)types[t].size());
+    if (level) {
+        gram_level_slices(w, budget, ntiles, nsl);
+        return nsl;
     }
-    // (many types -- the rectangles of a triangle that does not fit LDS: levelled as well since round 4, the proportional
-    //  rule below rounds 17.5 slices down to 16 for eight types at once; round 4)
-    if (pl.ntypes <= 4 || pl.nbr * tile > max_rows_lds) {
-        // few types, many slices each: whole tiles per slice, levelled (gram_level_slices)
-        gram_level_slices(w, std::max(wg_budget, pl.ntypes), ntiles, nsl);
-    } else {
-        const int budget = std::max(wg_budget, pl.ntypes);
-        // Types of (nearly) the same cost get the SAME number of slices, a multiple of 8 when there
-        // are that many: slice k of every such type then covers the same J range on the same XCD
-        // (workgroup id mod 8), and the rows the types share are fetched from HBM once (at C2 the two
-        // types of the second launch read 131 MB instead of 238 MB).
-        // ... unless there are many types with few slices each: rounding 17.5 down to 16 then costs more (the
-        // busiest workgroup sets the launch time) than the shared fetches save
-        const int align_from = pl.ntypes > 4 ? 64 : 16;
-        std::vector<double> want(pl.ntypes);
-        for (int t = 0; t < pl.ntypes; ++t) want[t] = total > 0 ? (double)budget * w[t] / total : 1.0;
-        std::vector<int> order(pl.ntypes);
-        for (int t = 0; t < pl.ntypes; ++t) order[t] = t;
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return want[a] > want[b]; });
-        int used = 0;
-        std::vector<std::pair<size_t, size_t>> groups;     // [first, last) in `order`
-        for (size_t i = 0; i < order.size();) {
-            size_t j = i;
-            double sum = 0.0;
-            while (j < order.size() && want[order[j]] >= 0.96 * want[order[i]]) sum += want[order[j++]];
-            int each = std::max(1, (int)std::floor(sum / (double)(j - i)));
-            if (each >= align_from) each -= each % 8;
-            for (size_t q = i; q < j; ++q) { nsl[order[q]] = each; used += each; }
-            groups.push_back({i, j});
-            i = j;
-        }
-        // workgroups left over by the rounding go to whole groups (members stay equal), the one
-        // whose members carry the most work per slice first
-        for (bool any = true; any;) {
-            any = false;
-            size_t best = groups.size();
-            double load = 0.0;
-            for (size_t g = 0; g < groups.size(); ++g) {
-                const int t0 = order[groups[g].first];
-                const int inc = nsl[t0] >= align_from ? 8 : 1;
-                if ((int)(groups[g].second - groups[g].first) * inc > budget - used) continue;
-                const double l = want[t0] / (double)nsl[t0];
-                if (l > load) { load = l; best = g; }
-            }
-            if (best < groups.size()) {
-                const int inc = nsl[order[groups[best].first]] >= align_from ? 8 : 1;
-                for (size_t q = groups[best].first; q < groups[best].second; ++q) { nsl[order[q]] += inc; used += inc; }
-                any = true;
-            }
-        }
-        for (int t = 0; t < pl.ntypes; ++t)
-            if ((long long)nsl[t] > ntiles) nsl[t] = (int)std::max<long long>(1, ntiles);
+    // Types of (nearly) the same cost get the SAME number of slices, a multiple of 8 when there
+    // are that many: slice k of every such type then covers the same J range on the same XCD
+    // (workgroup id mod 8), and the rows the types share are fetched from HBM once (at C2 the two
+    // types of the second launch read 131 MB instead of 238 MB).
+    // ... unless there are many types with few slices each (and here there are more than 4): rounding 17.5 down to 16
+    // then costs more (the busiest workgroup sets the launch time) than the shared fetches save
+    const int align_from = 64;
+    std::vector<double> want(ntypes);
+    for (int t = 0; t < ntypes; ++t) want[t] = total > 0 ? (double)budget * w[t] / total : 1.0;
+    std::vector<int> order(ntypes);
+    for (int t = 0; t < ntypes; ++t) order[t] = t;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return want[a] > want[b]; });
+    int used = 0;
+    std::vector<std::pair<size_t, size_t>> groups;     // [first, last) in `order`
+    for (size_t i = 0; i < order.size();) {
+        size_t j = i;
+        double sum = 0.0;
+        while (j < order.size() && want[order[j]] >= 0.96 * want[order[i]]) sum += want[order[j++]];
+        int each = std::max(1, (int)std::floor(sum / (double)(j - i)));
+        if (each >= align_from) each -= each % 8;
+        for (size_t q = i; q < j; ++q) { nsl[order[q]] = each; used += each; }
+        groups.push_back({i, j});
+        i = j;
     }
-    // output block ids: position in the row-major list of this plan's blocks
-    std::vector<int> idmap((size_t)pl.nbr * pl.nbr, -1);
-    pl.nblocks = 0;
-    pl.blk_rc.clear();
-    for (int R = 0; R < pl.nbr; ++R)
-        for (int C = 0; C <= R; ++C)
-            if (wanted(R, C)) {
-                idmap[(size_t)R * pl.nbr + C] = pl.nblocks++;
-                for (int q : {R, C, 0, 0, 0}) pl.blk_rc.push_back(q);
-            }
-    auto out_id = [&](int R, int C) { return idmap[(size_t)R * pl.nbr + C]; };
+    // workgroups left over by the rounding go to whole groups (members stay equal), the one
+    // whose members carry the most work per slice first
+    for (bool any = true; any;) {
+        any = false;
+        size_t best = groups.size();
+        double load = 0.0;
+        for (size_t g = 0; g < groups.size(); ++g) {
+            const int t0 = order[groups[g].first];
+            const int inc = nsl[t0] >= align_from ? 8 : 1;
+            if ((int)(groups[g].second - groups[g].first) * inc > budget - used) continue;
+            const double l = want[t0] / (double)nsl[t0];
+            if (l > load) { load = l; best = g; }
+        }
+        if (best < groups.size()) {
+            const int inc = nsl[order[groups[best].first]] >= align_from ? 8 : 1;
+            for (size_t q = groups[best].first; q < groups[best].second; ++q) { nsl[order[q]] += inc; used += inc; }
+            any = true;
+        }
+    }
+    for (int t = 0; t < ntypes; ++t)
+        if ((long long)nsl[t] > ntiles) nsl[t] = (int)std::max<long long>(1, ntiles);
+    return nsl;
+}
+
+// The device tables of a plan (GramPlan, cesx_internal.h; blk_rc holds (R, C) already) from its types and their slices.
+static void flatten_plan(GramPlan& pl, const Types& types, const std::vector<int>& nsl, const BlockIds& id) {
     pl.row_own.assign((size_t)pl.nbr * 2, 0);
+    pl.max_rb = 0;
     std::set<int> owned;
     int wg0 = 0, slab0 = 0, rs0 = 0;
     for (int t = 0; t < pl.ntypes; ++t) {
         const auto& v = types[t];
-        std::vector<int> rows;
-        for (auto& rc : v) { rows.push_back(rc.first); rows.push_back(rc.second); }
-        std::sort(rows.begin(), rows.end());
-        rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+        const int nv = (int)v.size();
+        const std::vector<int> rows = staged_rows(v.data(), nv);
         auto compact = [&](int r) { return (int)(std::lower_bound(rows.begin(), rows.end(), r) - rows.begin()); };
         pl.max_rb = std::max(pl.max_rb, (int)rows.size());
-        const int nv = (int)v.size();
         for (int q : {(int)rows.size(), (int)pl.rows.size(), (int)(pl.wblk.size() / 3), nv, wg0, nsl[t], slab0, rs0})
             pl.type_hdr.push_back(q);
         for (int r : rows) {
@@ -684,12 +673,12 @@ GramPlan make_gram_plan(int P, int tile, int nbw, int max_rows_lds, int subset, 
             const int cnt = nv / GRAM_WAVES + (w < nv % GRAM_WAVES ? 1 : 0);
             const int lo = next, hi = next + cnt;
             next = hi;
-            for (int b = 0; b < nbw; ++b) {
+            for (int b = 0; b < pl.nbw; ++b) {
                 if (lo + b < hi) {
                     pl.wblk.push_back(compact(v[lo + b].first));
                     pl.wblk.push_back(compact(v[lo + b].second));
                     pl.wblk.push_back(lo + b);                      // block index inside the type
-                    int* info = &pl.blk_rc[(size_t)out_id(v[lo + b].first, v[lo + b].second) * 5];
+                    int* info = &pl.blk_rc[(size_t)id[(size_t)v[lo + b].first * pl.nbr + v[lo + b].second] * 5];
                     info[2] = slab0 + lo + b; info[3] = nv; info[4] = nsl[t];
                 } else {
                     pl.wblk.push_back(-1); pl.wblk.push_back(-1); pl.wblk.push_back(-1);
@@ -701,66 +690,154 @@ GramPlan make_gram_plan(int P, int tile, int nbw, int max_rows_lds, int subset, 
         rs0 += nsl[t];
     }
     pl.total_wgs = wg0; pl.total_slabs = slab0; pl.total_rs = std::max(rs0, 1);
+}
+
+GramPlan make_gram_plan(int P, int tile, int nbw, int max_rows_lds, int subset, int pbU, int min_types,
+                        int wg_budget, long long ntiles) {
+    GramPlan pl;
+    pl.tile = tile;
+    pl.nbw = nbw;
+    pl.nbr = (P + tile - 1) / tile;
+    pl.own_lo = subset == 2 ? std::min(pbU, pl.nbr) : 0;
+    pl.own_hi = subset == 1 ? std::min(pbU, pl.nbr) : pl.nbr;
+    BlockIds id((size_t)pl.nbr * pl.nbr, -1);
+    pl.nblocks = 0;
+    for (int R = 0; R < pl.nbr; ++R)
+        for (int C = 0; C <= R; ++C) {
+            const bool uu = R < pbU && C < pbU;
+            if (subset != 0 && (subset == 1) != uu) continue;
+            id[(size_t)R * pl.nbr + C] = pl.nblocks++;
+            for (int q : {R, C, 0, 0, 0}) pl.blk_rc.push_back(q);
+        }
+    const int cap = GRAM_WAVES * nbw;                           // blocks the accumulators of one workgroup hold
+    const bool fits = pl.nbr * tile <= max_rows_lds;            // every type may stage all rows
+    const Types types = fits ? search_runs(tile, pl.nbr, id, cap, min_types, wg_budget, ntiles)
+                             : search_rectangles(tile, pl.nbr, id, cap, max_rows_lds, wg_budget, ntiles);
+    pl.ntypes = (int)types.size();
+    flatten_plan(pl, types, slice_types(tile, types, pl.ntypes <= 4 || !fits, wg_budget, ntiles), id);
     return pl;
 }
 
-template <typename T>
-static int launch_gram_t(Engine& e, int part, const void* U, const void* G, hipStream_t s) {
-    GramPart& gp = e.gp[part];
-    const GramPlan& pl = gp.plan;
-    if (pl.nblocks == 0) return CESX_OK;    // (a tiny problem can have all its blocks in part 0; the reduce still
-                                            //  writes part 1's share of the buffer: row sums it owns and the lagged tail)
-    int rc2 = e.gram_v2 ? launch_gram2(e, part, U, G, s) : -1;      // LDS-DMA kernel when the shapes allow
-    if (rc2 >= 0) return rc2;
-    const int lds = 2 * pl.max_rb * pl.tile * ROW_STRIDE + pl.max_rb * pl.tile * 16;
-    const bool aligned = (e.J % Mfma<T>::VEC == 0) && ((uintptr_t)U % 16 == 0) && ((uintptr_t)G % 16 == 0);
-    dim3 grid(pl.total_wgs), block(GRAM_THREADS);
-    auto kern = aligned ? gram_kernel<T, true> : gram_kernel<T, false>;
-    CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    {
-        e.prof_part = part;
-        ProfScope prof(e, 0, s);
-        hipLaunchKernelGGL(kern, grid, block, lds, s, (const T*)U, (const T*)G, (const T*)e.d_shiftT,
-                           e.p, e.n, (long long)e.J, gp.d_type_hdr, pl.ntypes, gp.d_rows, gp.d_wblk,
-                           (T*)gp.d_slabs, gp.d_rowsum_part);
+// The plans of an engine: part 0 = blocks among the first ceil(p / tile) block rows (U x U: all that chol(C) needs),
+// part 1 = the rest.  Part 1 is sized to leave a few CUs free, because the single-workgroup Cholesky runs beside it on
+// the side stream.
+int plan_gram_parts(Engine& e) {
+    const int dtype = e.cfg.dtype, tile = gram_tile(dtype), kt = gram_kt(dtype);
+    const int pbU = (e.p + tile - 1) / tile;
+    const long long ntiles = (e.J + kt - 1) / kt;
+    // part 1: 7 workgroups per shader engine (8 CUs), so that the Cholesky always finds a free CU
+    // Part 1 runs beside what the side stream carries, and a kernel on another stream is only placed
+    // while it needs no more whole CUs than are free (tools/place_probe.hip: beside 248 one-per-CU
+    // workgroups a kernel of <= 8 workgroups starts at once, one of 16 waits for the whole launch).
+    //   * one device, p <= 256: the side stream runs the U-only centring (8 workgroups), the one-workgroup
+    //     chol(C) and then the noise block -> 1 CU in 32 stays free (248 workgroups on MI355X);
+    //   * sharded ensembles (RCCL's all-reduce kernels run there too) and p > 256 (blocked Cholesky: TRSM /
+    //     GEMM launches of tens of workgroups) -> 1 CU in 8 stays free (224).
+    const bool slim_side = e.J == e.Jg && potrf_ld(e.p) <= 256;
+    e.center_u_wgs = slim_side ? 8 : 256;       // (16 x 1024 threads do NOT get placed on the 8 free CUs: measured)
+    for (int part = 0; part < 2; ++part) {
+        GramPlan& pl = e.gp[part].plan;
+        const int budget = part == 0 ? e.num_cus : e.num_cus - (slim_side ? e.num_cus / 32 : e.num_cus / 8);
+        auto plan = [&](int min_types) {
+            return make_gram_plan(e.P, tile, gram_nbw(dtype), gram_max_stage_rows(), part + 1, pbU, min_types, budget, ntiles);
+        };
+        pl = plan(1);
+        // fp32, second launch, two types by capacity: three lighter ones.  The planner's cost model prices the tiles, not
+        // the partial slabs a launch leaves behind -- written in a burst behind the last tile and read back by the reduce
+        // (~22 us of the step for 51 MB at C2).  Three types (32 / 48 / 20 blocks over 82 / 114 / 52 slices) leave 37 MB
+        // at 25 % more row traffic and a 4 % worse balance: 0.3944 -> 0.3924 ms/step (tools/ab_env.py, round 4); four
+        // types 0.3990, two types for the U x U launch 0.4015 against 0.3956.
+        if (part == 1 && dtype == CESX_F32 && pl.ntypes == 2) pl = plan(3);
+        if (pl.max_rb * tile > gram_max_stage_rows()) { e.err = "gram plan exceeds LDS"; return CESX_EINVAL; }
     }
-    CESX_HIP(hipGetLastError());
+    // MFMA cycles of the second Gram launch's busiest SIMD, roughly: blocks x tiles x MFMAs per block and tile x 64 / SIMDs
+    const double cyc = (double)e.gp[1].plan.nblocks * (double)ntiles * (dtype == CESX_F32 ? 16.0 : 4.0) * 64.0 /
+                       (4.0 * std::max(1, e.num_cus));
+    e.gram_b_short = cyc < 60e-6 * 2.3e9;
     return CESX_OK;
 }
 
+int gram_part_alloc(Engine& e, GramPart& gp) {
+    const GramPlan& pl = gp.plan;
+    int rc;
+    for (const GramPart::Table& t : gp.tables()) {
+        if ((rc = dmalloc(e, t.dev, t.host->size() * 4))) return rc;
+        CESX_HIP(hipMemcpy(*t.dev, t.host->data(), t.host->size() * 4, hipMemcpyHostToDevice));
+    }
+    char* slabs;
+    if ((rc = dmalloc(e, &slabs, (size_t)std::max(pl.total_slabs, 1) * pl.tile * pl.tile * e.esz))) return rc;
+    gp.d_slabs = slabs;
+    return dmalloc(e, &gp.d_rowsum_part, (size_t)pl.total_rs * e.P * 8);
+}
+
+void gram_part_free(GramPart& gp) {
+    for (const GramPart::Table& t : gp.tables()) (void)hipFree(*t.dev);      // (hipFree(nullptr) is a no-op)
+    (void)hipFree(gp.d_slabs);
+    (void)hipFree(gp.d_rowsum_part);
+}
+
+// ---------------------------------------------------------------------------
+// host: launches
+// ---------------------------------------------------------------------------
+GramKernel pick_gram_kernel(const Engine& e, int part, const void* U, const void* G) {
+    const GramPlan& pl = e.gp[part].plan;
+    // (a tiny problem can have all its blocks in part 0; the reduce still writes part 1's share of the buffer: row sums
+    //  it owns and the lagged tail)
+    if (pl.nblocks == 0) return GramKernel::None;
+    const bool al16 = (uintptr_t)U % 16 == 0 && (uintptr_t)G % 16 == 0;
+    const int kt = gram_kt(e.cfg.dtype);
+    bool imm = false;
+    // the LDS-DMA kernel when the shapes allow: J in whole tiles, 16-byte rows, the plan's types within its two LDS slots
+    if (e.gram_v2 && e.J % kt == 0 && e.J >= kt && al16 && gram2_rows_ok(pl.max_rb * pl.tile, &imm)) {
+        // sg: the DMA addresses as a scalar base + a 32-bit lane offset (glds16s)
+        const bool sg = e.p % 8 == 0 && e.P % 8 == 0 && (unsigned long long)e.J * e.esz * 7 + 128 < (1ull << 32);
+        return sg ? (imm ? GramKernel::Gram2SgImm : GramKernel::Gram2Sg) : (imm ? GramKernel::Gram2Imm : GramKernel::Gram2);
+    }
+    return e.J % (16 / (int)e.esz) == 0 && al16 ? GramKernel::Gram1Aligned : GramKernel::Gram1Scalar;
+}
+
+// the fp64 slab reduce of a part into L.mom
 template <typename T>
-static int launch_gram_reduce_t(Engine& e, int part, double* mom, hipStream_t s, hipEvent_t stop, const MetricFin* fin) {
-    GramPart& gp = e.gp[part];
+static int launch_gram_reduce_t(Engine& e, const GramLaunch& L) {
+    GramPart& gp = e.gp[L.part];
     const GramPlan& pl = gp.plan;
     const long long ngroups = (long long)pl.nblocks * pl.tile * pl.tile / Mfma<T>::VEC;
-    const int row_lo = std::min(pl.own_lo * pl.tile, e.p + e.n), row_hi = std::min(pl.own_hi * pl.tile, e.p + e.n);
-    const long long wgs = (ngroups + RED_G - 1) / RED_G + std::max(1, (row_hi - row_lo + RED_G - 1) / RED_G) + (fin ? 1 : 0);
-    const MetricFin f = fin ? *fin : MetricFin{};
-    const long long wgs_all = wgs;
-    if (stop)
-        hipExtLaunchKernelGGL(gram_reduce_kernel<T>, dim3((unsigned)wgs_all), dim3(RED_G * RED_S), 0, s, nullptr, stop, 0,
-                              (const T*)gp.d_slabs, (const int*)gp.d_blk_rc, (const int*)gp.d_row_own, pl.nblocks, pl.tile, e.ml,
-                              (long long)e.J, row_lo, row_hi, part == 0 ? 1 : 0, (const double*)gp.d_rowsum_part,
-                              part == 1 ? (const double*)e.d_metric_sums : (const double*)nullptr, mom, f);
-    else
-    hipLaunchKernelGGL(gram_reduce_kernel<T>, dim3((unsigned)wgs_all), dim3(RED_G * RED_S), 0, s,
-                       (const T*)gp.d_slabs, gp.d_blk_rc, gp.d_row_own, pl.nblocks, pl.tile, e.ml,
-                       (long long)e.J, row_lo, row_hi, part == 0 ? 1 : 0, gp.d_rowsum_part,
-                       part == 1 ? e.d_metric_sums : (const double*)nullptr, mom, f);
+    const int row_lo = std::min(pl.own_lo * pl.tile, e.P), row_hi = std::min(pl.own_hi * pl.tile, e.P);
+    const bool ride = L.fin.part != nullptr;
+    const dim3 grid((unsigned)((ngroups + RED_G - 1) / RED_G + std::max(1, (row_hi - row_lo + RED_G - 1) / RED_G) + (ride ? 1 : 0)));
+    auto launch = [&](auto... args) {
+        if (L.bound_stop) hipExtLaunchKernelGGL(gram_reduce_kernel<T>, grid, dim3(RED_G * RED_S), 0, L.s, nullptr, L.bound_stop, 0, args...);
+        else hipLaunchKernelGGL(gram_reduce_kernel<T>, grid, dim3(RED_G * RED_S), 0, L.s, args...);
+    };
+    launch((const T*)gp.d_slabs, (const int*)gp.d_blk_rc, (const int*)gp.d_row_own, pl.nblocks, pl.tile, e.ml, (long long)e.J,
+           row_lo, row_hi, L.part == 0 ? 1 : 0, (const double*)gp.d_rowsum_part,
+           L.part == 1 ? (const double*)e.d_metric_sums : (const double*)nullptr, L.mom, L.fin);
     CESX_HIP(hipGetLastError());
     return CESX_OK;
 }
-
-int launch_gram_reduce(Engine& e, int part, double* mom, hipStream_t s, hipEvent_t stop, const MetricFin* fin) {
-    return e.cfg.dtype == CESX_F32 ? launch_gram_reduce_t<float>(e, part, mom, s, stop, fin)
-                                   : launch_gram_reduce_t<double>(e, part, mom, s, stop, fin);
+// (in front of launch_moments: the compiler emits the kernels in the order host code first names them -- the reduce first)
+static int launch_gram_reduce(Engine& e, const GramLaunch& L) {
+    return e.cfg.dtype == CESX_F32 ? launch_gram_reduce_t<float>(e, L) : launch_gram_reduce_t<double>(e, L);
 }
 
-int launch_gram(Engine& e, int part, const void* U, const void* G, double* mom, hipStream_t s, bool no_reduce) {
-    int rc = e.cfg.dtype == CESX_F32 ? launch_gram_t<float>(e, part, U, G, s) : launch_gram_t<double>(e, part, U, G, s);
-    if (rc != CESX_OK || no_reduce) return rc;
-    return launch_gram_reduce(e, part, mom, s, nullptr, nullptr);
+template <typename T>
+static int launch_gram1_t(Engine& e, const GramLaunch& L, bool aligned) {
+    const int rows = e.gp[L.part].plan.max_rb * e.gp[L.part].plan.tile;
+    return launch_gram_kernel<T>(e, L, aligned ? gram_kernel<T, true> : gram_kernel<T, false>, GRAM_THREADS,
+                                 2 * rows * ROW_STRIDE + rows * 16, false);
+}
+
+int launch_moments(Engine& e, const GramLaunch& L) {
+    const GramKernel k = pick_gram_kernel(e, L.part, L.U, L.G);
+    e.prof_part = L.part;
+    int rc = CESX_OK;
+    if (k == GramKernel::Gram1Aligned || k == GramKernel::Gram1Scalar) {
+        const bool aligned = k == GramKernel::Gram1Aligned;
+        rc = e.cfg.dtype == CESX_F32 ? launch_gram1_t<float>(e, L, aligned) : launch_gram1_t<double>(e, L, aligned);
+    } else if (k != GramKernel::None) {
+        rc = launch_gram2(e, L, k);
+    }
+    return rc != CESX_OK ? rc : launch_gram_reduce(e, L);
 }
 
 int gram_nbw(int dtype) { return dtype == CESX_F32 ? GramCfg<float>::NBW : GramCfg<double>::NBW; }

@@ -41,7 +41,7 @@
 //
 // Work partition, slab layout and the fp64 fixed-order reduce are those of kernels_gram.hip
 // (GramPlan, gram_reduce_kernel).  Qualifies when J is a multiple of the tile width (32 f32 / 16 f64)
-// and U, G are 16-byte aligned; otherwise the register-staged kernel runs.
+// and U, G are 16-byte aligned; otherwise the register-staged kernel runs (pick_gram_kernel, kernels_gram.hip).
 // Bound: MFMA (v_mfma_f32_32x32x2_f32 / v_mfma_f64_16x16x4_f64).
 #include "cesx_internal.h"
 #include <hip/hip_ext.h>
@@ -484,39 +484,22 @@ void gram2_kernel(const T* __restrict__ U, const T* __restrict__ G, const T* __r
 #endif
 }
 
-template <typename T>
-static int launch_gram2_t(Engine& e, int part, const void* U, const void* G, hipStream_t s) {
-    GramPart& gp = e.gp[part];
-    const GramPlan& pl = gp.plan;
-    constexpr int KT = G2_ROWB / (int)sizeof(T);
-    if (e.J % KT != 0 || e.J < KT || ((uintptr_t)U & 15) || ((uintptr_t)G & 15)) return -1;
-    const int nrows = pl.max_rb * pl.tile;
-    if (nrows > G2_MAX_ROWS) return -1;
-    const bool imm = nrows * G2_ROWB <= G2_SLOT_IMM;
-    const int lds = imm ? 2 * G2_SLOT_IMM : 2 * G2_SLOT;
-    const bool sg = e.p % 8 == 0 && e.P % 8 == 0 && (unsigned long long)e.J * sizeof(T) * 7 + 128 < (1ull << 32);
-    auto kern = sg ? (imm ? gram2_kernel<T, true, true> : gram2_kernel<T, true, false>)
-                   : (imm ? gram2_kernel<T, false, true> : gram2_kernel<T, false, false>);
-    CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    {
-        e.prof_part = part;
-        ProfScope prof(e, (e.profile_gap_only && part == 0) ? -1 : 0, s, true);      // (gap-only: the second launch's stop, nothing else)
-        if (prof.on())
-            hipExtLaunchKernelGGL(kern, dim3(pl.total_wgs), dim3(G2_THREADS), (unsigned)lds, s, prof.a, prof.b, 0,
-                                  (const T*)U, (const T*)G, (const T*)e.d_shiftT, e.p, e.n, (long long)e.J,
-                                  (const int*)gp.d_type_hdr, pl.ntypes, (const int*)gp.d_rows, (const int*)gp.d_wblk,
-                                  (T*)gp.d_slabs, gp.d_rowsum_part);
-        else
-        hipLaunchKernelGGL(kern, dim3(pl.total_wgs), dim3(G2_THREADS), lds, s, (const T*)U, (const T*)G,
-                           (const T*)e.d_shiftT, e.p, e.n, (long long)e.J, gp.d_type_hdr, pl.ntypes, gp.d_rows,
-                           gp.d_wblk, (T*)gp.d_slabs, gp.d_rowsum_part);
-    }
-    CESX_HIP(hipGetLastError());
-    return CESX_OK;
+bool gram2_rows_ok(int nrows, bool* imm) {
+    *imm = nrows * G2_ROWB <= G2_SLOT_IMM;
+    return nrows <= G2_MAX_ROWS;
 }
 
-int launch_gram2(Engine& e, int part, const void* U, const void* G, hipStream_t s) {
-    return e.cfg.dtype == CESX_F32 ? launch_gram2_t<float>(e, part, U, G, s) : launch_gram2_t<double>(e, part, U, G, s);
+template <typename T>
+static int launch_gram2_t(Engine& e, const GramLaunch& L, GramKernel k) {
+    const bool imm = k == GramKernel::Gram2Imm || k == GramKernel::Gram2SgImm;
+    const bool sg = k == GramKernel::Gram2Sg || k == GramKernel::Gram2SgImm;
+    auto kern = sg ? (imm ? gram2_kernel<T, true, true> : gram2_kernel<T, true, false>)
+                   : (imm ? gram2_kernel<T, false, true> : gram2_kernel<T, false, false>);
+    return launch_gram_kernel<T>(e, L, kern, G2_THREADS, imm ? 2 * G2_SLOT_IMM : 2 * G2_SLOT, true);
+}
+
+int launch_gram2(Engine& e, const GramLaunch& L, GramKernel k) {
+    return e.cfg.dtype == CESX_F32 ? launch_gram2_t<float>(e, L, k) : launch_gram2_t<double>(e, L, k);
 }
 
 }  // namespace cesx

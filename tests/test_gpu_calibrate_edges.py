@@ -67,9 +67,9 @@ def gram_plan(p, n, J, dtype):
 
 
 def k1_launches(c, cus=256):
-    """Per Gram launch of a K1 case: (staged rows, kernel arm, replanned) -- launch_gram2_t restated: gram2_kernel when J is
+    """Per Gram launch of a K1 case: (staged rows, kernel arm, replanned) -- pick_gram_kernel restated: gram2_kernel when J is
     whole tiles and U, G are 16-byte aligned, its imm arm up to 480 staged rows (max_rb * tile of the PLAN, not p + n), the
-    other arm up to 512; otherwise the v1 Gram.  replanned: cesx_create plans that launch again (oracle/calibrate_ref.py)."""
+    other arm up to 512; otherwise the v1 Gram.  replanned: plan_gram_parts plans that launch again (oracle/calibrate_ref.py)."""
     tile = kt = 32 if c["dtype"] == "float32" else 16
     out = []
     for info, replanned in cr.gram_plans(c["p"], c["n"], c["J"], c["dtype"], cus, gram_plan(c["p"], c["n"], c["J"], c["dtype"])):

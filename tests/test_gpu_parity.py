@@ -814,6 +814,66 @@ def test_single_device_fast_path_variants_match(eng_mod, monkeypatch, dtype):
         assert o[1] == outs[0][1]
 
 
+@pytest.mark.parametrize("J", [1024, 1004])      # gram2_kernel | the register-staged Gram with scalar loads
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+def test_uu_entry_points_agree(eng_mod, dtype, J):
+    """The three ways into the first half of a step -- cesx_moments_uu + cesx_chol_async, cesx_moments_uu_handover +
+    cesx_chol_async, cesx_moments_uu_chol -- each on torch's current stream, on a second stream and on the engine's own
+    side stream (nothing to hand over there), followed by moments_rest, apply and result: the same U x U head of the
+    moment buffer, the same U_next and the same step result, bit for bit.  One engine per case, one centring pass, the
+    noise injected.  Every apply leaves the engine the shift it predicts for the NEXT ensemble (K2), and the moments are
+    taken of the shifted data: the shift of the one centring pass is installed again in front of every step, so that all
+    of them start from the same state.  One step up front, so that the lagged metrics every compared step reports are
+    those of an equal step."""
+    import contextlib
+    import torch
+    p, n = 33, 17
+    d = _synthetic(p, n, J, seed=J)
+    eng = eng_mod.Engine(p, n, J, dtype=dtype, seed=5)
+    eng.set_problem(d["y"], d["Gamma"], d["mu"], d["sigma"], d["ustar"])
+    U, G, xi = eng.to_device(d["U0"]), eng.to_device(d["G"]), eng.to_device(d["xi"])
+    sums = eng.colsum(U, G)
+    prm = eng_mod.step_params(update="aldi", step_index=0)
+    nuu = eng.moments_uu_len()
+
+    def plain(mom):
+        eng.moments_uu(U, G, out=mom)
+        eng.chol_async(prm, mom)
+
+    def handover(mom):
+        eng.moments_uu_handover(U, G, out=mom)
+        eng.chol_async(prm, mom)
+
+    def fused(mom):
+        eng.moments_uu_chol(prm, U, G, out=mom)
+
+    def step(entry, stream):
+        mom = torch.zeros(eng.moments_len(), dtype=torch.float64, device=eng.device)
+        out = eng.empty(p)
+        eng.set_shift(sums)
+        torch.cuda.synchronize()
+        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+            entry(mom)
+            eng.moments_rest(U, G, mom)
+            eng.apply(prm, mom, U, G, xi=xi, out=out)
+            res = eng.result()
+        torch.cuda.synchronize()
+        return (mom[:nuu].cpu().numpy().copy(), out.cpu().numpy().copy(),
+                (res.hk, res.t_new, res.bias, res.self_bias, res.bias_data, res.self_bias_data, res.radspec, res.status,
+                 res.lag_bias_data, res.lag_self_bias_data))
+
+    step(plain, None)
+    streams = {"current": None, "second": torch.cuda.Stream(device=eng.device), "side": eng.side_stream()}
+    outs = {(sn, en.__name__): step(en, st) for sn, st in streams.items() for en in (plain, handover, fused)}
+    ref = outs["current", "plain"]
+    assert np.isfinite(ref[0]).all() and np.isfinite(ref[1]).all() and ref[2][7] == 0
+    assert ref[0][0] == J and np.abs(ref[0][1 + p:]).max() > 0
+    for key, o in outs.items():
+        assert np.array_equal(o[0], ref[0]), key
+        assert np.array_equal(o[1], ref[1]), key
+        assert np.array_equal(np.array(o[2]), np.array(ref[2]), equal_nan=True), (key, o[2], ref[2])
+
+
 @pytest.mark.parametrize("dtype,p,n,J", [("float32", 256, 256, 16384), ("float32", 96, 80, 4096), ("float64", 128, 96, 4096),
                                          ("float64", 250, 130, 8192)])
 def test_polled_side_stream_join_is_bit_identical(eng_mod, monkeypatch, dtype, p, n, J):

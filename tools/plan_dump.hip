@@ -1,10 +1,43 @@
-// dev tool (host only, runs without a GPU): the Gram work partition of a shape -- types, staged block rows, slices, the row traffic
-// the plan implies and the busiest SIMD against the mean.   usage: plan_dump p n J f64(0|1) [workgroup budget of the second launch]
+// dev tool (host only, runs without a GPU): the Gram work partition of a shape.
+//   plan_dump p n J f64(0|1) [workgroup budget of the second launch]
+//       types, staged block rows, slices, the row traffic the plan implies and the busiest SIMD against the mean
+//   plan_dump engine p n J f64(0|1) [shards] [CUs]
+//       both parts as an engine of that shape plans them (plan_gram_parts: the budgets of `CUs` compute units -- 256 --, the
+//       slim or the blocked factorisation beside the second launch, J the local share of `shards` x J, the re-plan): the
+//       totals and every integer of the five device tables.  Two trees that print the same plan the same sums.
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -o tools/plan_dump tools/plan_dump.hip
 #include "../ces_amd/csrc/kernels_gram.hip"
+#include "../ces_amd/csrc/kernels_gram2.hip"
 #include <cstdio>
 using namespace cesx;
+static void table(const char* name, const std::vector<int>& v) {
+    printf("  %s[%zu]:", name, v.size());
+    for (int q : v) printf(" %d", q);
+    printf("\n");
+}
+static int dump_engine(int argc, char** argv) {
+    if (argc < 6) return 2;
+    Engine e;
+    e.p = atoi(argv[2]); e.n = atoi(argv[3]); e.P = e.p + e.n; e.J = atoll(argv[4]);
+    e.cfg.dtype = atoi(argv[5]) ? CESX_F64 : CESX_F32;
+    e.esz = e.cfg.dtype == CESX_F32 ? 4 : 8;
+    e.Jg = e.J * (argc > 6 ? atoi(argv[6]) : 1);
+    e.num_cus = argc > 7 ? atoi(argv[7]) : 256;
+    const int rc = plan_gram_parts(e);
+    printf("engine p %d n %d J %lld Jg %lld f64 %d cus %d: rc %d center_u_wgs %d gram_b_short %d\n", e.p, e.n, (long long)e.J,
+           (long long)e.Jg, e.cfg.dtype == CESX_F64, e.num_cus, rc, e.center_u_wgs, (int)e.gram_b_short);
+    for (int part = 0; part < 2; ++part) {
+        const GramPlan& pl = e.gp[part].plan;
+        printf(" part %d: tile %d nbr %d nblocks %d ntypes %d max_rb %d nbw %d wgs %d slabs %d rs %d own [%d, %d)\n", part, pl.tile,
+               pl.nbr, pl.nblocks, pl.ntypes, pl.max_rb, pl.nbw, pl.total_wgs, pl.total_slabs, pl.total_rs, pl.own_lo, pl.own_hi);
+        table("type_hdr", pl.type_hdr); table("rows", pl.rows); table("wblk", pl.wblk); table("blk_rc", pl.blk_rc);
+        table("row_own", pl.row_own);
+    }
+    return rc;
+}
 int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "engine")) return dump_engine(argc, argv);
+    if (argc < 5) return 2;
     int p = atoi(argv[1]), n = atoi(argv[2]); long long J = atoll(argv[3]); int f64 = atoi(argv[4]); int budget_b = argc > 5 ? atoi(argv[5]) : 248;
     int tile = f64 ? 16 : 32, nbw = f64 ? 8 : 4, kt = f64 ? 16 : 32, esz = f64 ? 8 : 4;
     int P = p + n, pbU = (p + tile - 1) / tile;
@@ -24,4 +57,3 @@ int main(int argc, char** argv) {
         printf("  row traffic %.1f MB (algorithmic %.1f MB), slabs %.1f MB\n", traffic / 1e6, (double)P * J * esz / 1e6, slabs / 1e6);
     }
 }
-namespace cesx { int launch_gram2(Engine&, int, const void*, const void*, hipStream_t) { return -1; } }
