@@ -355,7 +355,7 @@ struct Engine {
         bool signals = false;           // the last cesx_chol_async stores seq into d_cholflag (its last kernel does)
         unsigned long long seq = 0;     // cesx_chol_async calls so far: the sequence number of the last one
         unsigned long long waited_seq = 0; hipStream_t waited_stream = nullptr;      // the last one launch_dense joined, and on which stream
-        bool polled = false;            // the last launch_dense (phase 0 / 1) joined through the polled word, not the event
+        bool polled = false;            // the last launch_dense (Step / Drift) joined through the polled word, not the event
         bool image_only = false;        // the last factorisation into d_L wrote the chained image only: d_L does not hold it (ensure_factor)
     } fac;
     bool fuse_center_auto = true;     // no CESX_FUSE_CENTER given: fused where the step takes the hk-free form AND the second Gram launch is
@@ -599,10 +599,59 @@ int launch_moments(Engine& e, const GramLaunch& L);
 // kernels_gram2.hip: the staged rows gram2_kernel takes, and (imm) whether its ds_read offsets reach both slots
 bool gram2_rows_ok(int nrows, bool* imm);
 int launch_gram2(Engine& e, const GramLaunch& L, GramKernel k);      // k: one of the Gram2 arms
-// upd_ok: an update kernel takes the hk-free image of this step (pick_update_kernel)
-int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int phase, hipStream_t s, bool upd_ok = false);
-// whether launch_dense (phase 0) writes the hk-free image for this step when an update kernel takes it
-bool dense_hkfree(const Engine& e, const cesx_step_params& prm);
+// ---- K2: the dense algebra between the moments and the update (kernels_dense.hip) ----
+enum class DensePhase { Step, Drift, Noise };      // everything for eks / aldi; aldi_constant: the drift coefficients, the noise
+                                                   // coefficients once hk is known
+// One K2 launch; call sites name the fields they use.
+struct DenseLaunch {
+    const cesx_step_params* prm = nullptr;
+    const double* mom = nullptr;      // (Noise: none)
+    DensePhase phase = DensePhase::Step;
+    hipStream_t s = nullptr;
+    bool upd_ok = false;              // an update kernel takes the hk-free image of this step (pick_update_kernel)
+};
+// center_kernel's `what`
+constexpr int CENTER_U = 1;           // the part that depends on U alone (C, M, ubar, the trace / bias partials)
+constexpr int CENTER_G = 2;           // the part that involves G
+constexpr int CENTER_KEEP_STATUS = 4; // the status word stays: a factorisation with the centring fused into its load already ran
+enum class AssembleMode { Aldi, Eks, ConstDrift, ConstNoise };      // assemble_kernel's `mode`, in its order
+enum class DenseRoute {
+    NoiseOnly,      // hk from the drift's absmax, then the noise coefficients
+    Tail,           // hk-free: one launch behind the factorisation writes the rest of the image (tail_aldi_kernel)
+    Finish,         // aldi, default / spectral time step: scalars, matvecs and W in one launch (finish_aldi_kernel)
+    General         // scalars, the recomputed gain, the EKS inverse, assemble_kernel
+};
+enum class TailArm { None, DenseSigma, Chained, Plain };      // tail_aldi_kernel<DSIG, CHAIN>
+enum class SideJoin { None, Event, Polled };        // nothing in flight; ev_b; the word chol(C) stores, polled by a launch of this stream
+enum class UPart {
+    Side,           // the side stream formed it (centring launch in front of its factorisation)
+    Center,         // a centring launch of this stream forms it
+    FusedLoad       // the factorisation formed C while it loaded S_aa, the tail launch forms the rest (its self_u)
+};
+enum class InlineFactor { None, Image, Fp64 };      // chol(C) on this stream: into the hk-free image (and d_L unless chained), into d_L
+// Everything launch_dense decides, as plain data (plan_dense); a field its route does not use holds its zero value.
+struct DensePlan {
+    DenseRoute route = DenseRoute::General;
+    TailArm tail = TailArm::None;
+    SideJoin join = SideJoin::None;
+    UPart upart = UPart::Side;
+    int center = 0;                   // CENTER_* parts of the centring launch of this stream, 0: none
+    InlineFactor factor = InlineFactor::None;
+    bool refactor = false;            // d_L is wanted and the factor at hand is in the chained image only: ensure_factor factors C again
+    bool gemm_M = false;              // M = C Sigma^{-1} by GEMM (dense Sigma)
+    bool spectral = false;            // lambda_max of the whitened residual covariance (spectral time step)
+    bool gain_inverse = false;        // K' = C_ug (hk C_gg + Gamma)^{-1}
+    bool eks_inverse = false;         // P = Sigma (Sigma + hk C)^{-1}
+    AssembleMode mode = AssembleMode::Aldi;
+    int ktot = 0;                     // columns of the W assemble_kernel writes, 0: it does not run
+};
+// The K2 of this launch for the engine as it stands.  Pure: no HIP call, no write.  below_side: stream_below_side(e, L.s),
+// which a caller asks only where poll_join_open holds -- nothing else hinges on it.
+DensePlan plan_dense(const Engine& e, const DenseLaunch& L, bool below_side);
+// what every polled join asks besides the stream priorities: a signalling factorisation in flight, one device, two streams
+bool poll_join_open(const Engine& e, hipStream_t s);
+// runs a plan: no decision of its own.  The one writer of Engine::last_hkfree and, through join_side, of what Factor keeps of the join.
+int launch_dense(Engine& e, const DenseLaunch& L, const DensePlan& plan);
 // Kernels of the caller's stream and of the side stream may WAIT for each other inside a launch (the polled join of
 // launch_dense) only when the two streams cannot share a hardware queue: HIP maps the streams of one priority level
 // onto a few queues, and a waiter in front of what it waits for in one in-order queue never ends.  True when `s` has a

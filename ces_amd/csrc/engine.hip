@@ -108,8 +108,7 @@ int check_prm(Engine& e, const cesx_step_params* prm) {
     return CESX_OK;
 }
 
-int finish_step(Engine& e, const cesx_step_params& prm, hipStream_t s) {
-    TRY(launch_publish(e, s));
+int finish_step(Engine& e, const cesx_step_params& prm) {
     e.pending = true;
     e.last_prm = prm;
     return CESX_OK;
@@ -159,12 +158,6 @@ int run_update_main(Engine& e, const cesx_step_params& prm, const void* U, const
     const int rc = launch_update(e, main_update(e, prm, U, G, xi, Unext, e.last_hkfree), s);
     e.last_metric_parts = e.last_update_grid_x;
     return rc;
-}
-
-// data metrics: K3 accumulated them while the (whitened) G rows streamed by
-int finish_metrics(Engine& e, const double* mom, const void* G, bool publish, hipStream_t s) {
-    (void)G;
-    return launch_metric_final(e, mom, publish, s);
 }
 
 }  // namespace
@@ -605,13 +598,14 @@ int cesx_apply_drift(cesx_handle h, const cesx_step_params* prm, const double* m
     FLUSH(e);
     hipStream_t s = (hipStream_t)stream;
     WHITEN(e, G, s, false);
-    TRY(launch_dense(e, *prm, mom, 1, s));
+    const DenseLaunch K2{.prm = prm, .mom = mom, .phase = DensePhase::Drift, .s = s};
+    TRY(launch_dense(e, K2, plan_dense(e, K2, poll_join_open(e, s) && stream_below_side(e, s))));
     TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.d_W, .Wf = e.d_Wf, .ktot = e.kp + e.kn, .bias = e.d_bias,
                                       .src = {{U, e.p, 0, 0}, {G, e.n, 0, 0}}, .nsrc = 2, .out = Unext,
                                       .absmax_part = e.d_absmax_part, .step_index = prm->step_index, .metrics = true}, s));
     e.last_metric_parts = e.last_update_grid_x;
     const int nparts = e.last_update_grid;
-    TRY(finish_metrics(e, mom, G, false, s));
+    TRY(launch_metric_final(e, mom, false, s));      // data metrics: K3 accumulated them while the (whitened) G rows streamed by
     return launch_absmax_final(e, nparts, absmax, s);
 }
 
@@ -625,13 +619,15 @@ int cesx_apply_finish(cesx_handle h, const cesx_step_params* prm, const double* 
     FLUSH(e);
     hipStream_t s = (hipStream_t)stream;
     if (absmax != e.d_absmax) CESX_HIP(hipMemcpyAsync(e.d_absmax, absmax, 8, hipMemcpyDeviceToDevice, s));
-    TRY(launch_dense(e, *prm, nullptr, 2, s));
+    const DenseLaunch K2{.prm = prm, .phase = DensePhase::Noise, .s = s};
+    TRY(launch_dense(e, K2, plan_dense(e, K2, false)));
     // U_next = sqrt(2hk) L xi + 1 * U + hk * drift   (drift currently lives in U_next)
     if (!xi) xi = prefetched_noise(e, *prm, s);
     TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.d_W, .Wf = e.d_Wf, .ktot = e.kp, .src = {{xi, e.p, xi ? 0 : 1, 1}},
                                       .nsrc = 1, .add1 = {U, nullptr, 1.0}, .add2 = {Unext, &e.d_scal->hk, 1.0}, .out = Unext,
                                       .step_index = prm->step_index}, s));
-    return finish_step(e, *prm, s);
+    TRY(launch_publish(e, s));
+    return finish_step(e, *prm);
 }
 
 int cesx_apply(cesx_handle h, const cesx_step_params* prm, const double* mom, const void* U, const void* G,
@@ -652,11 +648,13 @@ int cesx_apply(cesx_handle h, const cesx_step_params* prm, const double* mom, co
     WHITEN(e, G, s, false);
     // (the kernel that would take this step's hk-free image is known here: the hk-free K2 has no other consumer)
     const UpdateKernel hk = pick_update_kernel(e, main_update(e, *prm, U, G, xi, Unext, true));
+    const DenseLaunch K2{.prm = prm, .mom = mom, .phase = DensePhase::Step, .s = s, .upd_ok = hk != UpdateKernel::None};
+    const DensePlan plan = plan_dense(e, K2, poll_join_open(e, s) && stream_below_side(e, s));
     // the chained form reads its noise from memory: a block neither injected nor drawn ahead goes into an engine buffer,
     // allocated here -- nothing is allocated once K2 is enqueued
-    if (hk == UpdateKernel::Update4 && !xi && prefetched_block(e, prm->step_index) < 0 && dense_hkfree(e, *prm) && !e.d_xi_tmp)
+    if (hk == UpdateKernel::Update4 && !xi && prefetched_block(e, prm->step_index) < 0 && plan.route == DenseRoute::Tail && !e.d_xi_tmp)
         CESX_HIP(hipMalloc(&e.d_xi_tmp, (size_t)e.p * (size_t)e.J * e.esz));
-    TRY(launch_dense(e, *prm, mom, 0, s, hk != UpdateKernel::None));
+    TRY(launch_dense(e, K2, plan));
     TRY(run_update_main(e, *prm, U, G, xi, Unext, s));
     // (Moving this last small kernel to the side stream was tried: the event record + wait pair costs
     //  as much GPU idle time as the 7 us kernel itself.)
@@ -665,11 +663,9 @@ int cesx_apply(cesx_handle h, const cesx_step_params* prm, const double* mom, co
         // stream) -- no one-workgroup kernel (7 us) between this update and the next Gram launch; anything else flushes it
         e.met_deferred = true; e.met_stream = s;      // (reads the engine's own d_lag, not `mom`)
     } else {
-        TRY(finish_metrics(e, mom, G, true, s));     // also publishes the step result to the host
+        TRY(launch_metric_final(e, mom, true, s));     // also publishes the step result to the host
     }
-    e.pending = true;
-    e.last_prm = *prm;
-    return CESX_OK;
+    return finish_step(e, *prm);
 }
 
 int cesx_step(cesx_handle h, const cesx_step_params* prm, const void* U, const void* G, const void* xi,
@@ -1177,6 +1173,33 @@ int cesx_calibrate_mfma(cesx_handle h, double target_ms, double* tflops, double*
     SET_DEVICE(e);
     FLUSH(e);
     return launch_calibrate(e, target_ms, tflops, clock_ghz, (hipStream_t)stream);
+}
+
+// Host-only: plan_dense for an engine state and a launch given as 23 facts (include/cesx.h), the plan's 13 fields as integers.
+int cesx_debug_dense_plan(const int32_t* f, int32_t* plan) {
+    if (!f || !plan || f[0] < CESX_UPDATE_EKS || f[0] > CESX_UPDATE_ALDI_CONSTANT || f[1] < CESX_TS_DEFAULT || f[1] > CESX_TS_MIX ||
+        f[2] < 0 || f[2] > 2) return -1;
+    try {
+        Engine e;
+        cesx_step_params prm{};
+        prm.update = f[0]; prm.time_step = f[1];
+        e.cfg.dtype = f[4] ? CESX_F64 : CESX_F32;
+        e.p = f[5] ? 256 : 257;                          // potrf_ld(p) <= 256 or not
+        e.kp = 16; e.kn = 32; e.ktot = 64;               // (any three that tell kp, kp + kn and ktot apart)
+        e.diag_sigma = f[6]; e.chain = f[7]; e.hkfree_ok = f[8]; e.update_v2 = f[9];
+        e.d_Wq = f[10] ? &e : nullptr;                   // (never dereferenced)
+        e.fac.inflight = f[11]; e.fac.fused_center = f[12]; e.fac.img = f[13]; e.fac.signals = f[14]; e.fac.image_only = f[15];
+        e.poll_join_ok = f[16];
+        e.J = 1; e.Jg = f[17] ? 2 : 1;
+        e.side = reinterpret_cast<hipStream_t>(&e.side);
+        e.fuse_center_ok = f[20]; e.fuse_center_auto = f[21]; e.gram_b_short = f[22];
+        const DenseLaunch L{.prm = &prm, .phase = (DensePhase)f[2], .s = f[18] ? e.side : nullptr, .upd_ok = f[3] != 0};
+        const DensePlan P = plan_dense(e, L, f[19] != 0);
+        const int32_t out[13] = {(int)P.route, (int)P.tail, (int)P.join, (int)P.upart, P.center, (int)P.factor, P.refactor, P.gemm_M,
+                                 P.spectral, P.gain_inverse, P.eks_inverse, (int)P.mode, P.ktot};
+        std::copy(out, out + 13, plan);
+        return 0;
+    } catch (...) { return -2; }
 }
 
 // Host-only: builds the Gram work partition a handle of this shape would use (no device needed) and checks its

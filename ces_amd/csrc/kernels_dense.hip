@@ -1906,17 +1906,16 @@ static int factor_C(Engine& e, hipStream_t s, PotrfLaunch f, bool chained) {
     return potrf(e, s, e.p, f);
 }
 
-// the fp64 factor of the current covariance in d_L, for every host reader of it (launch_dense, assemble, cesx_debug_dense)
+// the fp64 factor of the current covariance in d_L, for every host reader of it (launch_dense where its plan says so, cesx_debug_dense)
 int ensure_factor(Engine& e, hipStream_t s) {
     return e.fac.image_only ? factor_C(e, s, {.A = e.d_C}, false) : CESX_OK;
 }
 
 template <typename T>
-static int assemble(Engine& e, hipStream_t s, int mode, int ktot, double sw) {
+static int assemble(Engine& e, hipStream_t s, AssembleMode mode, int ktot, double sw) {
     const int mx = e.p > e.n ? e.p : e.n;
     const long long len = (long long)e.rpad * ktot;
-    if (const int rc = ensure_factor(e, s)) return rc;
-    hipLaunchKernelGGL(assemble_kernel<T>, g1(len), dim3(256), 0, s, mode, e.p, e.n, e.kp, e.kn, e.rpad, ktot,
+    hipLaunchKernelGGL(assemble_kernel<T>, g1(len), dim3(256), 0, s, (int)mode, e.p, e.n, e.kp, e.kn, e.rpad, ktot,
                        sw, e.d_scal, e.d_M, e.d_K, e.d_L, potrf_ld(e.p), e.d_P, e.d_PK, e.d_mv, mx, e.d_ubar, e.d_gbar,
                        e.d_y, (const double*)e.d_gw, (T*)e.d_W, (T*)e.d_bias,
                        (T*)e.d_shiftT, e.d_shift64, (T*)e.d_rowc,
@@ -1949,22 +1948,81 @@ static bool image_ok(const Engine& e, int update) {
         potrf_ld(e.p) <= 256;
 }
 
-bool dense_hkfree(const Engine& e, const cesx_step_params& prm) {
+bool poll_join_open(const Engine& e, hipStream_t s) {
+    return e.fac.inflight && e.poll_join_ok && e.fac.signals && e.J == e.Jg && s != e.side;
+}
+
+DensePlan plan_dense(const Engine& e, const DenseLaunch& L, bool below_side) {
+    const cesx_step_params& prm = *L.prm;
+    DensePlan P;
+    if (L.phase == DensePhase::Noise) {
+        P.route = DenseRoute::NoiseOnly;
+        P.refactor = e.fac.image_only;
+        P.mode = AssembleMode::ConstNoise; P.ktot = e.kp;
+        return P;
+    }
+    const bool step = L.phase == DensePhase::Step;
+    // If cesx_chol_async already ran for these moments, the U-only part of K2 (C, M, ubar, chol(C))
+    // is done or in flight on the side stream; otherwise do it here, in line.
+    // The side stream (U-only centring, chol(C), the prefetched noise block) is joined ONCE, as late as the
+    // data flow allows: the G part of the centring needs the moments only; the scalar kernel is the first to
+    // read what the side stream wrote (trace / bias partials, later L).  One event each way per step -- every
+    // record / wait pair costs ~6 us of idle GPU.
+    const bool early = e.fac.inflight;
+    const bool fused_finish = step && prm.update == CESX_UPDATE_ALDI &&
+        (prm.time_step == CESX_TS_DEFAULT || prm.time_step == CESX_TS_SPECTRAL);
+    // a launch of this stream may poll the word chol(C) stores: no shared hardware queue (stream_below_side)
+    const bool poll_ok = poll_join_open(e, L.s) && below_side;
     // hk kept out of the coefficient matrix (cesx_internal.h, Engine::d_Wq): the side stream wrote L, a I - M, M mu, M ubar
     // for this factorisation, ONE launch adds the rest and the update kernel takes hk at run time
-    return prm.time_step == CESX_TS_DEFAULT && image_ok(e, prm.update) && (!e.fac.inflight || e.fac.img);
+    if (L.upd_ok && step && prm.time_step == CESX_TS_DEFAULT && image_ok(e, prm.update) && (!early || e.fac.img)) {
+        P.route = DenseRoute::Tail;
+        P.tail = !e.diag_sigma ? TailArm::DenseSigma : e.chain ? TailArm::Chained : TailArm::Plain;
+        // the side stream is joined by the LAST workgroup of the tail launch (the polled word), else by the event in front of it
+        P.join = !early ? SideJoin::None : poll_ok ? SideJoin::Polled : SideJoin::Event;
+        // (no factorisation in flight: in line, the same kernels the side stream would have run -- with CESX_FUSE_CENTER=1 the
+        //  factorisation forms C while it loads S_aa and the tail launch forms the rest of the U part itself)
+        const bool self_u = early ? e.fac.fused_center : (e.fuse_center_ok || (e.fuse_center_auto && e.gram_b_short));
+        P.upart = self_u ? UPart::FusedLoad : early ? UPart::Side : UPart::Center;
+        if (!early) {
+            P.center = self_u ? 0 : CENTER_U;
+            P.factor = InlineFactor::Image;          // (an in-line factorisation of a step that IS hk-free)
+        }
+        return P;
+    }
+    P.route = fused_finish ? DenseRoute::Finish : DenseRoute::General;
+    // (early, centring fused into the Cholesky's load: the U part is done HERE, with the G part, and leaves the
+    //  status word alone -- the side stream carried nothing but the factorisation)
+    P.upart = early && !e.fac.fused_center ? UPart::Side : UPart::Center;
+    P.center = !early ? CENTER_U | CENTER_G : e.fac.fused_center ? CENTER_U | CENTER_G | CENTER_KEEP_STATUS : CENTER_G;
+    // The side stream joined WITHOUT a barrier packet (6-8 us of the caller's stream even when the event completed long
+    // before): workgroup 0 of the G-part centring launch -- the launch in front of the assembly launch -- ends only when
+    // chol(C) has stored its sequence number, and the assembly launch reads what that stream wrote with agent-scope
+    // loads (no queue-level acquire stands between that stream's kernels and it).  Only where nothing else sits between the
+    // two and reads those results (ALDI, default time step, diagonal Gamma / Sigma, one device), and only for the one-kernel
+    // factorisation that signals.
+    const bool polled = fused_finish && prm.time_step == CESX_TS_DEFAULT && !e.fac.fused_center && e.diag_sigma && poll_ok &&
+        !e.fac.image_only;      // (a factor that must be re-formed in line: joined with the event)
+    P.join = !early ? SideJoin::None : polled ? SideJoin::Polled : SideJoin::Event;
+    if (!early) P.factor = InlineFactor::Fp64;
+    // the factorisation in flight expected a chained step and kept L in the image only (the time-step rule changed, or the
+    // ensembles of this call do not qualify): factor C again, in line
+    else P.refactor = e.fac.image_only;
+    P.gemm_M = !e.diag_sigma;
+    P.spectral = prm.time_step == CESX_TS_SPECTRAL && prm.update != CESX_UPDATE_ALDI_CONSTANT;
+    if (fused_finish) return P;
+    P.gain_inverse = step && (prm.time_step == CESX_TS_CONSTANT || (prm.time_step == CESX_TS_MIX && prm.update == CESX_UPDATE_ALDI));
+    P.mode = !step ? AssembleMode::ConstDrift : prm.update == CESX_UPDATE_EKS ? AssembleMode::Eks : AssembleMode::Aldi;
+    P.eks_inverse = P.mode == AssembleMode::Eks;
+    P.ktot = P.mode == AssembleMode::ConstDrift ? e.kp + e.kn : e.ktot;
+    return P;
 }
 
-// what both launch_dense paths ask of a polled join: a signalling factorisation in flight, one device, no shared hardware queue
-static bool poll_join_possible(Engine& e, hipStream_t s) {
-    return e.fac.inflight && e.poll_join_ok && e.fac.signals && e.J == e.Jg && s != e.side && stream_below_side(e, s);
-}
-
-// every launch_dense (phase 0 / 1): s joins the factorisation in flight, if any, through the event or (polled) a launch's poll
-static int join_side(Engine& e, hipStream_t s, bool polled) {
-    e.fac.polled = polled;
-    if (!e.fac.inflight) return CESX_OK;
-    if (!polled) CESX_HIP(hipStreamWaitEvent(s, e.ev_b, 0));
+// every launch_dense (Step / Drift): s joins the factorisation in flight, if any, through the event or (polled) a launch's poll
+static int join_side(Engine& e, hipStream_t s, SideJoin join) {
+    e.fac.polled = join == SideJoin::Polled;
+    if (join == SideJoin::None) return CESX_OK;
+    if (join == SideJoin::Event) CESX_HIP(hipStreamWaitEvent(s, e.ev_b, 0));
     // (polled: no queue-level wait was issued, but the launches behind are ordered behind chol(C) all the same -- the
     //  poll ended on its word, or it ran out and they leave the step untouched (the update launch checks the same
     //  fault word).  A noise block drawn BEFORE this chol(C) on the side stream is therefore complete: take_noise
@@ -1973,52 +2031,80 @@ static int join_side(Engine& e, hipStream_t s, bool polled) {
     return CESX_OK;
 }
 
-// phase 0: everything for eks / aldi.  phase 1: aldi_constant drift coefficients.
-// phase 2: aldi_constant noise coefficients after hk is known.
-int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int phase, hipStream_t s, bool upd_ok) {
+// finish_aldi_kernel<T, POLLED>: POLLED leaves the step untouched when the centring launch's poll ran out
+template <typename T>
+static int launch_finish(Engine& e, const DenseLaunch& L, bool polled) {
+    const int p = e.p, mx = p > e.n ? p : e.n;
+    const int nwb = (int)(((long long)e.rpad * e.ktot + DT - 1) / DT), nvb = (p + DT / 64 - 1) / (DT / 64);
+    auto kern = polled ? finish_aldi_kernel<T, true> : finish_aldi_kernel<T, false>;
+    hipLaunchKernelGGL(kern, dim3(nwb + nvb), dim3(DT), 0, L.s, MomView{p, e.n, L.mom}, *L.prm, (const double*)e.d_part, e.d_scal, nwb,
+                       e.kp, e.kn, e.rpad, e.ktot, (const double*)e.d_M, (const double*)e.d_K, (const double*)e.d_L, potrf_ld(p),
+                       (const double*)e.d_y, (const double*)e.d_gbar, (const double*)e.d_mu,
+                       (const double*)e.d_ubar, (const double*)e.d_gw, mx, e.d_mv, (T*)e.d_W,
+                       (T*)e.d_bias, (T*)e.d_shiftT, e.d_shift64, (T*)e.d_rowc, (float*)e.d_Wf,
+                       (const unsigned long long*)(e.d_cholflag + 1), (unsigned long long)e.fac.seq);
+    CESX_HIP(hipGetLastError());
+    return CESX_OK;
+}
+
+// lambda_max(B), B = Gamma^{-1/2} See Gamma^{-1/2} (Gamma diagonal, or whitened away): symmetric PSD, same non-zero spectrum as D (times N)
+static int launch_spectral(Engine& e, const double* mom, hipStream_t s) {
+    const int n = e.n;
+    hipLaunchKernelGGL(whiten_diag_kernel, g1((long long)n * n), dim3(256), 0, s, n, e.d_See, e.d_gw, e.d_t3);
+    // by repeated squaring (spec_square_kernel above): B in d_t3, the squares alternate between d_t1 and d_t2
+    const int nb16 = (n + 15) / 16, npart = nb16 * nb16;
+    double* acc = e.d_spec;                          // {sum of 2^-k log N_k, 2^-k, degenerate flag}
+    double* parts[2] = {e.d_spec + 4, e.d_spec + 4 + npart};
+    hipLaunchKernelGGL(spec_begin_kernel, dim3(npart), dim3(DT), 0, s, (long long)n * n, (const double*)e.d_t3, parts[0], npart, acc);
+    const double* src = e.d_t3;
+    double* dst = e.d_t1;
+    for (int q = 0; q < SPEC_SQUARINGS; ++q) {
+        hipLaunchKernelGGL(spec_square_kernel, dim3(nb16, nb16), dim3(DT), 0, s, n, src, (const double*)parts[q & 1], npart, dst,
+                           parts[(q & 1) ^ 1], acc);
+        src = dst;
+        dst = dst == e.d_t1 ? e.d_t2 : e.d_t1;
+    }
+    hipLaunchKernelGGL(spec_end_kernel, dim3(1), dim3(DT), 0, s, n, (const double*)parts[SPEC_SQUARINGS & 1], npart, (const double*)acc,
+                       mom, e.d_scal);
+    CESX_HIP(hipGetLastError());
+    return CESX_OK;
+}
+
+int launch_dense(Engine& e, const DenseLaunch& L, const DensePlan& P) {
+    const cesx_step_params& prm = *L.prm;
+    const double* mom = L.mom;
+    hipStream_t s = L.s;
     const int p = e.p, n = e.n, mx = p > n ? p : n;
     const bool f32 = e.cfg.dtype == CESX_F32;
+    const bool tail = P.route == DenseRoute::Tail, polled = P.join == SideJoin::Polled;
     int rc;
-    if (phase == 2) {
+    if (P.route == DenseRoute::NoiseOnly) {
         hipLaunchKernelGGL(constant_hk_kernel, dim3(1), dim3(1), 0, s, prm, e.d_absmax, e.d_scal);
         CESX_HIP(hipGetLastError());
-        return f32 ? assemble<float>(e, s, 3, e.kp, 0.0) : assemble<double>(e, s, 3, e.kp, 0.0);
+        if (P.refactor && (rc = ensure_factor(e, s))) return rc;
+        return f32 ? assemble<float>(e, s, P.mode, P.ktot, 0.0) : assemble<double>(e, s, P.mode, P.ktot, 0.0);
     }
     MomView mv{p, n, mom};
     const int unbiased = prm.update == CESX_UPDATE_EKS ? 0 : 1;
-    // If cesx_chol_async already ran for these moments, the U-only part of K2 (C, M, ubar, chol(C))
-    // is done or in flight on the side stream; otherwise do it here, in line.
-    // The side stream (U-only centring, chol(C), the prefetched noise block) is joined ONCE, as late as the
-    // data flow allows: the G part of the centring needs the moments only; the scalar kernel is the first to
-    // read what the side stream wrote (trace / bias partials, later L).  One event each way per step -- every
-    // record / wait pair costs ~6 us of idle GPU.
-    const bool early = e.fac.inflight;
-    const bool fused_finish = phase == 0 && prm.update == CESX_UPDATE_ALDI &&
-        (prm.time_step == CESX_TS_DEFAULT || prm.time_step == CESX_TS_SPECTRAL);
-    // (early, centring fused into the Cholesky's load: the U part is done HERE, with the G part, and leaves the
-    //  status word alone -- the side stream carried nothing but the factorisation)
-    const int what = !early ? 3 : e.fac.fused_center ? (3 | 4) : 2;
-    const bool hkfree = upd_ok && phase == 0 && dense_hkfree(e, prm);
     e.last_hkfree = false;
-    if (hkfree) {
-        // the side stream is joined by the LAST workgroup of that launch (a polled word, under the conditions of the polled
-        // join below), else by the event in front of it; no factorisation in flight: the U part runs here, in line
-        const bool polled = poll_join_possible(e, s);
-        // (no factorisation in flight: in line, the same kernels the side stream would have run -- with CESX_FUSE_CENTER=1 the
-        //  factorisation forms C while it loads S_aa and the tail launch forms the rest of the U part itself)
-        const int self_u = (early ? e.fac.fused_center : (e.fuse_center_ok || (e.fuse_center_auto && e.gram_b_short))) ? 1 : 0;
-        if (!early) {
-            PotrfLaunch f{.A = e.d_C, .wq = (float*)e.d_Wq};
-            if (self_u) { f.A = mom + e.ml.Saa(); f.lda = p; f.cen = {mom + e.ml.sa(), mom, unbiased}; }
-            else if ((rc = launch_center(e, s, dim3(NPB), dim3(DT), mom, unbiased, 1, nullptr))) return rc;
-            if ((rc = factor_C(e, s, f, true))) return rc;          // (an in-line factorisation of a step that IS hk-free)
-        }
-        if ((rc = join_side(e, s, polled))) return rc;
-        auto tail_kern = !e.diag_sigma ? tail_aldi_kernel<true, false> : e.chain ? tail_aldi_kernel<false, true> : tail_aldi_kernel<false, false>;
+    // (the tail launch polls for the side stream itself; otherwise the centring launch in front of the join does)
+    if (P.center && (rc = tail ? launch_center(e, s, dim3(NPB), dim3(DT), mom, unbiased, P.center, nullptr)
+                               : launch_center(e, s, dim3(NPB), dim3(DT), mom, unbiased, P.center, e.d_lag,
+                                               polled ? e.d_cholflag : nullptr, e.fac.seq, e.d_cholflag + 1))) return rc;
+    if ((rc = join_side(e, s, P.join))) return rc;
+    if (P.factor == InlineFactor::Image) {
+        PotrfLaunch f{.A = e.d_C, .wq = (float*)e.d_Wq};
+        if (P.upart == UPart::FusedLoad) { f.A = mom + e.ml.Saa(); f.lda = p; f.cen = {mom + e.ml.sa(), mom, unbiased}; }
+        if ((rc = factor_C(e, s, f, true))) return rc;
+    }
+    if (P.factor == InlineFactor::Fp64 && (rc = factor_C(e, s, {.A = e.d_C}, false))) return rc;
+    if (tail) {
+        auto tail_kern = P.tail == TailArm::DenseSigma ? tail_aldi_kernel<true, false>
+                       : P.tail == TailArm::Chained ? tail_aldi_kernel<false, true> : tail_aldi_kernel<false, false>;
         hipLaunchKernelGGL(tail_kern, dim3(NPB), dim3(DT), 0, s, mv, prm, (const double*)e.d_shift64, (const double*)e.d_y,
                            (const double*)e.d_gw, e.d_gbar, e.d_m, e.d_dg, e.d_Cug, e.d_See, e.d_Srr, e.d_K, e.d_part, e.d_scal,
                            e.d_lag, e.d_mv, mx, (const double*)e.d_sw, e.diag_sigma ? (const double*)nullptr : (const double*)e.d_Sinv,
-                           (const double*)e.d_mu, self_u, (const double*)e.d_ustar,
+                           (const double*)e.d_mu, P.upart == UPart::FusedLoad ? 1 : 0, (const double*)e.d_ustar,
                            e.d_ubar, e.d_C, e.d_M, (float*)e.d_Wq, e.ktot / 16, e.kp,
                            e.kn, (float*)e.d_bias, (float*)e.d_shiftT, e.d_shift64, (float*)e.d_rowc,
                            e.d_ticket, polled ? (const unsigned long long*)e.d_cholflag : (const unsigned long long*)nullptr,
@@ -2027,96 +2113,36 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
         e.last_hkfree = true;
         return CESX_OK;
     }
-    // The side stream joined WITHOUT a barrier packet (6-8 us of the caller's stream even when the event completed long
-    // before): workgroup 0 of the G-part centring launch -- the launch in front of the assembly launch -- ends only when
-    // chol(C) has stored its sequence number, and the assembly launch reads what that stream wrote with agent-scope
-    // loads (no queue-level acquire stands between that stream's kernels and it).  Only where nothing else sits between the two and reads those results (ALDI, default time
-    // step, diagonal Gamma / Sigma, one device), and only for the one-kernel factorisation that signals.
-    const bool polled = fused_finish && prm.time_step == CESX_TS_DEFAULT && !e.fac.fused_center && e.diag_sigma && poll_join_possible(e, s) &&
-        !e.fac.image_only;      // (a factor that must be re-formed in line: joined with the event)
-    if ((rc = launch_center(e, s, dim3(NPB), dim3(DT), mom, unbiased, what, e.d_lag, polled ? e.d_cholflag : nullptr, e.fac.seq,
-                            e.d_cholflag + 1))) return rc;
-    if ((rc = join_side(e, s, polled))) return rc;
-    if (!early && (rc = factor_C(e, s, {.A = e.d_C}, false))) return rc;
-    // the factorisation in flight expected a chained step and kept L in the image only (the time-step rule changed, or the
-    // ensembles of this call do not qualify): factor C again, in line
-    if ((rc = ensure_factor(e, s))) return rc;
-    if (!e.diag_sigma)
-        if ((rc = gemm(e, s, p, p, p, 1.0, e.d_C, p, 1, e.d_Sinv, p, 1, e.d_M))) return rc;
-    if (prm.time_step == CESX_TS_SPECTRAL && prm.update != CESX_UPDATE_ALDI_CONSTANT) {
-        // B = Gamma^{-1/2} See Gamma^{-1/2} (Gamma diagonal, or whitened away), symmetric PSD, same non-zero spectrum as D (times N)
-        hipLaunchKernelGGL(whiten_diag_kernel, g1((long long)n * n), dim3(256), 0, s, n, e.d_See, e.d_gw, e.d_t3);
-        // lambda_max(B) by repeated squaring (spec_square_kernel above): B in d_t3, the squares alternate between d_t1 and d_t2
-        const int nb16 = (n + 15) / 16, npart = nb16 * nb16;
-        double* acc = e.d_spec;                          // {sum of 2^-k log N_k, 2^-k, degenerate flag}
-        double* parts[2] = {e.d_spec + 4, e.d_spec + 4 + npart};
-        hipLaunchKernelGGL(spec_begin_kernel, dim3(npart), dim3(DT), 0, s, (long long)n * n, (const double*)e.d_t3, parts[0], npart, acc);
-        const double* src = e.d_t3;
-        double* dst = e.d_t1;
-        for (int q = 0; q < SPEC_SQUARINGS; ++q) {
-            hipLaunchKernelGGL(spec_square_kernel, dim3(nb16, nb16), dim3(DT), 0, s, n, src, (const double*)parts[q & 1], npart, dst,
-                               parts[(q & 1) ^ 1], acc);
-            src = dst;
-            dst = dst == e.d_t1 ? e.d_t2 : e.d_t1;
-        }
-        hipLaunchKernelGGL(spec_end_kernel, dim3(1), dim3(DT), 0, s, n, (const double*)parts[SPEC_SQUARINGS & 1], npart, (const double*)acc,
-                           mom, e.d_scal);
-        CESX_HIP(hipGetLastError());
-    }
-    if (fused_finish) {
-        if (e.fac.image_only) { e.err = "launch_dense: d_L does not hold the factor"; return CESX_ESTATE; }     // (ensure_factor above)
-        const int nwb = (int)(((long long)e.rpad * e.ktot + DT - 1) / DT), nvb = (p + DT / 64 - 1) / (DT / 64);
-        auto go = [&](auto tag, auto poll_tag) {
-            using T = decltype(tag);
-            constexpr bool POLLED = decltype(poll_tag)::value;
-            hipLaunchKernelGGL((finish_aldi_kernel<T, POLLED>), dim3(nwb + nvb), dim3(DT), 0, s, mv, prm, (const double*)e.d_part, e.d_scal, nwb,
-                               e.kp, e.kn, e.rpad, e.ktot, (const double*)e.d_M, (const double*)e.d_K, (const double*)e.d_L, potrf_ld(p),
-                               (const double*)e.d_y, (const double*)e.d_gbar, (const double*)e.d_mu,
-                               (const double*)e.d_ubar, (const double*)e.d_gw, mx, e.d_mv, (T*)e.d_W,
-                               (T*)e.d_bias, (T*)e.d_shiftT, e.d_shift64, (T*)e.d_rowc, (float*)e.d_Wf,
-                               (const unsigned long long*)(e.d_cholflag + 1), (unsigned long long)e.fac.seq);
-        };
-        auto pick = [&](auto tag) {
-            if (polled) go(tag, std::true_type{});
-            else go(tag, std::false_type{});
-        };
-        if (f32) pick(float{}); else pick(double{});
-        CESX_HIP(hipGetLastError());
-        return CESX_OK;
-    }
+    if (P.refactor && (rc = ensure_factor(e, s))) return rc;
+    if (P.gemm_M && (rc = gemm(e, s, p, p, p, 1.0, e.d_C, p, 1, e.d_Sinv, p, 1, e.d_M))) return rc;
+    if (P.spectral && (rc = launch_spectral(e, mom, s))) return rc;
+    if (P.route == DenseRoute::Finish) return f32 ? launch_finish<float>(e, L, polled) : launch_finish<double>(e, L, polled);
     auto scalars_and_matvecs = [&]() {
         hipLaunchKernelGGL(scalar_kernel, dim3(1 + (4 * p + DT / 64 - 1) / (DT / 64)), dim3(DT), 0, s, mv, prm,
                            e.d_part, e.d_scal, e.d_K, e.d_M, e.d_y, e.d_gbar, e.d_mu, e.d_ubar, mx, e.d_mv);
     };
     scalars_and_matvecs();
     CESX_HIP(hipGetLastError());
-
-    bool gain_inverse = false;
-    if (phase == 0 && (prm.time_step == CESX_TS_CONSTANT || (prm.time_step == CESX_TS_MIX && prm.update == CESX_UPDATE_ALDI))) {
+    if (P.gain_inverse) {
         // K' = C_ug (hk C_gg + Gamma)^{-1},  C_gg = See / N   (:440-441, :472-473)
         hipLaunchKernelGGL(axpb_kernel, g1((long long)n * n), dim3(256), 0, s, (long long)n * n, &e.d_scal->hk,
                            mom, e.d_See, e.d_Gamma, e.d_t3);
         CESX_HIP(hipGetLastError());
         const double* inv;
         if ((rc = spd_inverse(e, s, n, e.d_t3, &inv, 0, false))) return rc;
-        gain_inverse = true;
         if ((rc = gemm(e, s, p, n, n, 1.0, e.d_Cug, n, 1, inv, n, 1, e.d_Kp))) return rc;
         hipLaunchKernelGGL(select_kernel, g1((long long)p * n), dim3(256), 0, s, (long long)p * n, e.d_scal, e.d_Kp, e.d_K);
         CESX_HIP(hipGetLastError());
         scalars_and_matvecs();          // K y and K gbar with the selected gain (scalars are recomputed identically)
         CESX_HIP(hipGetLastError());
     }
-
-    int mode = 0;
-    if (phase == 1) mode = 2;
-    else if (prm.update == CESX_UPDATE_EKS) {
-        mode = 1;
+    if (P.eks_inverse) {
         // P = Sigma (Sigma + hk C)^{-1}  ( = (I + hk C Sigma^{-1})^{-1}, :443 )
         hipLaunchKernelGGL(axpb_kernel, g1((long long)p * p), dim3(256), 0, s, (long long)p * p, &e.d_scal->hk,
                            (const double*)nullptr, e.d_C, e.d_Sigma, e.d_t3);
         CESX_HIP(hipGetLastError());
         const double* inv;
-        if ((rc = spd_inverse(e, s, p, e.d_t3, &inv, 1, gain_inverse))) return rc;
+        if ((rc = spd_inverse(e, s, p, e.d_t3, &inv, 1, P.gain_inverse))) return rc;
         if (e.diag_sigma) {
             hipLaunchKernelGGL(scale_rows_kernel, g1((long long)p * p), dim3(256), 0, s, p, (const double*)e.d_Sigma, p + 1, inv, e.d_P);
             CESX_HIP(hipGetLastError());
@@ -2126,8 +2152,7 @@ int launch_dense(Engine& e, const cesx_step_params& prm, const double* mom, int 
         hipLaunchKernelGGL(matvec_kernel, g1(p, 4), dim3(DT), 0, s, p, p, e.d_P, e.d_mv + 5 * mx, e.d_mv + 4 * mx);
         CESX_HIP(hipGetLastError());
     }
-    const int ktot = mode == 2 ? e.kp + e.kn : e.ktot;
-    return f32 ? assemble<float>(e, s, mode, ktot, prm.switch_mult) : assemble<double>(e, s, mode, ktot, prm.switch_mult);
+    return f32 ? assemble<float>(e, s, P.mode, P.ktot, prm.switch_mult) : assemble<double>(e, s, P.mode, P.ktot, prm.switch_mult);
 }
 
 // U-only part of K2, started as soon as the U x U part of the moments is complete (and, on
@@ -2164,7 +2189,7 @@ int launch_chol_async(Engine& e, int update, const double* mom, hipStream_t s, b
     } else {
         // (few workgroups -> 1024 threads each: 8 x 256 threads took 25 us for the 65 k elements of C, latency bound)
         if ((rc = launch_center(e, e.side, dim3(std::min(NPB, e.center_u_wgs)), dim3(e.center_u_wgs < NPB ? 1024 : DT), mom,
-                                unbiased, 1, nullptr))) return rc;
+                                unbiased, CENTER_U, nullptr))) return rc;
     }
     // (whether THIS step is hk-free is decided in cesx_apply: expect what the last one was)
     if ((rc = factor_C(e, e.side, f, e.last_hkfree))) return rc;

@@ -27,7 +27,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_forward_lineal", "cesx_debug_dense", "cesx_profile_enable", "cesx_profile_read",
            "cesx_moments_uu_len", "cesx_moments_uu", "cesx_chol_async", "cesx_moments_rest", "cesx_side_stream",
            "cesx_prefetch_noise", "cesx_forward_set_lineal", "cesx_forward_apply", "cesx_moments_uu_chol", "cesx_debug_poll_recoveries", "cesx_comm_unique_id", "cesx_comm_init", "cesx_comm_destroy", "cesx_comm_nranks",
-           "cesx_comm_stats", "cesx_allreduce_head", "cesx_allreduce_tail", "cesx_allreduce_whole", "cesx_allreduce_sum", "cesx_allreduce_max", "cesx_moments_uu_handover", "cesx_debug_gram_plan",
+           "cesx_comm_stats", "cesx_allreduce_head", "cesx_allreduce_tail", "cesx_allreduce_whole", "cesx_allreduce_sum", "cesx_allreduce_max", "cesx_moments_uu_handover", "cesx_debug_gram_plan", "cesx_debug_dense_plan",
            "cesx_profile_clock", "cesx_calibrate_mfma", "cesx_profile_gap", "cesx_moments_rest_lineal", "cesx_copy_cols_async",
            "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count",
            "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats",
@@ -170,6 +170,7 @@ def load_library(path=None):
     lib.cesx_forward_apply.argtypes = [vp, vp, vp, vp]
     lib.cesx_debug_dense.argtypes = [vp, dp, dp, dp, dp, dp, dp]
     lib.cesx_debug_gram_plan.argtypes = [i32, i32, i32, i32, i32, C.c_longlong, C.POINTER(C.c_int)]
+    lib.cesx_debug_dense_plan.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.cesx_profile_enable.argtypes = [vp, i32]
     lib.cesx_profile_read.argtypes = [vp, i32, dp, C.POINTER(C.c_int)]
     lib.cesx_profile_clock.argtypes = [vp, dp]

@@ -530,6 +530,20 @@ int cesx_calibrate_mfma(cesx_handle h, double target_ms, double* tflops, double*
    blocks, busiest workgroup's tiles x blocks per SIMD, max staged row blocks, slabs}.  Needs no device. */
 int cesx_debug_gram_plan(int p, int n_obs, int dtype, int part, int wg_budget, long long J_local, int* info);
 
+/* Host-only introspection for tests: the K2 (dense algebra) the library runs for an engine state and a launch, both
+   given as facts[23] = {update, time_step, phase (0 step, 1 aldi_constant drift, 2 aldi_constant noise), an update
+   kernel takes the hk-free image, dtype, potrf_ld(p) <= 256, diagonal Sigma, chained image; hk-free allowed, LDS-DMA
+   update kernels, the image is allocated; of the last cesx_chol_async: in flight, centring fused into its load, L
+   into the image, signals, d_L left out; polled join allowed, sharded, the caller is on the side stream, the caller's
+   stream has a lower priority than the side stream; CESX_FUSE_CENTER=1, no CESX_FUSE_CENTER given, short second Gram
+   launch}.  plan[13] = {route (0 noise only, 1 tail, 2 finish, 3 general), tail arm (1 dense Sigma, 2 chained,
+   3 plain), join of the side stream (0 none, 1 event, 2 polled), U part (0 side stream, 1 centring launch, 2 fused
+   into the factorisation's load), centring parts (1 U | 2 G | 4 keep the status word), in-line factorisation (1 image,
+   2 fp64), re-factorisation of an image-only factor, M = C Sigma^{-1} GEMM, spectral block, gain inverse, EKS inverse,
+   assemble mode (0 aldi, 1 eks, 2 constant drift, 3 constant noise), its ktot for kp = 16, kn = 32, ktot = 64 (0: no
+   assemble launch)}.  Returns 0, < 0 on bad arguments.  Needs no handle and no device. */
+int cesx_debug_dense_plan(const int32_t* facts, int32_t* plan);
+
 /* Copies the engine's current small dense state to HOST buffers (any may be
    NULL): ubar (p), gbar (n), C (p x p), L = chol(C) (p x p), K (p x n),
    M = C Sigma^{-1} (p x p).  Synchronises.  After a step that kept L in its coefficient image only

@@ -17,7 +17,7 @@ carry it).
 
 Which kernel ran: cesx_debug_update_form tells the three ALDI forms apart and is asserted.  update2_kernel / update2s_kernel
 / update3_kernel / update3s_kernel / update_kernel and the Gram arms (gram2_kernel sg / imm, the v1 Gram) cannot be told
-apart from outside; ``pick`` below restates pick_update_kernel, update4_shape_ok, dense_hkfree and update2_lds /
+apart from outside; ``pick`` below restates pick_update_kernel, update4_shape_ok, plan_dense's tail route and update2_lds /
 update3_lds, the case tables carry the kernel the restatement names, and the shapes sit on both sides of every border so that
 the picker's source leaves no doubt; the Gram arm of a launch follows from its PLAN (``k1_launches``).  The measured worst
 ratios |err| / (eps B) are printed per part when the module ends (NOTEBOOK.md, "Calibrate: edges"); a record, not the bar."""
@@ -82,7 +82,7 @@ def k1_launches(c, cus=256):
 
 
 # ---- the pickers, restated (kernels_update.hip pick_update_kernel, kernels_update4.hip update4_shape_ok,
-#      kernels_dense.hip dense_hkfree / image_ok, kernels_update2.hip update2_lds, kernels_update3.hip update3_lds) ----------
+#      kernels_dense.hip plan_dense / image_ok, kernels_update2.hip update2_lds, kernels_update3.hip update3_lds) ----------
 
 U2_LDS_MAX, U3_LDS_MAX = 80 * 1024, 78 * 1024
 
