@@ -322,7 +322,10 @@ class sampling(enka):
         return self._device_update("aldi_constant", y_obs, U0, Geval, Gamma, **kwargs)
 
     def _device_loop_ok(self, model, save_online, kwargs):
+        # (a caller that replaced ``G_ens`` or an ``eks_update*`` hook on the instance -- the benchmark's Darcy leg times the
+        #  host map that way -- gets the plain loop, which calls them: the device loop would bypass both)
         return (getattr(model, "type", None) == "map" and hasattr(model, "forward_device") and not save_online
+                and "G_ens" not in self.__dict__ and not self._updates_overridden()
                 and (self.noise == "device" or kwargs.get("xis", None) is not None)
                 and kwargs.get("update", "aldi") in _engine.UPDATES
                 and kwargs.get("time_step", None) in _engine.TIME_STEPS and kwargs.get("time_step", None) != "adaptive"

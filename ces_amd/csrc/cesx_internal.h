@@ -509,6 +509,10 @@ struct Engine {
     double *d_gf_theta = nullptr, *d_gf_out = nullptr;                    // [n][ntheta], [n][2 + ntheta] of the evaluation in flight
     int *d_gf_idx = nullptr, *d_gf_status = nullptr;                      // [n]
     std::vector<double> h_gf_out;
+    // ---- Darcy forward map over the columns (cesx_darcy_*, kernels_darcy.hip); state of its own: the lineal map is untouched ----
+    int dc_K = 0;                                   // Nmesh of the installed map (0: none)
+    double *d_dc_mat = nullptr;                     // [4][K][K] coef (K folded in, entry 0 zero), D, S, R, row-major
+    int *d_dc_idx = nullptr;                        // [p] scatter, then [n] obs_index
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -786,6 +790,12 @@ int launch_gp_predict(Engine& e, const void* X, double* mean, double* var, bool 
 // counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double* mean, const double* var, void* U,
                     const double* logu, unsigned step, hipStream_t s);
+
+// kernels_darcy.hip: G = the installed Darcy map of the columns of U (engine dtype in and out, fp64 inside); status (J int32,
+// or nullptr): 0, the 1-based column of the zero pivot of a particle whose outputs are NaN, or minus the column that held a
+// non-finite entry.  darcy_prepare: once per installed map (the kernels' dynamic LDS limit for this K)
+int darcy_prepare(Engine& e, int K);
+int launch_darcy(Engine& e, const void* U, void* G, int* status, hipStream_t s);
 
 // kernels_gpfit.hip: lml, gradient and status of the GPs d_gf_idx[0 .. n_active) at d_gf_theta into d_gf_out
 int launch_gpfit_eval(Engine& e, int n_active, hipStream_t s);

@@ -363,7 +363,7 @@ void cesx_destroy(cesx_handle h) {
                     e.d_mh_W, e.d_mh_Wf, e.d_mh_Li, e.d_mh_Li_f, e.d_mh_lb, e.d_mh_w, e.d_mh_xi, e.d_mh_phi, e.d_mh_cnt,
                     e.d_gp_A, e.d_gp_c, e.d_gp_Z, e.d_gp_par, e.d_gp_mw, e.d_gp_alpha, e.d_gp_Li, e.d_gp_ws, e.d_gp_LSi,
                     e.d_gf_X, e.d_gf_Y, e.d_gf_Xs, e.d_gf_r, e.d_gf_t, e.d_gf_alpha, e.d_gf_A, e.d_gf_W, e.d_gf_Ki, e.d_gf_Ld, e.d_gf_part,
-                    e.d_gf_theta, e.d_gf_out, e.d_gf_idx, e.d_gf_status};
+                    e.d_gf_theta, e.d_gf_out, e.d_gf_idx, e.d_gf_status, e.d_dc_mat, e.d_dc_idx};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     for (GramPart& gp : e.gp) gram_part_free(gp);
@@ -1407,6 +1407,54 @@ int cesx_gpfit_factors(cesx_handle h, int i, double* alpha, double* Li) {
     for (size_t r = 0; r < Jt; ++r)                         // L^{-1} = W^T: the engine keeps the upper-triangular L^{-T}
         for (size_t c = 0; c < Jt; ++c) Li[r * Jt + c] = c <= r ? W[c * Jp + r] : 0.0;
     return CESX_OK;
+}
+
+// ---- Darcy forward map over the columns (ces_amd/darcy.py; kernels_darcy.hip) ----
+
+int cesx_darcy_set(cesx_handle h, const cesx_darcy_desc* d) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!d || d->struct_bytes != sizeof(cesx_darcy_desc)) { e.err = "cesx_darcy_set: bad cesx_darcy_desc"; return CESX_EINVAL; }
+    if (!d->coef || !d->scatter || !d->D || !d->S || !d->R || !d->obs_index) { e.err = "cesx_darcy_set: null pointer"; return CESX_EINVAL; }
+    if (d->K < 4) { e.err = "cesx_darcy_set: K < 4 (a not-a-knot spline needs four points)"; return CESX_EINVAL; }
+    if (d->K > 16) { e.err = "cesx_darcy_set: K > 16 (the working band of one particle no longer fits in LDS)"; return CESX_EINVAL; }
+    const int K = d->K, KK = K * K, p = e.p, n = e.n;
+    if (d->p != p || d->n_obs != n) { e.err = "cesx_darcy_set: p / n_obs differ from the handle's"; return CESX_EINVAL; }
+    if (p > KK) { e.err = "cesx_darcy_set: p exceeds K^2"; return CESX_EINVAL; }
+    std::vector<int> idx((size_t)p + n);
+    std::vector<char> seen((size_t)KK, 0);
+    for (int q = 0; q < p; ++q) {
+        const int s = d->scatter[q];
+        if (s < 0 || s >= KK || seen[s]) { e.err = "cesx_darcy_set: scatter index out of range or repeated"; return CESX_EINVAL; }
+        seen[s] = 1; idx[q] = s;
+    }
+    for (int k = 0; k < n; ++k) {
+        const int o = d->obs_index[k];
+        if (o < 0 || o >= KK) { e.err = "cesx_darcy_set: obs_index out of range"; return CESX_EINVAL; }
+        idx[(size_t)p + k] = o;
+    }
+    SET_DEVICE(e);
+    CESX_HIP(hipDeviceSynchronize());          // (the old image may be read by launches still in flight)
+    e.dc_K = 0;
+    TRY(darcy_prepare(e, K));
+    if (e.d_dc_mat) { CESX_HIP(hipFree(e.d_dc_mat)); e.d_dc_mat = nullptr; }
+    if (e.d_dc_idx) { CESX_HIP(hipFree(e.d_dc_idx)); e.d_dc_idx = nullptr; }
+    TRY(dmalloc(e, &e.d_dc_mat, (size_t)4 * KK * 8));
+    TRY(dmalloc(e, &e.d_dc_idx, idx.size() * 4));
+    const double* mats[4] = {d->coef, d->D, d->S, d->R};
+    for (int k = 0; k < 4; ++k) TRY(upload(e, e.d_dc_mat + (size_t)k * KK, mats[k], (size_t)KK * 8));
+    TRY(upload(e, e.d_dc_idx, idx.data(), idx.size() * 4));
+    e.dc_K = K;
+    return CESX_OK;
+}
+
+int cesx_darcy_apply(cesx_handle h, const void* U, void* G, int32_t* status, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U || !G) { e.err = "cesx_darcy_apply: null pointer"; return CESX_EINVAL; }
+    if (e.dc_K < 4) { e.err = "cesx_darcy_apply: cesx_darcy_set has not been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    return launch_darcy(e, U, G, status, (hipStream_t)stream);
 }
 
 }  // extern "C"

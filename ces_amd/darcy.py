@@ -19,12 +19,23 @@ restates their arithmetic:
 Same classes and call conventions as the reference (``model``, ``model_trunc``,
 ``set_initial``, ``set_rank``, ``eval_rf``, ``solve_pde``, ``obs_index``);
 ``start`` / ``stop`` / ``set_rnd_seed`` are kept as no-ops so that
-examples/scripts/darcy-flow.py:6-14 runs unchanged.  The forward map stays on
-the host (BASELINE.json north_star); only the ensemble update runs on the GPU.
+examples/scripts/darcy-flow.py:6-14 runs unchanged.
+
+``__call__`` evaluates the map on the host, one particle per call, as the
+reference does.  ``forward_device`` (build-only hook, Nmesh 4..16) evaluates the
+same map for every column of a device-resident ensemble in one launch
+(cesx_darcy_apply, ces_amd/csrc/kernels_darcy.hip): everything but the solve is a
+fixed linear operator or an elementwise ``exp``, so the host hands the engine the
+matrices once (``device_descriptor``) and the kernel runs KL synthesis, the two
+spline maps, the assembly and a banded LU with partial pivoting per particle, all
+in fp64.  With the hook ``sampling.run`` keeps a Darcy ensemble resident
+(``noise='device'`` or ``xis=``) and ``MCMC.model_mh(chains=M)`` runs; the
+default host flow is unchanged.
 
 PARITY UNPINNED: the MATLAB reference cannot run here, so there is no golden
 output; tests validate the restatement through the PDE itself (discrete
 residual, manufactured solution, symmetry) rather than against the reference.
+The device map is pinned to this host restatement, not to MATLAB.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -140,6 +151,76 @@ class model(object):
     def solve_pde(self, theta):
         return solve_gwf(theta)
 
+    # ---- build-only hook: the whole ensemble on the device (cesx_darcy_*) ----
+    DEVICE_NMESH = (4, 16)     # not-a-knot needs four points; beyond 16 one particle's working band no longer fits in LDS
+
+    def _device_scatter(self):
+        """The Nmesh^2 slot of the KL array each parameter lands on (``eval_rf``'s reshape: the identity)."""
+        return np.arange(int(self.p))
+
+    def device_descriptor(self, n_obs=None):
+        """What cesx_darcy_set takes (include/cesx.h), computed once in fp64 with this module's own calls:
+        ``coef`` (K, K) with the factor K folded in and the constant mode zeroed (gaussrnd_coarse), ``D`` with
+        ``idctn(L) == D @ L @ D.T``, ``S`` / ``R`` with ``_interp2_spline(centres, z, nodes) == S @ z @ S.T`` and
+        ``_interp2_spline(nodes, P, centres) == R @ P @ R.T``, ``scatter`` and ``obs_index``.
+        ``ValueError`` where only the host map ``model(xi)`` applies."""
+        host = "; evaluate the map on the host (model(xi), enka.G_ens) instead"
+        if getattr(self, "obs_index", None) is None:
+            raise ValueError("darcy forward_device: obs_index is not set" + host)
+        K = int(self.Nmesh)
+        if K != self.Nmesh or K < self.DEVICE_NMESH[0]:
+            raise ValueError("darcy forward_device: Nmesh = %r < 4 (or not an integer)" % (self.Nmesh,) + host)
+        if K > self.DEVICE_NMESH[1]:
+            raise ValueError("darcy forward_device: Nmesh = %d > 16 is not supported on the device" % K + host)
+        obs = np.asarray(self.obs_index).reshape(-1)
+        if n_obs is not None and obs.size != int(n_obs):
+            raise ValueError("darcy forward_device: len(obs_index) = %d differs from the engine's n_obs = %d" % (obs.size, n_obs)
+                             + host)
+        scatter = np.asarray(self._device_scatter()).reshape(-1)
+        if obs.size and (obs.min() < 0 or obs.max() >= K * K):
+            raise ValueError("darcy forward_device: obs_index out of range" + host)
+        k = np.arange(K)
+        K1, K2 = np.meshgrid(k, k)
+        coef = K * (self.tau ** (self.alpha - 1) * (np.pi ** 2 * (K1 ** 2 + K2 ** 2) + self.tau ** 2) ** (-self.alpha / 2))
+        coef[0, 0] = 0.0
+        eye = np.eye(K)
+        centres = np.arange(1, 2 * K, 2) / (2.0 * K)
+        nodes = np.linspace(0.0, 1.0, K)
+        return dict(K=K, coef=coef, scatter=scatter.astype(np.int32), D=idctn(eye, axes=[0], norm="ortho"),
+                    S=CubicSpline(centres, eye, axis=0, bc_type="not-a-knot", extrapolate=True)(nodes),
+                    R=CubicSpline(nodes, eye, axis=0, bc_type="not-a-knot", extrapolate=True)(centres),
+                    obs_index=obs.astype(np.int32))
+
+    def _fingerprint(self):
+        rank = getattr(self, "rank", None)
+        return (float(self.alpha), float(self.tau), float(self.Nmesh), int(self.p),
+                None if rank is None else np.asarray(rank).tobytes(),
+                None if getattr(self, "obs_index", None) is None else np.asarray(self.obs_index).tobytes())
+
+    def invalidate_device(self):
+        """Forget the map installed in an engine: the next ``forward_device`` builds and installs the descriptor again."""
+        self._dev_fp = None
+        self._dev_token = 0
+
+    def ensure_installed(self, engine):
+        """Make THIS map the Darcy map installed in ``engine``: installed once, again when alpha, tau, Nmesh, p, rank or
+        obs_index changed or another model installed its map on the same engine (``invalidate_device()`` forces it)."""
+        fp = self._fingerprint()
+        if (getattr(self, "_dev_fp", None) != fp
+                or getattr(engine, "_darcy_token", None) is not getattr(self, "_dev_token", 0)):
+            desc = self.device_descriptor(engine.n_obs)
+            if desc["scatter"].size != engine.p:
+                raise ValueError("darcy forward_device: the model's p = %d differs from the engine's p = %d"
+                                 % (desc["scatter"].size, engine.p))
+            self._dev_token = engine.darcy_set(desc)
+            self._dev_fp = fp
+
+    def forward_device(self, engine, U_dev, out=None):
+        """G (n_obs, J) = this map of the columns of the device tensor ``U_dev`` (p, J), on the device.
+        ``numpy.linalg.LinAlgError`` names the first particle whose system is exactly singular."""
+        self.ensure_installed(engine)
+        return engine.darcy_apply(U_dev, out=out)
+
 
 class model_trunc(model):
     """Rank-ordered truncated KL expansion (ces/darcy.py:100-138)."""
@@ -158,3 +239,6 @@ class model_trunc(model):
         full = np.zeros(int(self.Nmesh * self.Nmesh))
         full[self.rank[:self.p]] = np.copy(xi)
         return gaussrnd_coarse(full.reshape(int(self.Nmesh), -1), self.alpha, self.tau, self.Nmesh)
+
+    def _device_scatter(self):
+        return np.asarray(self.rank[:self.p])

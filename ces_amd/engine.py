@@ -18,7 +18,7 @@ OK, EINVAL, ENOTPD, EHIP, ESTATE, EUNSUPPORTED, ENOCONV = 0, 1, 2, 3, 4, 5, 6
 F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
-ABI_VERSION = 2
+ABI_VERSION = 3
 MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
@@ -32,7 +32,8 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count",
            "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats",
            "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept",
-           "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors")
+           "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
+           "cesx_darcy_set", "cesx_darcy_apply")
 GPFIT_MEANS = {"zero": 0, "constant": 1, "linear": 2}   # CESX_GPFIT_MEAN_*
 GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
 
@@ -66,6 +67,12 @@ class GpDesc(C.Structure):
 class GpFitDesc(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("n_gp", C.c_int32), ("J_t", C.c_int32), ("family", C.c_int32),
                 ("ard", C.c_int32), ("mean", C.c_int32), ("X", C.c_void_p), ("Y", C.c_void_p)]
+
+
+class DarcyDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("K", C.c_int32), ("p", C.c_int32), ("n_obs", C.c_int32),
+                ("coef", C.c_void_p), ("scatter", C.c_void_p), ("D", C.c_void_p), ("S", C.c_void_p), ("R", C.c_void_p),
+                ("obs_index", C.c_void_p)]
 
 
 class CesxError(RuntimeError):
@@ -190,6 +197,8 @@ def load_library(path=None):
     lib.cesx_gpfit_ntheta.argtypes = [vp]
     lib.cesx_gpfit_eval.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     lib.cesx_gpfit_factors.argtypes = [vp, i32, vp, vp]
+    lib.cesx_darcy_set.argtypes = [vp, C.POINTER(DarcyDesc)]
+    lib.cesx_darcy_apply.argtypes = [vp, vp, vp, vp, vp]
     if lib.cesx_abi_version() != ABI_VERSION:
         raise ImportError("libcesx.so ABI %d != binding ABI %d" % (lib.cesx_abi_version(), ABI_VERSION))
     if path == LIB_PATH:
@@ -943,6 +952,47 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(self.lib.cesx_gpfit_factors(self._h, int(i), alpha.ctypes.data, Li.ctypes.data))
         return alpha, Li
+
+    # -- Darcy forward map over the columns (include/cesx.h, cesx_darcy_*; ces_amd/darcy.py builds the descriptor) --
+    def darcy_set(self, desc):
+        """Install a Darcy map: ``desc`` as ``ces_amd.darcy.model.device_descriptor`` returns it (cesx_darcy_set; the engine
+        keeps its own copy).  Returns the token that identifies the installed map."""
+        K = int(desc["K"])
+        mats = {k: np.ascontiguousarray(np.asarray(desc[k], dtype=np.float64)) for k in ("coef", "D", "S", "R")}
+        for k, a in mats.items():
+            if a.shape != (K, K):
+                raise ValueError("darcy_set: %s has shape %s, expected %s" % (k, a.shape, (K, K)))
+        scatter = np.ascontiguousarray(np.asarray(desc["scatter"], dtype=np.int32).reshape(-1))
+        obs = np.ascontiguousarray(np.asarray(desc["obs_index"], dtype=np.int32).reshape(-1))
+        d = DarcyDesc(C.sizeof(DarcyDesc), K, scatter.size, obs.size, mats["coef"].ctypes.data, scatter.ctypes.data,
+                      mats["D"].ctypes.data, mats["S"].ctypes.data, mats["R"].ctypes.data, obs.ctypes.data)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_darcy_set(self._h, C.byref(d)))
+        self._darcy_token = object()
+        return self._darcy_token
+
+    def darcy_apply(self, U, out=None):
+        """G (n_obs, J) = the installed Darcy map of the columns of U (cesx_darcy_apply).  Raises ``numpy.linalg.LinAlgError``
+        naming the first particle whose system is exactly singular, or whose system left fp64's range (exp(theta) overflowed) --
+        the outputs of such a particle are NaN; the host map's ``spsolve`` warns and returns NaN or inf there.  Reads the
+        per-particle status words: synchronises."""
+        out = self.empty(self.n_obs) if out is None else out
+        status = self.__dict__.get("_darcy_status")
+        if status is None:
+            status = self._darcy_status = torch.empty(self.J, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_darcy_apply(self._h, U.data_ptr(), out.data_ptr(), status.data_ptr(), self._stream()))
+            self._keep_darcy = (U, out)
+            bad = torch.nonzero(status).reshape(-1)
+            if bad.numel():
+                j = int(bad[0])
+                st = int(status[j])
+                if st > 0:
+                    raise np.linalg.LinAlgError("Darcy forward map: the system of particle %d is singular (zero pivot in "
+                                                "column %d)" % (j, st - 1))
+                raise np.linalg.LinAlgError("Darcy forward map: the system of particle %d is not finite (NaN or inf in column "
+                                            "%d: exp(theta) overflowed?)" % (j, -st - 1))
+        return out
 
     def profile_enable(self, on=True):
         """on: False / True, 2 = bind only the events cesx_profile_gap needs, 3 / 4 = the update / the moments

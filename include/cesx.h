@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CESX_ABI_VERSION 2
+#define CESX_ABI_VERSION 3
 
 /* status codes */
 #define CESX_OK            0
@@ -368,6 +368,39 @@ int cesx_forward_lineal(cesx_handle h, const void* A_dev, const void* b_dev,
    may be freed or changed afterwards (call set again to change the map). */
 int cesx_forward_set_lineal(cesx_handle h, const void* A_dev, const void* b_dev, void* stream);
 int cesx_forward_apply(cesx_handle h, const void* U_dev, void* G_dev, void* stream);
+
+/* ---- forward-map hook: the Darcy flow map of the reference's example (ces/darcy.py and its MATLAB files) ----
+   The map of examples/scripts/darcy-flow.py for every column of U at once instead of one MATLAB call per particle
+   (ces/calibrate.py:123-130).  For one particle xi (p values), K = Nmesh, m = K - 2:
+       L     = coef o Xi, Xi the K x K (row-major) array with Xi[scatter[q]] = xi[q] and zeros elsewhere, L[0][0] = 0
+       theta = D L D^T                 (gaussrnd_coarse.m:6-23: D the orthonormal inverse DCT-II matrix, MATLAB's idct2)
+       a     = S exp(theta) S^T        (solve_gwf.m: interp2 'spline' from the cell centres to the K x K nodes)
+       A x   = 1                       (5-point operator, arithmetic-mean face coefficients, scaled by (K-1)^2, the m^2 interior
+                                        unknowns column by column; half-bandwidth m)
+       g_k   = (R' X R'^T)[obs_index[k]],  R' = R[:, 1:-1], X = x as m x m column-major, the K x K centres flattened row-major
+   The solve is a banded LU with partial (row) pivoting (LAPACK gbtf2 / gbtrs): the spline of exp(theta) overshoots below zero
+   on ordinary inputs and A is then symmetric indefinite.  ALL arithmetic is fp64 whatever the engine dtype, which governs only
+   how U_dev is read and G_dev written; every sum runs in a fixed order: two calls are bit-identical.
+   These entry points keep state of their own: the linear map of cesx_forward_set_lineal is untouched. */
+typedef struct {
+    uint32_t struct_bytes;    /* sizeof(cesx_darcy_desc) */
+    int32_t K;                /* Nmesh, 4 <= K <= 16 (a not-a-knot spline needs four points; one particle's band must fit in LDS) */
+    int32_t p, n_obs;         /* must equal the handle's p and n_obs; p <= K^2 */
+    const double* coef;       /* [K][K] KL coefficients, ALREADY multiplied by K and with entry [0][0] zeroed */
+    const int32_t* scatter;   /* [p] the K^2 slot each parameter lands on, distinct (identity: darcy.model; rank[:p]: model_trunc) */
+    const double* D;          /* [K][K] row-major */
+    const double* S;          /* [K][K] centres -> nodes spline matrix */
+    const double* R;          /* [K][K] nodes -> centres spline matrix */
+    const int32_t* obs_index; /* [n_obs] picked centres, each in [0, K^2) */
+} cesx_darcy_desc;
+/* Copies the map (host fp64) into engine-owned memory; replaces an earlier one.  CESX_EINVAL (text in cesx_last_error) for
+   K < 4, K > 16, a size mismatch, an index out of range or a repeated scatter index; the installed map is kept then. */
+int cesx_darcy_set(cesx_handle h, const cesx_darcy_desc* desc);
+/* G_dev (n_obs x J_local) = the installed map of the columns of U_dev (p x J_local), both in the engine dtype.  status_dev
+   (J_local int32 on the device, or NULL): 0; or c > 0 -- the pivot of column c (1-based) of that particle was exactly zero, its
+   system is singular --; or -c -- column c held a NaN or an infinity when its pivot was sought (exp(theta) overflowed: nothing
+   is singular, the input left fp64's range).  The outputs of such a particle are NaN, the other particles are unaffected. */
+int cesx_darcy_apply(cesx_handle h, const void* U_dev, void* G_dev, int32_t* status_dev, void* stream);
 
 /* ---- Sample: Metropolis-Hastings over the columns (ces/sample.py) -------
    MCMC.model_mh (ces/sample.py:121-196) runs ONE host chain; here every column of the handle's (p, J_local) layout is an
