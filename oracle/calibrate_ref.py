@@ -292,6 +292,21 @@ def dense_ref(mom, shift, prob, update, time_step=None, delta_t=None, spinup=4.0
     return out
 
 
+def dense_from_inputs(U, G, prob, update, dtype, **ts):
+    """K2 from a step's OWN inputs (no device buffer in it): the fp64 moments of U and G -- with a dense Gamma of the whitened
+    rows L_Gamma^{-1} G -- about the dtype-rounded row means, through ``dense_ref``.  ubar, gbar, C, K, M and the scalars do not
+    depend on the shift in exact arithmetic, so any engine shift (recomputed or predicted) is held to the same reference; what
+    separates a device from it is the Gram rounding of the engine dtype (tests/reuse_cases.py: BAND for an fp64
+    engine, the project's fp32 bar for an fp32 one).  ts: the keywords of ``dense_ref``."""
+    U, G = np.asarray(U, dtype=np.float64), np.asarray(G, dtype=np.float64)
+    p, J = U.shape
+    Lg, Li = whitening(prob["Gamma"])
+    Gw = G if Lg is None else Li @ G
+    shift = round_shift(np.concatenate([[float(J)], U.sum(axis=1), Gw.sum(axis=1)]), dtype)
+    mom, _ = moments_ref(U, Gw, shift[:p], shift[p:])
+    return dense_ref(mom, shift, prob, update, **ts)
+
+
 # ---- K3 -------------------------------------------------------------------------------------------------------------------
 
 FORMS = ("assembled", "hkfree", "chained", "eks", "drift", "finish")
