@@ -323,8 +323,13 @@ class sampling(enka):
 
     def _device_loop_ok(self, model, save_online, kwargs):
         # (a caller that replaced ``G_ens`` or an ``eks_update*`` hook on the instance -- the benchmark's Darcy leg times the
-        #  host map that way -- gets the plain loop, which calls them: the device loop would bypass both)
-        return (getattr(model, "type", None) == "map" and hasattr(model, "forward_device") and not save_online
+        #  host map that way -- gets the plain loop, which calls them: the device loop would bypass both;
+        #  a ``type == 'pde'`` model qualifies with its own hook, ``forward_pde_device`` (lorenz96.set_solver(device=True)),
+        #  unless the start states are drawn from a ``ws`` library: that draw uses the host's global RNG once per iteration)
+        kind = getattr(model, "type", None)
+        hook = ((kind == "map" and hasattr(model, "forward_device"))
+                or (kind == "pde" and hasattr(model, "forward_pde_device") and kwargs.get("ws", None) is None))
+        return (hook and not save_online
                 and "G_ens" not in self.__dict__ and not self._updates_overridden()
                 and (self.noise == "device" or kwargs.get("xis", None) is not None)
                 and kwargs.get("update", "aldi") in _engine.UPDATES
@@ -347,25 +352,54 @@ class sampling(enka):
         self.update_rule = {"eks": "eks_update", "aldi": "eks_update_linear", "aldi_constant": "eks_update_aldi"}[rule]
         prm0 = _engine.step_params(update=rule, T=self.T)
         U = eng.to_device(U0, self.p, "U")
-        G = model.forward_device(eng, U)
+        pde = getattr(model, "type", None) == "pde"
+        if pde:
+            # ces/calibrate.py:342-350 with the carried states W (n_state, J, fp64) resident: every evaluation starts from
+            # ``carry["W"]`` and writes a W_out of its own; ``update_wt`` (default) makes that the next start.  A redo
+            # (``out=``) repeats the LAST evaluation: the same start, into the same G and W_out.
+            import torch
+            t_pde = kwargs.get("t", None)
+            carry = {"W": torch.as_tensor(np.ascontiguousarray(self.W0, dtype=np.float64), device=eng.device), "last": None}
+            update_wt = kwargs.get("update_wt", True)
+
+            def fwd(u, out=None):
+                if out is None:
+                    W_in = carry["W"]
+                    g, W_out = model.forward_pde_device(eng, u, W_in, t_pde)
+                    carry["last"] = (W_in, W_out)
+                    if update_wt:
+                        carry["W"] = W_out
+                    return g
+                W_in, W_out = carry["last"]
+                model.forward_pde_device(eng, u, W_in, t_pde, out=out, W_out=W_out)
+                return out
+            evaluate = fwd
+
+            def g_host(g):                    # what G_pde_ens returns: the statistics over the carried end states (:358)
+                return np.vstack([eng.to_host(g), carry["last"][1].cpu().numpy()])
+        else:
+            from .utils import hook_takes_out
+            takes_out = hook_takes_out(model.forward_device)
+
+            def fwd(u, out=None):             # (``out``: a redo after a re-run step refreshes G in place, ShardedUpdate.result)
+                if out is None:
+                    return model.forward_device(eng, u)
+                if takes_out:
+                    return model.forward_device(eng, u, out=out)
+                out.copy_(model.forward_device(eng, u))          # a hook without ``out=``
+                return out
+
+            def evaluate(u):
+                return model.forward_device(eng, u)
+            g_host = eng.to_host
+        G = evaluate(U)
         sh.begin(prm0, U, G, recenter=True, noise_step=None if xis is not None else self._step_counter)
         fast = sh.lineal_fast_ok(model)       # linear map on the device: G's moments follow from U's (no second Gram launch)
         G_next = None
-
-        from .utils import hook_takes_out
-        takes_out = hook_takes_out(model.forward_device)
-
-        def fwd(u, out=None):                 # (``out``: a redo after a re-run step refreshes G in place, ShardedUpdate.result)
-            if out is None:
-                return model.forward_device(eng, u)
-            if takes_out:
-                return model.forward_device(eng, u, out=out)
-            out.copy_(model.forward_device(eng, u))          # a hook without ``out=``
-            return out
         for i in range(self.T):
             if trace and (i % stride == 0):                        # :356-358 (a copy: the device buffers are reused)
                 self.Uall.append(U0 if i == 0 and isinstance(U0, np.ndarray) else eng.to_host(U))
-                self.Gall.append(eng.to_host(G))
+                self.Gall.append(g_host(G))
             t = self.metrics["t"]
             first = len(t) == 0                                    # = len(self.Uall) == 1 of :262 / :520 on a full trace
             prm = _engine.step_params(update=rule, time_step=kwargs.get("time_step", None), first_step=first,
@@ -381,7 +415,7 @@ class sampling(enka):
                 if fast:
                     _, G_next = sh.begin_lineal(prm0, U_new, fwd, noise_step=ns, model=model)
                 else:
-                    G_next = model.forward_device(eng, U_new)
+                    G_next = evaluate(U_new)
                     sh.begin(prm0, U_new, G_next, noise_step=ns, forward=fwd)
             res = sh.result()
             self._append_result(rule, res, kwargs)
@@ -389,9 +423,11 @@ class sampling(enka):
             if self.metrics["t"][-1] > kwargs.get("t_tol", 2.0):   # :387-388
                 break
         if G is None:                                              # :390-398 one more evaluation of the final ensemble
-            G = model.forward_device(eng, U)
+            G = evaluate(U)
         self.Ustar = eng.to_host(U)
-        Gfinal = eng.to_host(G)
+        Gfinal = g_host(G)
+        if pde:                                                    # :396 (a host array, as the plain loop leaves it)
+            self.W0 = carry["W"].cpu().numpy()
         if trace:                                                  # :400-405
             self.Uall.append(self.Ustar)
             self.Gall.append(Gfinal)

@@ -513,6 +513,9 @@ struct Engine {
     int dc_K = 0;                                   // Nmesh of the installed map (0: none)
     double *d_dc_mat = nullptr;                     // [4][K][K] coef (K folded in, entry 0 zero), D, S, R, row-major
     int *d_dc_idx = nullptr;                        // [p] scatter, then [n] obs_index
+    // ---- Lorenz '96 forward map over the columns (cesx_lorenz_*, kernels_l96.hip); state of its own, as the Darcy map's ----
+    cesx_l96_desc l9{};                             // the installed descriptor (n_slow 0: none; its t points nowhere: d_l9_t)
+    double *d_l9_t = nullptr;                       // [n_t] the sample times
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -796,6 +799,11 @@ int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double
 // non-finite entry.  darcy_prepare: once per installed map (the kernels' dynamic LDS limit for this K)
 int darcy_prepare(Engine& e, int K);
 int launch_darcy(Engine& e, const void* U, void* G, int* status, hipStream_t s);
+
+// kernels_l96.hip: per column, RK45 of the installed two-scale Lorenz '96 model from W_in (n_state x J fp64) with the
+// parameters the descriptor's map takes from U; G = the last window's statistics (engine dtype), W_out = the state at t[-1]
+// (may be W_in), info ([4][J] int32 or nullptr) = status, accepted steps, attempted steps, 0
+int launch_l96(Engine& e, const void* U, const double* W_in, void* G, double* W_out, int* info, hipStream_t s);
 
 // kernels_gpfit.hip: lml, gradient and status of the GPs d_gf_idx[0 .. n_active) at d_gf_theta into d_gf_out
 int launch_gpfit_eval(Engine& e, int n_active, hipStream_t s);

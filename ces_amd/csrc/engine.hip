@@ -363,7 +363,7 @@ void cesx_destroy(cesx_handle h) {
                     e.d_mh_W, e.d_mh_Wf, e.d_mh_Li, e.d_mh_Li_f, e.d_mh_lb, e.d_mh_w, e.d_mh_xi, e.d_mh_phi, e.d_mh_cnt,
                     e.d_gp_A, e.d_gp_c, e.d_gp_Z, e.d_gp_par, e.d_gp_mw, e.d_gp_alpha, e.d_gp_Li, e.d_gp_ws, e.d_gp_LSi,
                     e.d_gf_X, e.d_gf_Y, e.d_gf_Xs, e.d_gf_r, e.d_gf_t, e.d_gf_alpha, e.d_gf_A, e.d_gf_W, e.d_gf_Ki, e.d_gf_Ld, e.d_gf_part,
-                    e.d_gf_theta, e.d_gf_out, e.d_gf_idx, e.d_gf_status, e.d_dc_mat, e.d_dc_idx};
+                    e.d_gf_theta, e.d_gf_out, e.d_gf_idx, e.d_gf_status, e.d_dc_mat, e.d_dc_idx, e.d_l9_t};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     for (GramPart& gp : e.gp) gram_part_free(gp);
@@ -1455,6 +1455,61 @@ int cesx_darcy_apply(cesx_handle h, const void* U, void* G, int32_t* status, voi
     if (e.dc_K < 4) { e.err = "cesx_darcy_apply: cesx_darcy_set has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     return launch_darcy(e, U, G, status, (hipStream_t)stream);
+}
+
+// ---- Lorenz '96 forward map over the columns (ces_amd/models.py; kernels_l96.hip) ----
+
+int cesx_lorenz_set(cesx_handle h, const cesx_l96_desc* d) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!d || d->struct_bytes != sizeof(cesx_l96_desc)) { e.err = "cesx_lorenz_set: bad cesx_l96_desc"; return CESX_EINVAL; }
+    if (d->n_slow < 4) { e.err = "cesx_lorenz_set: n_slow < 4 (the slow tendencies reach from k - 2 to k + 1)"; return CESX_EINVAL; }
+    if (d->n_fast < 1) { e.err = "cesx_lorenz_set: n_fast < 1"; return CESX_EINVAL; }
+    if ((long long)d->n_slow * ((long long)d->n_fast + 1) > 448) { e.err = "cesx_lorenz_set: n_state = n_slow (n_fast + 1) > 448"; return CESX_EINVAL; }
+    if (d->p != e.p || d->n_obs != e.n) { e.err = "cesx_lorenz_set: p / n_obs differ from the handle's"; return CESX_EINVAL; }
+    if (d->stat_mode < 0 || d->stat_mode > 2) { e.err = "cesx_lorenz_set: stat_mode is not 0, 1 or 2"; return CESX_EINVAL; }
+    if (d->n_obs != (d->stat_mode == 0 ? 5 * d->n_slow : 5)) { e.err = "cesx_lorenz_set: n_obs is not 5 n_slow (stat_mode 0) / 5 (stat_mode 1, 2)"; return CESX_EINVAL; }
+    if (d->stat_mode == 2 && d->n_slow < 8) { e.err = "cesx_lorenz_set: stat_mode 2 reads slow index 7, n_slow < 8"; return CESX_EINVAL; }
+    for (int k = 0; k < 4; ++k) {
+        if (d->par_row[k] < -1 || d->par_row[k] >= e.p) { e.err = "cesx_lorenz_set: par_row out of range"; return CESX_EINVAL; }
+        for (int m = 0; m < k; ++m)
+            if (d->par_row[k] >= 0 && d->par_row[k] == d->par_row[m]) { e.err = "cesx_lorenz_set: par_row repeated"; return CESX_EINVAL; }
+        if (d->par_row[k] < 0 && !std::isfinite(d->par_fixed[k])) { e.err = "cesx_lorenz_set: a fixed parameter is not finite"; return CESX_EINVAL; }
+    }
+    if (!(d->T > 0.0) || !(d->max_step > 0.0) || !(d->rtol > 0.0) || !(d->atol > 0.0) || !std::isfinite(d->T) || !std::isfinite(d->rtol)
+        || !std::isfinite(d->atol)) {
+        e.err = "cesx_lorenz_set: T, max_step, rtol and atol must be positive"; return CESX_EINVAL;
+    }
+    if (d->n_t < 2 || !d->t) { e.err = "cesx_lorenz_set: no sample times"; return CESX_EINVAL; }
+    for (int k = 0; k < d->n_t; ++k)
+        if (!(d->t[k] >= 0.0 && d->t[k] <= d->T) || (k && d->t[k] < d->t[k - 1])) {
+            e.err = "cesx_lorenz_set: t is not non-decreasing within [0, T]"; return CESX_EINVAL;
+        }
+    if (d->spinup_samples < 0 || d->window_samples < 1 || d->n_t - 1 - d->spinup_samples < d->window_samples
+        || (d->n_t - 1 - d->spinup_samples) % d->window_samples != 0) {
+        e.err = "cesx_lorenz_set: n_t - 1 - spinup_samples is not a positive multiple of window_samples"; return CESX_EINVAL;
+    }
+    if (d->max_attempts < 1) { e.err = "cesx_lorenz_set: max_attempts < 1"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    CESX_HIP(hipDeviceSynchronize());          // (the old sample times may be read by launches still in flight)
+    double* tnew = nullptr;
+    TRY(dmalloc(e, &tnew, (size_t)d->n_t * 8));
+    if (int rc = upload(e, tnew, d->t, (size_t)d->n_t * 8)) { (void)hipFree(tnew); return rc; }
+    if (e.d_l9_t) (void)hipFree(e.d_l9_t);
+    e.d_l9_t = tnew;
+    e.l9 = *d;
+    e.l9.t = nullptr;
+    return CESX_OK;
+}
+
+int cesx_lorenz_apply(cesx_handle h, const void* U, const double* W_in, void* G, double* W_out, int32_t* info, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U || !W_in || !G || !W_out) { e.err = "cesx_lorenz_apply: null pointer"; return CESX_EINVAL; }
+    if (G == U) { e.err = "cesx_lorenz_apply: G must not alias U"; return CESX_EINVAL; }
+    if (e.l9.n_slow < 4) { e.err = "cesx_lorenz_apply: cesx_lorenz_set has not been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    return launch_l96(e, U, W_in, G, W_out, info, (hipStream_t)stream);
 }
 
 }  // extern "C"

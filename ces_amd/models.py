@@ -4,8 +4,9 @@
 ``type == 'map'`` (one call per particle, ces/utils.py:5-122) and ``type ==
 'pde'`` (an ODE solved per particle from a carried state, then summarised into
 observables: ces/calibrate.py:132-168 and ces/utils.py:124-455).  These are host
-code in the reference and stay host code here (BASELINE.json north_star); only
-the ensemble update runs on the GPU.  The classes keep the reference's names,
+code in the reference and the default here (BASELINE.json north_star); the
+two-scale Lorenz '96 family also offers the whole ensemble on the device
+(``set_solver(device=True)`` -> ``forward_pde_device``, cesx_lorenz_*).  The classes keep the reference's names,
 attributes, call conventions and default arguments so that its notebooks
 (examples/notebooks/{linear,lorenz63}.ipynb) run against ``ces_amd.calibrate``
 unchanged; the right-hand sides are written in vectorised numpy rather than
@@ -136,9 +137,18 @@ class lorenz96(object):
         x = np.random.rand(self.n_slow) * 15 - 5
         return np.concatenate([x, np.repeat(x, self.n_fast)])
 
-    def set_solver(self, method="RK45", T=20, dt=0.1):
+    def set_solver(self, method="RK45", T=20, dt=0.1, device=False):
+        """``device=True`` (build-only): the model also offers ``forward_pde_device``, the whole ensemble integrated on the
+        device (cesx_lorenz_*, ces_amd/csrc/kernels_l96.hip: scipy's RK45 restated, one wave per particle).  ``solve`` and
+        ``statistics`` stay the host path either way."""
+        if device and method != "RK45":
+            raise ValueError("lorenz96.set_solver: device=True integrates with RK45 only, not %r" % (method,))
         self.method, self.dt, self.T = method, dt, T
         self.solve_init = True
+        if device:
+            self.forward_pde_device = self._forward_pde_device
+        else:
+            self.__dict__.pop("forward_pde_device", None)
 
     def solve(self, w0, t, args=()):
         from scipy import integrate
@@ -163,6 +173,100 @@ class lorenz96(object):
     def statistics(self, ws):
         return self._phi(ws)[:, -1]
 
+    # ---- build-only hook: the whole ensemble on the device (cesx_lorenz_*) ----
+    DEVICE_PAR_ROW = (0, 1, 2, 3)                      # the row of U each of (h, F, log c, b) is read from, or -1 ...
+    DEVICE_PAR_FIXED = (0.0, 0.0, 0.0, 0.0)            # ... and its fixed value (the subclasses' ``__call__`` defaults)
+    DEVICE_MAX_STATE = 448
+    DEVICE_RTOL, DEVICE_ATOL = 1e-3, 1e-6              # solve_ivp's defaults: ``solve`` passes neither
+    device_max_attempts = 1000000                      # attempted steps after which a particle ends with status 3
+
+    def _device_stat_mode(self):
+        return 0
+
+    def device_descriptor(self, t, p=None, n_obs=None):
+        """What cesx_lorenz_set takes (include/cesx.h), as a dict built in numpy.  ``ValueError`` with the reason wherever
+        only the host path (``solve`` + ``statistics``, enka.G_pde_ens) applies."""
+        host = "; integrate on the host (model.solve, enka.G_pde_ens) instead"
+        if "forward_pde_device" not in self.__dict__:
+            raise ValueError("lorenz96 forward_pde_device: set_solver(device=True) has not been called" + host)
+        if self.method != "RK45":
+            raise ValueError("lorenz96 forward_pde_device: method %r is not RK45" % (self.method,) + host)
+        if t is None:
+            raise ValueError("lorenz96 forward_pde_device: no sample times t" + host)
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        n_slow, n_fast = int(self.n_slow), int(self.n_fast)
+        if n_slow != self.n_slow or n_fast != self.n_fast or n_slow < 4 or n_fast < 1:
+            raise ValueError("lorenz96 forward_pde_device: n_slow = %r < 4 or n_fast = %r < 1" % (self.n_slow, self.n_fast) + host)
+        if n_slow * (n_fast + 1) > self.DEVICE_MAX_STATE:
+            raise ValueError("lorenz96 forward_pde_device: n_state = %d > %d is not supported on the device"
+                             % (n_slow * (n_fast + 1), self.DEVICE_MAX_STATE) + host)
+        mode = self._device_stat_mode()
+        if mode == 2 and n_slow < 8:
+            raise ValueError("lorenz96 forward_pde_device: hom = False reads slow index 7, n_slow = %d" % n_slow + host)
+        mine = 5 * n_slow if mode == 0 else 5
+        if n_obs is not None and int(n_obs) != mine:
+            raise ValueError("lorenz96 forward_pde_device: the model's n_obs = %d differs from the engine's n_obs = %d"
+                             % (mine, n_obs) + host)
+        if p is not None and int(p) != self.n_params:
+            raise ValueError("lorenz96 forward_pde_device: the model's p = %d differs from the engine's p = %d"
+                             % (self.n_params, p) + host)
+        T, dt = float(self.T), float(self.dt)
+        if not (T > 0 and np.isfinite(T)) or not dt > 0:
+            raise ValueError("lorenz96 forward_pde_device: T = %r and dt = %r must be positive" % (self.T, self.dt) + host)
+        if t.size < 2 or not np.all(np.isfinite(t)) or np.any(np.diff(t) <= 0) or t[0] < 0 or t[-1] > T:
+            # (solve_ivp: "Values in t_eval are not within t_span" / "not properly sorted")
+            raise ValueError("lorenz96 forward_pde_device: t must increase within [0, T = %g]" % T + host)
+        spin, win = int(self.spinup * self.freq), int(self.l_window * self.freq)
+        if spin != self.spinup * self.freq or win != self.l_window * self.freq or spin < 0 or win < 1:
+            raise ValueError("lorenz96 forward_pde_device: spinup * freq and l_window * freq must be whole sample counts" + host)
+        rest = t.size - 1 - spin
+        if rest < win or rest % win:
+            # (the reshape of ``_phi`` raises there)
+            raise ValueError("lorenz96 forward_pde_device: the %d samples after the spin-up do not fill whole windows of %d"
+                             % (rest, win) + host)
+        return dict(n_slow=n_slow, n_fast=n_fast, n_obs=mine, p=int(self.n_params), stat_mode=mode,
+                    par_row=np.asarray(self.DEVICE_PAR_ROW, dtype=np.int32),
+                    par_fixed=np.asarray(self.DEVICE_PAR_FIXED, dtype=np.float64),
+                    T=T, max_step=dt, rtol=self.DEVICE_RTOL, atol=self.DEVICE_ATOL, t=t,
+                    spinup_samples=spin, window_samples=win, max_attempts=int(self.device_max_attempts))
+
+    def _fingerprint(self, t):
+        return (type(self).__name__, int(self.n_slow), int(self.n_fast), int(self.n_params), self._device_stat_mode(),
+                tuple(self.DEVICE_PAR_ROW), tuple(float(v) for v in self.DEVICE_PAR_FIXED), float(self.T), float(self.dt),
+                self.method, float(self.spinup), float(self.l_window), float(self.freq), int(self.device_max_attempts),
+                np.asarray(t, dtype=np.float64).tobytes())
+
+    def invalidate_device(self):
+        """Forget the map installed in an engine: the next ``forward_pde_device`` builds and installs the descriptor again."""
+        self._dev_fp = None
+        self._dev_token = 0
+
+    def ensure_installed(self, engine, t):
+        """Make THIS model the Lorenz '96 map installed in ``engine``: installed once, again when any field of the descriptor
+        changed or another model installed its own on the same engine (``invalidate_device()`` forces it)."""
+        fp = self._fingerprint(t)
+        if (getattr(self, "_dev_fp", None) != fp
+                or getattr(engine, "_l96_token", None) is not getattr(self, "_dev_token", 0)):
+            desc = self.device_descriptor(t, engine.p, engine.n_obs)
+            self._dev_token = engine.l96_set(desc)
+            self._dev_fp = fp
+
+    def _forward_pde_device(self, engine, U_dev, W_dev, t, out=None, W_out=None):
+        """(G (n_obs, J), W_next (n_state, J) fp64) on the device: every column of ``U_dev`` integrated from its column of
+        ``W_dev`` over ``t`` (what enka.G_pde does per particle).  ``ValueError`` names the first particle that failed --
+        the exception the host path ends in (``statistics``' reshape of a truncated solution).  Reads the status words:
+        synchronises."""
+        self.ensure_installed(engine, t)
+        G, W_next, info = engine.l96_apply(U_dev, W_dev, out=out, W_out=W_out)
+        status = info[0].cpu().numpy()
+        bad = np.flatnonzero(status)
+        if bad.size:
+            from .engine import L96_STATUS
+            j = int(bad[0])
+            raise ValueError("lorenz96 forward_pde_device: particle %d failed with status %d: %s"
+                             % (j, status[j], L96_STATUS.get(int(status[j]), "unknown")))
+        return G, W_next
+
     def grad_logjacobian(self, params):
         # as the reference computes it (ces/utils.py:343-347): the exponent is taken of the zero it
         # has just written, so the third entry is -1
@@ -182,6 +286,9 @@ class lorenz96_hom(lorenz96):
         phi = self._phi(ws)[:, -1].reshape(5, -1)
         return phi.mean(axis=1) if self.hom else phi[:, 7]
 
+    def _device_stat_mode(self):
+        return 1 if self.hom else 2
+
 
 class lorenz96Fc(lorenz96):
     """(F, log c) free, h = 1, b = 10 (ces/utils.py:369-389)."""
@@ -193,6 +300,9 @@ class lorenz96Fc(lorenz96):
     def __call__(self, t, w, F=10., log_c=np.log(10.)):
         return self.model(w, t, 1., F, log_c, 10.)
 
+    DEVICE_PAR_ROW = (-1, 0, 1, -1)
+    DEVICE_PAR_FIXED = (1., 0., 0., 10.)
+
 
 class lorenz96Fb(lorenz96):
     """(F, b) free (ces/utils.py:391-408)."""
@@ -200,6 +310,9 @@ class lorenz96Fb(lorenz96):
 
     def __call__(self, t, w, F=10., b=10.):
         return self.model(w, t, 1., F, np.log(10), b)
+
+    DEVICE_PAR_ROW = (-1, 0, -1, 1)
+    DEVICE_PAR_FIXED = (1., 0., np.log(10), 0.)
 
 
 class lorenz96hFb(lorenz96):
@@ -209,6 +322,9 @@ class lorenz96hFb(lorenz96):
     def __call__(self, t, w, h=1., F=10., b=10.):
         return self.model(w, t, h, F, np.log(10), b)
 
+    DEVICE_PAR_ROW = (0, 1, -1, 2)
+    DEVICE_PAR_FIXED = (0., 0., np.log(10), 0.)
+
 
 class lorenz96hcb(lorenz96):
     """(h, log c, b) free (ces/utils.py:430-448)."""
@@ -216,6 +332,9 @@ class lorenz96hcb(lorenz96):
 
     def __call__(self, t, w, h=1., log_c=np.log(10.), b=10.):
         return self.model(w, t, h, 10., log_c, b)
+
+    DEVICE_PAR_ROW = (0, -1, 1, 2)
+    DEVICE_PAR_FIXED = (0., 10., 0., 0.)
 
 
 def lorenz96_dim(t, X, h=1., F=10., c=2 ** 7., b=1.):

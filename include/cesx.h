@@ -402,6 +402,45 @@ int cesx_darcy_set(cesx_handle h, const cesx_darcy_desc* desc);
    is singular, the input left fp64's range).  The outputs of such a particle are NaN, the other particles are unaffected. */
 int cesx_darcy_apply(cesx_handle h, const void* U_dev, void* G_dev, int32_t* status_dev, void* stream);
 
+/* ---- forward-map hook: the two-scale Lorenz '96 models of the reference (ces/utils.py:229-448, type == 'pde') ----
+   What G_pde (ces/calibrate.py:132-154) does for one particle, for every column at once: integrate the model from the
+   carried state over [0, T] with scipy's RK45 as solve_ivp(method='RK45', max_step=dt, t_eval=t) runs it (rtol, atol,
+   select_initial_step, the step controller, min_step and the 4th-order dense output of scipy/integrate/_ivp), form the five
+   blocks of window statistics X, X^2, mean_l Y, mean_l Y^2, X mean_l Y over the LAST window of window_samples samples (the
+   samples 1 + spinup_samples .. n_t - 1 are cut into such windows), and carry the state at t[n_t - 1] on.  One wave per
+   particle, fp64 whatever the engine dtype, no atomics, every sum in a fixed order: two calls are bit-identical and a
+   particle's result does not depend on J_local, on its column or on the other particles.
+   The model's parameters (h, F, log c, b) are each a row of U or a fixed value, which covers lorenz96, lorenz96Fc, lorenz96Fb,
+   lorenz96hFb, lorenz96hcb (stat_mode 0, n_obs = 5 n_slow) and lorenz96_hom (stat_mode 1: the blocks averaged over the slow
+   index, 2: taken at slow index 7; n_obs = 5).
+   These entry points keep state of their own: the lineal and the Darcy maps are untouched. */
+typedef struct {
+    uint32_t struct_bytes;       /* sizeof(cesx_l96_desc) */
+    int32_t n_slow, n_fast;      /* n_slow >= 4, n_fast >= 1, n_state = n_slow (n_fast + 1) <= 448 */
+    int32_t n_obs, p;            /* must equal the handle's */
+    int32_t stat_mode;           /* 0 per slow index, 1 hom mean, 2 hom index 7 */
+    int32_t par_row[4];          /* h, F, log c, b: the row of U, or -1 and ... */
+    double par_fixed[4];         /* ... the fixed value */
+    double T, max_step, rtol, atol;
+    int32_t n_t;                 /* samples */
+    const double* t;             /* [n_t] HOST, non-decreasing, within [0, T]; copied */
+    int32_t spinup_samples, window_samples;   /* n_t - 1 - spinup_samples is a positive multiple of window_samples */
+    int64_t max_attempts;        /* attempted steps after which a particle ends with status 3 (>= 1) */
+} cesx_l96_desc;
+/* Copies the descriptor; replaces an earlier one.  CESX_EINVAL (text in cesx_last_error) for a shape outside the limits above,
+   p / n_obs differing from the handle's, a par_row out of range or repeated, t decreasing or outside [0, T], a sample count
+   that does not fill whole windows, or a non-positive T, max_step, rtol, atol; the installed map is kept then. */
+int cesx_lorenz_set(cesx_handle h, const cesx_l96_desc* desc);
+/* U_dev (p x J_local, engine dtype), W_in_dev (n_state x J_local fp64: the start states) -> G_dev (n_obs x J_local, engine
+   dtype), W_out_dev (n_state x J_local fp64: the states at t[n_t - 1]; may equal W_in_dev).  G_dev must not alias U_dev.
+   info_dev ([4][J_local] int32 on the device, or NULL): row 0 the status -- 0; 1 the step fell below min_step (scipy's
+   "required step size is less than spacing between numbers"); 2 a state or an error norm was not finite; 3 max_attempts
+   steps were attempted --, row 1 the accepted steps, row 2 the attempted steps, row 3 zero.  The outputs of a particle with
+   a status other than 0 are NaN, the other particles are unaffected.  Where t[n_t - 1] < T a particle stops once its last
+   sample is out. */
+int cesx_lorenz_apply(cesx_handle h, const void* U_dev, const double* W_in_dev, void* G_dev, double* W_out_dev,
+                   int32_t* info_dev, void* stream);
+
 /* ---- Sample: Metropolis-Hastings over the columns (ces/sample.py) -------
    MCMC.model_mh (ces/sample.py:121-196) runs ONE host chain; here every column of the handle's (p, J_local) layout is an
    independent chain of it (no communication between chains).  Per step:
