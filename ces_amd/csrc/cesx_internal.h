@@ -496,6 +496,12 @@ struct Engine {
     double *d_gp_ws = nullptr;                      // the K* panels of the launches that do not fit in LDS
     size_t gp_ws_len = 0;
     double *d_gp_LSi = nullptr;                     // [p][p] L_Sigma^{-1} of a dense Sigma, fp64 (cesx_mh_set_proposal)
+    // ---- the dense per-chain Sigma of CESX_GP_DENSE (cesx_gp_dense_set, kernels_gpdense.hip) ----
+    std::vector<double> h_y_raw, h_Gamma_raw;       // y and Gamma as cesx_set_problem got them (UNWHITENED; Gamma symmetric from its lower triangle)
+    int gpd_k = 0, gpd_logdet = 0;                  // columns of B (0: no descriptor; cesx_set_problem drops it), the log det term
+    double *d_gpd_B = nullptr, *d_gpd_Bt = nullptr; // B [n][gpd_k] and its transpose [gpd_k][n]
+    double *d_gpd_g0 = nullptr;                     // [n] the mean shift (zeros for a NULL g0)
+    double *d_gpd_y = nullptr, *d_gpd_Gam = nullptr;  // [n], [n][n] the unwhitened problem on the device
     // ---- GP training: batched likelihood and gradient (cesx_gpfit_*, kernels_gpfit.hip) ----
     int gf_n = 0, gf_Jt = 0, gf_Jp = 0;             // GPs, training points, training points rounded up to 16 (gf_n 0: no fit problem)
     int gf_family = 0, gf_ard = 0, gf_mean = 0;     // kernel family, ARD, mean kind (CESX_GPFIT_MEAN_*): one of each per problem
@@ -793,6 +799,11 @@ int launch_gp_predict(Engine& e, const void* X, double* mean, double* var, bool 
 // counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double* mean, const double* var, void* U,
                     const double* logu, unsigned step, hipStream_t s);
+// kernels_gpdense.hip: the same for CESX_GP_DENSE -- Sigma_j = Gamma + B diag(var_j) B^T factored per chain; mean and var
+// are (gpd_k x J).  gp_dense_prepare: once per installed descriptor (the kernels' dynamic LDS limit for n and k)
+int gp_dense_prepare(Engine& e, int n, int k);
+int launch_gp_score_dense(Engine& e, bool start, const void* X, const double* mean, const double* var, void* U,
+                          const double* logu, unsigned step, hipStream_t s);
 
 // kernels_darcy.hip: G = the installed Darcy map of the columns of U (engine dtype in and out, fp64 inside); status (J int32,
 // or nullptr): 0, the 1-based column of the zero pivot of a particle whose outputs are NaN, or minus the column that held a

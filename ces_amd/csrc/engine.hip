@@ -362,6 +362,7 @@ void cesx_destroy(cesx_handle h) {
                     e.d_absmax_part, e.d_clk, e.d_cholflag, e.d_lag, e.d_A64, e.d_b64, e.d_lvec, e.d_Wq, e.d_ticket,
                     e.d_mh_W, e.d_mh_Wf, e.d_mh_Li, e.d_mh_Li_f, e.d_mh_lb, e.d_mh_w, e.d_mh_xi, e.d_mh_phi, e.d_mh_cnt,
                     e.d_gp_A, e.d_gp_c, e.d_gp_Z, e.d_gp_par, e.d_gp_mw, e.d_gp_alpha, e.d_gp_Li, e.d_gp_ws, e.d_gp_LSi,
+                    e.d_gpd_B, e.d_gpd_Bt, e.d_gpd_g0, e.d_gpd_y, e.d_gpd_Gam,
                     e.d_gf_X, e.d_gf_Y, e.d_gf_Xs, e.d_gf_r, e.d_gf_t, e.d_gf_alpha, e.d_gf_A, e.d_gf_W, e.d_gf_Ki, e.d_gf_Ld, e.d_gf_part,
                     e.d_gf_theta, e.d_gf_out, e.d_gf_idx, e.d_gf_status, e.d_dc_mat, e.d_dc_idx, e.d_l9_t};
     for (void* q : ptrs)
@@ -403,8 +404,14 @@ int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const 
     e.problem_set = false;
     e.mh_kind = -1;                // (a new problem drops the MH proposal: include/cesx.h)
     e.mh_started = false;
+    e.gpd_k = 0;                   // (... and the dense descriptor of CESX_GP_DENSE)
     e.whiten = false;
     e.gw_src = nullptr;
+    // the problem as given, for the one mode that factors Sigma_j = Gamma + B diag(v_j) B^T itself (kernels_gpdense.hip)
+    e.h_y_raw.assign(y, y + n);
+    e.h_Gamma_raw.resize((size_t)n * n);
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k <= i; ++k) e.h_Gamma_raw[(size_t)i * n + k] = e.h_Gamma_raw[(size_t)k * n + i] = Gamma[(size_t)i * n + k];
     std::vector<double> gw(n), yi(y, y + n), Gi(Gamma, Gamma + (size_t)n * n);
     for (int i = 0; i < n; ++i) gw[i] = 1.0 / Gamma[(size_t)i * n + i];
     if (whiten) {
@@ -1041,7 +1048,57 @@ int cesx_gp_predict(cesx_handle h, const void* X, double* mean, double* var, int
     return launch_gp_predict(e, X, mean, var, nugget != 0, (hipStream_t)stream);
 }
 
+int cesx_gp_dense_set(cesx_handle h, const cesx_gp_dense_desc* d) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!d || d->struct_bytes != sizeof(cesx_gp_dense_desc)) { e.err = "cesx_gp_dense_set: bad cesx_gp_dense_desc"; return CESX_EINVAL; }
+    if (e.n > CESX_GP_DENSE_NMAX) { e.err = "cesx_gp_dense_set: n_obs is limited to 128 (the factor of Sigma lives in LDS)"; return CESX_EINVAL; }
+    if (d->k < 1 || d->k > e.n) { e.err = "cesx_gp_dense_set: k must be in 1 .. n_obs"; return CESX_EINVAL; }
+    if (!d->B) { e.err = "cesx_gp_dense_set: null pointer"; return CESX_EINVAL; }
+    if (!e.problem_set) { e.err = "cesx_gp_dense_set: cesx_set_problem has not been called"; return CESX_ESTATE; }
+    const int n = e.n, k = d->k;
+    std::vector<double> B(d->B, d->B + (size_t)n * k), Bt((size_t)n * k), g0(n, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int t = 0; t < k; ++t) Bt[(size_t)t * n + i] = B[(size_t)i * k + t];
+    if (d->g0) g0.assign(d->g0, d->g0 + n);
+    SET_DEVICE(e);
+    FLUSH(e);
+    CESX_HIP(hipDeviceSynchronize());          // (the old image may be read by launches still in flight)
+    e.gpd_k = 0;
+    // B for the largest k once: a later descriptor of the same engine fits
+    if (!e.d_gpd_B) TRY(dmalloc(e, &e.d_gpd_B, (size_t)n * n * 8));
+    if (!e.d_gpd_Bt) TRY(dmalloc(e, &e.d_gpd_Bt, (size_t)n * n * 8));
+    if (!e.d_gpd_g0) TRY(dmalloc(e, &e.d_gpd_g0, (size_t)n * 8));
+    if (!e.d_gpd_y) TRY(dmalloc(e, &e.d_gpd_y, (size_t)n * 8));
+    if (!e.d_gpd_Gam) TRY(dmalloc(e, &e.d_gpd_Gam, (size_t)n * n * 8));
+    TRY(upload(e, e.d_gpd_B, B.data(), B.size() * 8)); TRY(upload(e, e.d_gpd_Bt, Bt.data(), Bt.size() * 8));
+    TRY(upload(e, e.d_gpd_g0, g0.data(), (size_t)n * 8));
+    TRY(upload(e, e.d_gpd_y, e.h_y_raw.data(), (size_t)n * 8));
+    TRY(upload(e, e.d_gpd_Gam, e.h_Gamma_raw.data(), (size_t)n * n * 8));
+    TRY(gp_dense_prepare(e, n, k));
+    e.gpd_logdet = d->logdet ? 1 : 0;
+    e.gpd_k = k;
+    return CESX_OK;
+}
+
+int cesx_mh_phi(cesx_handle h, double* phi_host) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!phi_host) { e.err = "cesx_mh_phi: null pointer"; return CESX_EINVAL; }
+    if (!e.mh_started) { e.err = "cesx_mh_phi: no start (cesx_mh_start / cesx_gp_start) has been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    CESX_HIP(hipDeviceSynchronize());
+    CESX_HIP(hipMemcpy(phi_host, e.d_mh_phi, (size_t)e.J * 8, hipMemcpyDeviceToHost));
+    return CESX_OK;
+}
+
 static int gp_check_mode(Engine& e, int mode, const double* mean, const double* var) {
+    if (mode == CESX_GP_DENSE) {
+        if (e.gpd_k < 1) { e.err = "cesx_gp: CESX_GP_DENSE needs a descriptor (cesx_gp_dense_set after cesx_set_problem)"; return CESX_ESTATE; }
+        if (!mean || !var) { e.err = "cesx_gp: null pointer"; return CESX_EINVAL; }
+        if (e.gp_n != e.gpd_k) { e.err = "cesx_gp: the emulator's n_gp differs from the descriptor's k"; return CESX_EINVAL; }
+        return CESX_OK;
+    }
     if (mode != CESX_GP_GAMMA && mode != CESX_GP_VAR && mode != CESX_GP_GAMMA_VAR) { e.err = "cesx_gp: unknown likelihood mode"; return CESX_EINVAL; }
     if (!mean || (mode != CESX_GP_GAMMA && !var)) { e.err = "cesx_gp: null pointer"; return CESX_EINVAL; }
     if (mode != CESX_GP_GAMMA && e.whiten) { e.err = "cesx_gp: the variance modes need a diagonal Gamma"; return CESX_EINVAL; }
@@ -1057,7 +1114,8 @@ int cesx_gp_start(cesx_handle h, int mode, const void* U, const double* mean, co
     TRY(gp_check_mode(e, mode, mean, var));
     SET_DEVICE(e);
     FLUSH(e);
-    TRY(launch_gp_score(e, mode, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
+    if (mode == CESX_GP_DENSE) TRY(launch_gp_score_dense(e, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
+    else TRY(launch_gp_score(e, mode, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
     e.mh_started = true;
     e.mh_steps = 0;
     return CESX_OK;
@@ -1073,7 +1131,8 @@ int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U, const 
     TRY(gp_check_mode(e, mode, mean, var));
     SET_DEVICE(e);
     FLUSH(e);
-    TRY(launch_gp_score(e, mode, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    if (mode == CESX_GP_DENSE) TRY(launch_gp_score_dense(e, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    else TRY(launch_gp_score(e, mode, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
     ++e.mh_steps;
     return CESX_OK;
 }

@@ -18,7 +18,7 @@ OK, EINVAL, ENOTPD, EHIP, ESTATE, EUNSUPPORTED, ENOCONV = 0, 1, 2, 3, 4, 5, 6
 F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
-ABI_VERSION = 3
+ABI_VERSION = 4
 MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
@@ -30,15 +30,16 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_comm_stats", "cesx_allreduce_head", "cesx_allreduce_tail", "cesx_allreduce_whole", "cesx_allreduce_sum", "cesx_allreduce_max", "cesx_moments_uu_handover", "cesx_debug_gram_plan", "cesx_debug_dense_plan",
            "cesx_profile_clock", "cesx_calibrate_mfma", "cesx_profile_gap", "cesx_moments_rest_lineal", "cesx_copy_cols_async",
            "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count",
-           "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats",
-           "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept",
+           "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats", "cesx_mh_phi",
+           "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_dense_set",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_lorenz_set", "cesx_lorenz_apply")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
               2: "a state or an error norm was not finite",
               3: "max_attempts steps were attempted"}
 GPFIT_MEANS = {"zero": 0, "constant": 1, "linear": 2}   # CESX_GPFIT_MEAN_*
-GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
+GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2, "dense": 3}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR / _DENSE: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
+GP_DENSE_NMAX = 128                                   # CESX_GP_DENSE_NMAX
 
 
 class Config(C.Structure):
@@ -65,6 +66,10 @@ class GpDesc(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("n_gp", C.c_int32), ("J_t", C.c_int32),
                 ("A", C.c_void_p), ("c", C.c_void_p), ("Z", C.c_void_p), ("family", C.c_void_p),
                 ("par", C.c_void_p), ("mw", C.c_void_p), ("alpha", C.c_void_p), ("Li", C.c_void_p)]
+
+
+class GpDenseDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("k", C.c_int32), ("logdet", C.c_int32), ("B", C.c_void_p), ("g0", C.c_void_p)]
 
 
 class GpFitDesc(C.Structure):
@@ -222,6 +227,8 @@ def load_library(path=None):
     lib.cesx_gp_predict.argtypes = [vp, vp, vp, vp, i32, vp]
     lib.cesx_gp_start.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.cesx_gp_accept.argtypes = [vp, i32, u64, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gp_dense_set.argtypes = [vp, C.POINTER(GpDenseDesc)]
+    lib.cesx_mh_phi.argtypes = [vp, dp]
     lib.cesx_gpfit_set.argtypes = [vp, C.POINTER(GpFitDesc)]
     lib.cesx_gpfit_ntheta.argtypes = [vp]
     lib.cesx_gpfit_eval.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
@@ -888,6 +895,12 @@ class Engine:
             return int(steps.value), rate.value, buf
         return int(steps.value), rate.value
 
+    def mh_phi(self):
+        """The J current phi values of the chains, float64 on the host (cesx_mh_phi; synchronises)."""
+        buf = np.zeros(self.J, dtype=np.float64)
+        self._check(self.lib.cesx_mh_phi(self._h, _dptr(buf)))
+        return buf
+
     # -- GP emulator over the columns (include/cesx.h, cesx_gp_*; ces_amd/emulate.py and ces_amd/sample.py drive it) --
     def gp_set(self, img):
         """Install an emulator: ``img`` as ``ces_amd.emulate.device_image`` returns it (cesx_gp_set)."""
@@ -906,6 +919,22 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(self.lib.cesx_gp_set(self._h, C.byref(d)))
         self.gp_n = n
+
+    def gp_dense_set(self, B, g0=None, logdet=False):
+        """The descriptor of mode 'dense' (cesx_gp_dense_set): B (n_obs, k), the data space's basis (pca_tools['VD_k']); g0
+        (n_obs,) its shift (pca_tools['mG']) or None; logdet: add 1/2 log det Sigma.  Needs the problem; a later set_problem
+        drops it.  In mode 'dense' gp_start / gp_accept take (k, J) mean and variance rows."""
+        B = np.ascontiguousarray(np.asarray(B, dtype=np.float64))
+        if B.ndim != 2 or B.shape[0] != self.n_obs:
+            raise ValueError("gp_dense_set: B has shape %s, expected (%d, k)" % (B.shape, self.n_obs))
+        if g0 is not None:
+            g0 = np.ascontiguousarray(np.asarray(g0, dtype=np.float64).reshape(-1))
+            if g0.shape != (self.n_obs,):
+                raise ValueError("gp_dense_set: g0 has %d values, expected %d" % (g0.size, self.n_obs))
+        d = GpDenseDesc(C.sizeof(GpDenseDesc), B.shape[1], 1 if logdet else 0, B.ctypes.data if B.size else None,
+                        None if g0 is None else g0.ctypes.data)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_dense_set(self._h, C.byref(d)))
 
     def gp_predict(self, X, nugget=True, var=True, out=None):
         """(mean, var) float64 device tensors (n_gp, J) of the installed GPs at the columns of X (cesx_gp_predict);

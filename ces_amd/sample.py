@@ -12,9 +12,15 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          ``model.forward_device`` and ``mh_accept_kernel``, for gp_mh the batched GP prediction
                          ``gp_predict_kernel`` (fp64, MFMA) and ``gp_score_kernel``.  model_mh needs a model with
                          ``forward_device`` (``ces_amd.utils.lineal``); gp_mh needs this package's ``emulate.GPR`` models,
-                         one per output, and keeps ``pca_tools``, ``separable`` and ``noise_compounded`` with a dense
-                         Gamma on the host (ValueError).  Both need a prior with ``.mean`` / ``.cov`` (a frozen
+                         one per output, and keeps ``separable`` and ``noise_compounded`` with a dense Gamma and no
+                         ``pca_tools`` on the host (ValueError).  Both need a prior with ``.mean`` / ``.cov`` (a frozen
                          ``scipy.stats.multivariate_normal``).
+                         gp_mh with ``pca_tools=dict(VD_k=(n, k), mG=(n,) or (n, 1))`` and ``Gamma`` (required, dense or
+                         diagonal) runs the PCA-decorrelated route on the device: k GPs, and per chain and state
+                         ``Sigma = Gamma + VD_k diag(gvars) VD_k^T`` (ces/sample.py:52-53) built, factored and scored by
+                         one wave (``gp_score_dense_kernel``, n <= 128), with 1/2 log det Sigma when
+                         ``noise_compounded``.  ``pca_tools=dict(VD_k=np.eye(n), mG=np.zeros((n, 1)))`` gives the dense
+                         compounded likelihood ``Gamma + diag(gvars)`` of :50-51 on the device.
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -343,17 +349,39 @@ class MCMC(object):
     def _gp_mh_device(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
         import torch
         from . import emulate
+        from . import engine as _engine
         host = "; run gp_mh without chains= (the host path)"
-        if kwargs.get("pca_tools", None) is not None or kwargs.get("separable", False):
-            raise ValueError("chains=: pca_tools and separable need a per-chain n x n factorisation or one point at a "
-                             "time" + host)
+        if kwargs.get("separable", False):
+            raise ValueError("chains=: separable predicts one point at a time" + host)
         p, n = enka.p, enka.n_obs
         gpmodels = kwargs.get("gpmodels", None)
         gpmodels = enka.gpmodels if gpmodels is None else gpmodels
-        if len(gpmodels) != n:
-            raise ValueError("chains=: %d GPs for n_obs = %d" % (len(gpmodels), n) + host)
+        pca = kwargs.get("pca_tools", None)
         Gamma = kwargs.get("Gamma", None)
-        if Gamma is None:                                 # Sigma = diag(gvars) (:48-49)
+        n_gp, VD_k, mG, logdet = n, None, None, False
+        if pca is not None:                               # Sigma = Gamma + VD_k diag(gvars) VD_k^T (:52-53), dense per chain
+            if Gamma is None:
+                raise ValueError("chains=: pca_tools needs Gamma (the reference adds the (n, n) gvars of pca_tools to it, "
+                                 "ces/sample.py:52-53, and cannot run without)")
+            if n > _engine.GP_DENSE_NMAX:
+                raise ValueError("chains=: pca_tools factors an n x n Sigma per chain in LDS, n_obs <= %d (got %d)"
+                                 % (_engine.GP_DENSE_NMAX, n) + host)
+            VD_k = np.asarray(pca["VD_k"], dtype=np.float64)
+            if VD_k.ndim != 2 or VD_k.shape[0] != n or not 1 <= VD_k.shape[1] <= n:
+                raise ValueError("chains=: pca_tools['VD_k'] has shape %s, expected (n_obs, k) = (%d, k <= %d)"
+                                 % (VD_k.shape, n, n))
+            mG = np.asarray(pca["mG"], dtype=np.float64)
+            if mG.shape not in ((n,), (n, 1)):
+                raise ValueError("chains=: pca_tools['mG'] has shape %s, expected (%d,) or (%d, 1)" % (mG.shape, n, n))
+            mG = mG.reshape(n)
+            n_gp = VD_k.shape[1]
+            if len(gpmodels) != n_gp:
+                raise ValueError("chains=: %d GPs for the k = %d columns of pca_tools['VD_k']" % (len(gpmodels), n_gp))
+            logdet = bool(kwargs.get("noise_compounded", False))      # (:69-72)
+            mode, G = "dense", np.asarray(Gamma, dtype=np.float64).reshape(n, n)
+        elif len(gpmodels) != n:
+            raise ValueError("chains=: %d GPs for n_obs = %d" % (len(gpmodels), n) + host)
+        elif Gamma is None:                               # Sigma = diag(gvars) (:48-49)
             mode, G = "var", np.eye(n)
         else:
             G = np.asarray(Gamma, dtype=np.float64).reshape(n, n)
@@ -374,8 +402,10 @@ class MCMC(object):
 
         def bind(eng, M):
             eng.gp_set(img)
+            if mode == "dense":
+                eng.gp_dense_set(VD_k, mG, logdet)
             nugget, want_var = kwargs.get("nugget", True), mode != "gamma"
-            rows = lambda: torch.empty((n, M), dtype=torch.float64, device=eng.device)    # noqa: E731
+            rows = lambda: torch.empty((n_gp, M), dtype=torch.float64, device=eng.device)    # noqa: E731
             mean_u, mean_p = rows(), rows()
             var_u, var_p = (rows(), rows()) if want_var else (None, None)
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CESX_ABI_VERSION 3
+#define CESX_ABI_VERSION 4
 
 /* status codes */
 #define CESX_OK            0
@@ -481,6 +481,9 @@ int cesx_mh_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* 
 /* cesx_mh_accept calls since cesx_mh_start, the overall accept rate (accepted / (steps J_local)) and, per_chain_host != NULL,
    the J_local counters.  Synchronises. */
 int cesx_mh_stats(cesx_handle h, unsigned long long* steps, double* rate, unsigned long long* per_chain_host);
+/* The J_local current phi values of the chains (fp64, host), as the last start / accept left them; every MH and GP mode.
+   Synchronises.  CESX_ESTATE before a start (cesx_mh_start / cesx_gp_start). */
+int cesx_mh_phi(cesx_handle h, double* phi_host);
 
 /* ---- Emulate: GP prediction and the GP sampler over the columns (ces/emulate.py, ces/sample.py:17-119) --
    One exact GP per output, trained on the host (ces_amd/emulate.py); the engine holds its own fp64 image of them and
@@ -520,9 +523,31 @@ int cesx_gp_predict(cesx_handle h, const void* X_dev, double* mean_dev, double* 
 #define CESX_GP_GAMMA      0
 #define CESX_GP_VAR        1
 #define CESX_GP_GAMMA_VAR  2
+#define CESX_GP_DENSE      3
 int cesx_gp_start(cesx_handle h, int mode, const void* U_dev, const double* mean_dev, const double* var_dev, void* stream);
 int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev, const void* P_dev, const double* mean_dev,
                    const double* var_dev, const double* logu_dev, void* stream);
+/* CESX_GP_DENSE: k GPs on PCA-decorrelated outputs (pca_tools of ces/emulate.py:74-77 and ces/sample.py:52-53, :91-92).  The
+   data space is rebuilt per chain j from column j of the (k x J_local) rows of cesx_gp_predict (n_gp == k):
+       d = B m_j + g0 - y,    Sigma_j = Gamma + B diag(v_j) B^T,    phi = 1/2 d^T Sigma_j^{-1} d [+ 1/2 log det Sigma_j] + prior term
+   with y and Gamma of cesx_set_problem as given (dense or diagonal; NOT whitened) and the prior term of the other modes.
+   Sigma_j is a dense n x n matrix per chain and state: one wave factors it (Cholesky, resident in LDS) and scores, all in
+   fp64 in one fixed order -- two calls are bit-identical and a chain's phi does not depend on J_local, on its column or on
+   its neighbours.  A pivot that is not > 0 or not finite makes phi NaN: the test rejects, a start state stays stuck.
+   Limits: 1 <= k <= n_obs <= CESX_GP_DENSE_NMAX. */
+#define CESX_GP_DENSE_NMAX 128
+typedef struct {
+    uint32_t struct_bytes;    /* sizeof(cesx_gp_dense_desc) */
+    int32_t k;                /* columns of B = GPs */
+    int32_t logdet;           /* != 0: add 1/2 log det Sigma_j (noise_compounded, ces/sample.py:69-72) */
+    const double* B;          /* [n][k] row-major (VD_k) */
+    const double* g0;         /* [n] (mG) or NULL = 0 */
+} cesx_gp_dense_desc;
+/* Copies the descriptor (host fp64); replaces an earlier one.  CESX_EINVAL (text in cesx_last_error) for k < 1, k > n_obs,
+   n_obs > CESX_GP_DENSE_NMAX or a null B -- the installed descriptor stays; CESX_ESTATE without a problem.  A later
+   cesx_set_problem drops the descriptor, as it drops the proposal.  cesx_gp_start / cesx_gp_accept in mode CESX_GP_DENSE
+   return CESX_ESTATE without one, and need var_dev and n_gp == k. */
+int cesx_gp_dense_set(cesx_handle h, const cesx_gp_dense_desc* desc);
 
 /* ---- Emulate: training the GPs on device (ces_amd/emulate.py train_gps(device=True)) --------------------
    The log marginal likelihood of n_gp exact GPs on SHARED training inputs X and its gradient, all GPs of a call in the same
