@@ -7,8 +7,10 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../include/cesx.h"
+#include "cesx_stages.h"
 
 namespace cesx {
 
@@ -262,7 +264,7 @@ struct GramPart {
     int *d_type_hdr = nullptr, *d_rows = nullptr, *d_wblk = nullptr, *d_blk_rc = nullptr, *d_row_own = nullptr;
     void* d_slabs = nullptr;            // per type [slices][blocks of the type][tile*tile] engine dtype
     double* d_rowsum_part = nullptr;    // [row-sum slots][p+n]
-    // the plan's flattened tables: allocated, uploaded and freed from this one list (gram_part_alloc / gram_part_free)
+    // the plan's flattened tables: allocated and uploaded from this one list (gram_part_alloc); Engine::core owns the memory
     struct Table { int** dev; const std::vector<int>* host; };
     std::array<Table, 5> tables() {
         return {{{&d_type_hdr, &plan.type_hdr}, {&d_rows, &plan.rows}, {&d_wblk, &plan.wblk}, {&d_blk_rc, &plan.blk_rc},
@@ -398,7 +400,7 @@ struct Engine {
     void*   d_yT = nullptr;        // y in engine dtype
     void*   d_gwT = nullptr;       // diag(Gamma^{-1}) in engine dtype
     // gram: part 0 = U x U blocks (all chol(C) needs), part 1 = the rest
-    GramPart gp[2];
+    GramPart gram[2];
     MomLayout ml{};
     // stats partials
     int colsum_slices = 0;
@@ -469,59 +471,15 @@ struct Engine {
     bool  fwd_set = false, fwd_has_b = false;
     double *d_A64 = nullptr, *d_b64 = nullptr;   // the installed map in fp64 (n x p, n): cesx_moments_rest_lineal
     double *d_lvec = nullptr;                    // [2][n] c = A s_u + b - s_g and A sa
-    // ---- Metropolis-Hastings over the columns (cesx_mh_*, kernels_mh.hip) ----
+    // ---- the stages behind Calibrate: each struct owns its device memory and has one drop() (cesx_stages.h) ----
     std::vector<double> h_LSi, h_mu;   // L_Sigma^{-1} and mu of the problem (cesx_set_problem): the dense prior's image
-    int mh_kind = -1;                  // CESX_MH_RW / CESX_MH_PCN after cesx_mh_set_proposal, -1: none (cesx_set_problem drops it)
-    double mh_a = 1.0;                 // P = mh_a U + (b S) xi
-    bool mh_dense_prior = false;       // RW with a dense Sigma: the prior term is scored through w = L_Sigma^{-1} (u - mu)
-    bool mh_started = false;
-    unsigned long long mh_steps = 0;   // cesx_mh_accept calls since cesx_mh_start
-    void *d_mh_W = nullptr, *d_mh_Wf = nullptr;     // b S zero padded [rpad][kp], row-major and in the LDS-DMA kernels' order
-    void *d_mh_Li = nullptr, *d_mh_Li_f = nullptr;  // dense prior: L_Sigma^{-1} in the same two layouts
-    void *d_mh_lb = nullptr;                        // dense prior: -L_Sigma^{-1} mu [rpad] (the bias of the w launch)
-    void *d_mh_w = nullptr;                         // dense prior: [p][J] w of the states being scored
-    void *d_mh_xi = nullptr;                        // fp64: [p][J] the step's noise block (update3_kernel reads segments from memory)
-    double* d_mh_phi = nullptr;                     // [J] phi of the chains' current states
-    unsigned long long* d_mh_cnt = nullptr;         // [J] accepted proposals per chain
-    // ---- GP emulator over the columns (cesx_gp_*, kernels_gp.hip) ----
-    int gp_n = 0, gp_Jt = 0, gp_Jp = 0;             // GPs, training points, training points rounded up to 16 (0: no emulator)
-    size_t gp_li_len = 0;                           // doubles of one GP's packed L^{-1} (gp_Jp/16 (gp_Jp/16 + 1)/2 blocks of 256)
-    double *d_gp_A = nullptr;                       // [n][p][p] the input maps A_i (lower triangular)
-    double *d_gp_c = nullptr;                       // [p] the input shift c
-    double *d_gp_Z = nullptr;                       // [n][Jt][p] the mapped training points
-    double *d_gp_par = nullptr;                     // [n][4] sigma^2, sn^2, mean bias, kernel family
-    double *d_gp_mw = nullptr;                      // [n][p] the affine mean's weights over z
-    double *d_gp_alpha = nullptr;                   // [n][Jp] alpha, zero padded
-    double *d_gp_Li = nullptr;                      // [n][gp_li_len] L^{-1} in v_mfma_f64_16x16x4 A-operand order
-    double *d_gp_ws = nullptr;                      // the K* panels of the launches that do not fit in LDS
-    size_t gp_ws_len = 0;
-    double *d_gp_LSi = nullptr;                     // [p][p] L_Sigma^{-1} of a dense Sigma, fp64 (cesx_mh_set_proposal)
-    // ---- the dense per-chain Sigma of CESX_GP_DENSE (cesx_gp_dense_set, kernels_gpdense.hip) ----
     std::vector<double> h_y_raw, h_Gamma_raw;       // y and Gamma as cesx_set_problem got them (UNWHITENED; Gamma symmetric from its lower triangle)
-    int gpd_k = 0, gpd_logdet = 0;                  // columns of B (0: no descriptor; cesx_set_problem drops it), the log det term
-    double *d_gpd_B = nullptr, *d_gpd_Bt = nullptr; // B [n][gpd_k] and its transpose [gpd_k][n]
-    double *d_gpd_g0 = nullptr;                     // [n] the mean shift (zeros for a NULL g0)
-    double *d_gpd_y = nullptr, *d_gpd_Gam = nullptr;  // [n], [n][n] the unwhitened problem on the device
-    // ---- GP training: batched likelihood and gradient (cesx_gpfit_*, kernels_gpfit.hip) ----
-    int gf_n = 0, gf_Jt = 0, gf_Jp = 0;             // GPs, training points, training points rounded up to 16 (gf_n 0: no fit problem)
-    int gf_family = 0, gf_ard = 0, gf_mean = 0;     // kernel family, ARD, mean kind (CESX_GPFIT_MEAN_*): one of each per problem
-    int gf_nl = 0, gf_ntheta = 0, gf_ntile = 0;     // lengthscales (p or 1), parameters per GP, 64 x 64 tiles of the lower triangle
-    double *d_gf_X = nullptr, *d_gf_Y = nullptr;    // [Jt][p], [n][Jt]
-    double *d_gf_Xs = nullptr;                      // [n][Jp][p] X / l of the last evaluation
-    double *d_gf_r = nullptr, *d_gf_t = nullptr, *d_gf_alpha = nullptr;   // [n][Jp]: y - m(X), L^{-1} r, alpha
-    double *d_gf_A = nullptr, *d_gf_W = nullptr, *d_gf_Ki = nullptr;      // [n][Jp][Jp]: Ky -> L, L^{-T}, K^{-1}
-    double *d_gf_Ld = nullptr;                      // [n][Jp][16] the diagonal blocks of L (Ky's stay in d_gf_A: every workgroup of a launch reads them)
-    double *d_gf_part = nullptr;                    // [n][gf_ntile][gf_nl + 2] the gradient pass's partial sums
-    double *d_gf_theta = nullptr, *d_gf_out = nullptr;                    // [n][ntheta], [n][2 + ntheta] of the evaluation in flight
-    int *d_gf_idx = nullptr, *d_gf_status = nullptr;                      // [n]
-    std::vector<double> h_gf_out;
-    // ---- Darcy forward map over the columns (cesx_darcy_*, kernels_darcy.hip); state of its own: the lineal map is untouched ----
-    int dc_K = 0;                                   // Nmesh of the installed map (0: none)
-    double *d_dc_mat = nullptr;                     // [4][K][K] coef (K folded in, entry 0 zero), D, S, R, row-major
-    int *d_dc_idx = nullptr;                        // [p] scatter, then [n] obs_index
-    // ---- Lorenz '96 forward map over the columns (cesx_lorenz_*, kernels_l96.hip); state of its own, as the Darcy map's ----
-    cesx_l96_desc l9{};                             // the installed descriptor (n_slow 0: none; its t points nowhere: d_l9_t)
-    double *d_l9_t = nullptr;                       // [n_t] the sample times
+    MhState mh;                        // Metropolis-Hastings over the columns (cesx_mh_*, kernels_mh.hip)
+    GpState gp;                        // GP emulator over the columns (cesx_gp_*, kernels_gp.hip)
+    GpDenseState gpd;                  // the dense per-chain Sigma of CESX_GP_DENSE (cesx_gp_dense_set, kernels_gpdense.hip)
+    GpFitState gf;                     // GP training (cesx_gpfit_*, kernels_gpfit.hip)
+    DarcyState dc;                     // Darcy forward map (cesx_darcy_*, kernels_darcy.hip)
+    L96State l9;                       // Lorenz '96 forward map (cesx_lorenz_*, kernels_l96.hip)
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -579,6 +537,9 @@ struct Engine {
     double* d_lag = nullptr;       // [3] {N, lagged sum q_r^2, lagged sum q_e^2} of the moment buffer of the last cesx_apply (K2 copies
                                    // them here: the deferred finalisation reads engine-owned memory, not the caller's buffer)
     cesx_step_params last_prm{};
+    // Every d_ pointer above (the GramParts' and d_xi included) points into one of these: allocated through core_alloc, never
+    // released before the engine is.  An engine that never allocated (tools/plan_dump.hip) destructs without a dev_free call.
+    std::vector<DevBuf<void>> core;
 };
 
 // ---------------------------------------------------------------------------
@@ -587,11 +548,10 @@ struct Engine {
 int launch_colsum(Engine& e, const void* U, const void* G, double* sums, hipStream_t s);
 int launch_set_shift(Engine& e, const double* sums, hipStream_t s);
 // ---- K1: the moments launches (kernels_gram.hip, kernels_gram2.hip) ----
-// The plans of both launches of this engine (Engine::gp[.].plan), with center_u_wgs and gram_b_short; needs p, n, J, Jg, the
+// The plans of both launches of this engine (Engine::gram[.].plan), with center_u_wgs and gram_b_short; needs p, n, J, Jg, the
 // dtype and num_cus, no device.  CESX_EINVAL (Engine::err) when a plan does not fit in LDS.
 int plan_gram_parts(Engine& e);
-int gram_part_alloc(Engine& e, GramPart& gp);      // the plan's tables (uploaded), its slabs and row-sum slots (zeroed)
-void gram_part_free(GramPart& gp);
+int gram_part_alloc(Engine& e, GramPart& gp);      // the plan's tables (uploaded), its slabs and row-sum slots (zeroed): Engine::core
 // One moments launch: the Gram kernel of a part and the fp64 reduce of its slabs into `mom`; call sites name the fields they use.
 struct GramLaunch {
     int part = 0;                     // 0: the U x U blocks, 1: the rest
@@ -788,19 +748,19 @@ int launch_moments_lineal(Engine& e, double* mom, hipStream_t s);               
 int launch_calibrate(Engine& e, double target_ms, double* tflops, double* clock_ghz, hipStream_t s);   // kernels_calib.hip
 // the chains' state of a score launch (launch_mh_score, launch_gp_score)
 inline MhChains mh_chains(const Engine& e, bool start, const double* logu, unsigned step) {
-    return {e.cfg.j_offset, e.d_mh_phi, e.d_mh_cnt, logu, (unsigned)e.cfg.seed, (unsigned)(e.cfg.seed >> 32), step, start ? 1 : 0};
+    return {e.cfg.j_offset, e.mh.phi, e.mh.cnt, logu, (unsigned)e.cfg.seed, (unsigned)(e.cfg.seed >> 32), step, start ? 1 : 0};
 }
 // kernels_mh.hip: phi of the states X (with their forward map G, whitened when Gamma is dense) of every chain; start: into
-// Engine::d_mh_phi, counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
+// Engine::mh.phi, counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_mh_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s);
-// kernels_gp.hip: the GP means (and variances, var_out != nullptr) of the states X (p x J, engine dtype) into fp64 (gp_n x J)
+// kernels_gp.hip: the GP means (and variances, var_out != nullptr) of the states X (p x J, engine dtype) into fp64 (gp.n x J)
 int launch_gp_predict(Engine& e, const void* X, double* mean, double* var, bool nugget, hipStream_t s);
-// kernels_gp.hip: phi of the states X from the GP rows (mode CESX_GP_GAMMA / _VAR / _GAMMA_VAR); start: into d_mh_phi,
+// kernels_gp.hip: phi of the states X from the GP rows (mode CESX_GP_GAMMA / _VAR / _GAMMA_VAR); start: into mh.phi,
 // counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double* mean, const double* var, void* U,
                     const double* logu, unsigned step, hipStream_t s);
 // kernels_gpdense.hip: the same for CESX_GP_DENSE -- Sigma_j = Gamma + B diag(var_j) B^T factored per chain; mean and var
-// are (gpd_k x J).  gp_dense_prepare: once per installed descriptor (the kernels' dynamic LDS limit for n and k)
+// are (gpd.k x J).  gp_dense_prepare: once per installed descriptor (the kernels' dynamic LDS limit for n and k)
 int gp_dense_prepare(Engine& e, int n, int k);
 int launch_gp_score_dense(Engine& e, bool start, const void* X, const double* mean, const double* var, void* U,
                           const double* logu, unsigned step, hipStream_t s);
@@ -816,7 +776,7 @@ int launch_darcy(Engine& e, const void* U, void* G, int* status, hipStream_t s);
 // (may be W_in), info ([4][J] int32 or nullptr) = status, accepted steps, attempted steps, 0
 int launch_l96(Engine& e, const void* U, const double* W_in, void* G, double* W_out, int* info, hipStream_t s);
 
-// kernels_gpfit.hip: lml, gradient and status of the GPs d_gf_idx[0 .. n_active) at d_gf_theta into d_gf_out
+// kernels_gpfit.hip: lml, gradient and status of the GPs gf.idx[0 .. n_active) at gf.theta into gf.out
 int launch_gpfit_eval(Engine& e, int n_active, hipStream_t s);
 int gpfit_tiles(int Jp);                            // 64 x 64 tiles of the lower triangle of a Jp x Jp matrix
 
@@ -857,10 +817,19 @@ void set_global_error(const std::string& msg);
         }                                                                           \
     } while (0)
 
-// zeroed device memory (never an empty allocation)
-template <typename P> int dmalloc(Engine& e, P** ptr, size_t bytes) {
-    CESX_HIP(hipMalloc(reinterpret_cast<void**>(ptr), bytes ? bytes : 8));
-    CESX_HIP(hipMemset(*ptr, 0, bytes ? bytes : 8));
+// a failed DevBuf::alloc / ensure (dev_alloc's code: the hipError_t of its allocation, or of its memset) as an entry point's error
+inline int buf_fail(Engine& e, int rc) {
+    e.err = std::string("device allocation: ") + hipGetErrorString((hipError_t)rc);
+    return CESX_EHIP;
+}
+#define TRY_BUF(x) do { if (const int _b = (x)) return buf_fail(e, _b); } while (0)
+
+// a core buffer (Engine::core owns it; freed with the engine), its pointer handed out into the engine's own field
+template <typename P> int core_alloc(Engine& e, P** ptr, size_t bytes, bool zero = true) {
+    DevBuf<void> b;
+    TRY_BUF(b.alloc(bytes, zero));
+    *ptr = static_cast<P*>(b.get());
+    e.core.push_back(std::move(b));
     return CESX_OK;
 }
 
@@ -902,7 +871,7 @@ int launch_update_bound(Engine& e, K kern, dim3 grid, int lds, A& a, int prof_wh
 // bound: the profiling events are tied to the kernel's own start / end (ProfScope); otherwise they are recorded around it.
 template <typename T, typename K>
 int launch_gram_kernel(Engine& e, const GramLaunch& L, K kern, int threads, int lds, bool bound) {
-    GramPart& gp = e.gp[L.part];
+    GramPart& gp = e.gram[L.part];
     const dim3 grid(gp.plan.total_wgs), block(threads);
     CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     {

@@ -1,0 +1,100 @@
+// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gf, dc, l9).  Each owns its
+// device memory (DevBuf: freed with the struct), says what "nothing installed" is, and has one drop() that establishes it.
+// drop() releases the buffers whose size comes from the installed descriptor and keeps the ones sized by the engine's
+// shape alone (allocated on first use, reused by every later install).  No hip/ header: tools/devbuf_check.cpp runs these
+// structs on the host.
+#pragma once
+#include <vector>
+#include "devbuf.h"
+#include "../../include/cesx.h"
+
+namespace cesx {
+
+// ---- Metropolis-Hastings over the columns (cesx_mh_*, kernels_mh.hip); the chains of cesx_gp_* are these too ----
+struct MhState {
+    int kind = -1;                     // CESX_MH_RW / CESX_MH_PCN after cesx_mh_set_proposal, -1: none (cesx_set_problem drops it)
+    double a = 1.0;                    // P = a U + (b S) xi
+    bool dense_prior = false;          // RW with a dense Sigma: the prior term is scored through w = L_Sigma^{-1} (u - mu)
+    bool started = false;
+    unsigned long long steps = 0;      // cesx_mh_accept calls since cesx_mh_start
+    DevBuf<void> W, Wf;                // b S zero padded [rpad][kp], row-major and in the LDS-DMA kernels' order
+    DevBuf<void> Li, Li_f;             // dense prior: L_Sigma^{-1} in the same two layouts
+    DevBuf<void> lb;                   // dense prior: -L_Sigma^{-1} mu [rpad] (the bias of the w launch)
+    DevBuf<void> w;                    // dense prior: [p][J] w of the states being scored
+    DevBuf<void> xi;                   // fp64: [p][J] the step's noise block (update3_kernel reads segments from memory)
+    DevBuf<double> phi;                // [J] phi of the chains' current states
+    DevBuf<unsigned long long> cnt;    // [J] accepted proposals per chain
+    DevBuf<double> LSi;                // [p][p] L_Sigma^{-1} of a dense Sigma, fp64: the dense prior's factor as gp_score_kernel reads it
+    bool none() const { return kind < 0; }
+    void drop() { kind = -1; started = false; }      // every buffer is sized by the engine: kept
+};
+
+// ---- GP emulator over the columns (cesx_gp_*, kernels_gp.hip) ----
+struct GpState {
+    int n = 0, Jt = 0, Jp = 0;         // GPs, training points, training points rounded up to 16 (n 0: no emulator)
+    size_t li_len = 0;                 // doubles of one GP's packed L^{-1} (Jp/16 (Jp/16 + 1)/2 blocks of 256)
+    DevBuf<double> A;                  // [n][p][p] the input maps A_i (lower triangular)
+    DevBuf<double> c;                  // [p] the input shift c
+    DevBuf<double> Z;                  // [n][Jt][p] the mapped training points
+    DevBuf<double> par;                // [n][4] sigma^2, sn^2, mean bias, kernel family
+    DevBuf<double> mw;                 // [n][p] the affine mean's weights over z
+    DevBuf<double> alpha;              // [n][Jp] alpha, zero padded
+    DevBuf<double> Li;                 // [n][li_len] L^{-1} in v_mfma_f64_16x16x4 A-operand order
+    DevBuf<double> ws;                 // the K* panels of the launches that do not fit in LDS (grown by launch_gp_predict)
+    bool none() const { return n == 0; }
+    void drop() {                      // the image goes, ws stays
+        n = 0;
+        A.reset(); c.reset(); Z.reset(); par.reset(); mw.reset(); alpha.reset(); Li.reset();
+    }
+};
+
+// ---- the dense per-chain Sigma of CESX_GP_DENSE (cesx_gp_dense_set, kernels_gpdense.hip) ----
+struct GpDenseState {
+    int k = 0, logdet = 0;             // columns of B (0: no descriptor; cesx_set_problem drops it), the log det term
+    DevBuf<double> B, Bt;              // B [n][k] and its transpose [k][n]; both [n][n]: the largest k fits
+    DevBuf<double> g0;                 // [n] the mean shift (zeros for a NULL g0)
+    DevBuf<double> y, Gam;             // [n], [n][n] the unwhitened problem on the device
+    bool none() const { return k == 0; }
+    void drop() { k = 0; }             // every buffer is sized by the engine: kept
+};
+
+// ---- GP training: batched likelihood and gradient (cesx_gpfit_*, kernels_gpfit.hip) ----
+struct GpFitState {
+    int n = 0, Jt = 0, Jp = 0;         // GPs, training points, training points rounded up to 16 (n 0: no fit problem)
+    int family = 0, ard = 0, mean = 0; // kernel family, ARD, mean kind (CESX_GPFIT_MEAN_*): one of each per problem
+    int nl = 0, ntheta = 0, ntile = 0; // lengthscales (p or 1), parameters per GP, 64 x 64 tiles of the lower triangle
+    DevBuf<double> X, Y;               // [Jt][p], [n][Jt]
+    DevBuf<double> Xs;                 // [n][Jp][p] X / l of the last evaluation
+    DevBuf<double> r, t, alpha;        // [n][Jp]: y - m(X), L^{-1} r, alpha
+    DevBuf<double> A, W, Ki;           // [n][Jp][Jp]: Ky -> L, L^{-T}, K^{-1}
+    DevBuf<double> Ld;                 // [n][Jp][16] the diagonal blocks of L (Ky's stay in A: every workgroup of a launch reads them)
+    DevBuf<double> part;               // [n][ntile][nl + 2] the gradient pass's partial sums
+    DevBuf<double> theta, out;         // [n][ntheta], [n][2 + ntheta] of the evaluation in flight
+    DevBuf<int> idx, status;           // [n]
+    std::vector<double> h_out;
+    bool none() const { return n == 0; }
+    void drop() {                      // everything is sized by the descriptor
+        n = 0;
+        X.reset(); Y.reset(); Xs.reset(); r.reset(); t.reset(); alpha.reset(); A.reset(); W.reset(); Ki.reset(); Ld.reset();
+        part.reset(); theta.reset(); out.reset(); idx.reset(); status.reset();
+    }
+};
+
+// ---- Darcy forward map over the columns (cesx_darcy_*, kernels_darcy.hip); state of its own: the lineal map is untouched ----
+struct DarcyState {
+    int K = 0;                         // Nmesh of the installed map (0: none)
+    DevBuf<double> mat;                // [4][K][K] coef (K folded in, entry 0 zero), D, S, R, row-major
+    DevBuf<int> idx;                   // [p] scatter, then [n] obs_index
+    bool none() const { return K == 0; }
+    void drop() { K = 0; mat.reset(); idx.reset(); }
+};
+
+// ---- Lorenz '96 forward map over the columns (cesx_lorenz_*, kernels_l96.hip); state of its own, as the Darcy map's ----
+struct L96State {
+    cesx_l96_desc desc{};              // the installed descriptor (n_slow 0: none; its t points nowhere: the member t)
+    DevBuf<double> t;                  // [n_t] the sample times
+    bool none() const { return desc.n_slow == 0; }
+    void drop() { desc = cesx_l96_desc{}; t.reset(); }
+};
+
+}  // namespace cesx

@@ -164,6 +164,16 @@ int run_update_main(Engine& e, const cesx_step_params& prm, const void* U, const
 namespace cesx {
 void set_global_error(const std::string& msg) { try { g_create_err = msg; } catch (...) {} }
 
+// devbuf.h over HIP: the engine allocates and frees device memory here and nowhere else (kernels_calib.hip: the scratch of its one call)
+int dev_alloc(void** p, size_t bytes, bool zero) {
+    const size_t len = bytes ? bytes : 8;
+    hipError_t st = hipMalloc(p, len);
+    if (st != hipSuccess) { *p = nullptr; return (int)st; }
+    if (zero && (st = hipMemset(*p, 0, len)) != hipSuccess) { (void)hipFree(*p); *p = nullptr; return (int)st; }
+    return 0;
+}
+void dev_free(void* p) { (void)hipFree(p); }
+
 const void* whitened_G(Engine& e, const void* G, hipStream_t s, bool force, int* rc) {
     *rc = CESX_OK;
     if (!e.whiten) return G;
@@ -265,28 +275,20 @@ static int create_impl(const cesx_config* cfg, cesx_handle* out) {
     e.rpad = (mx + 255) / 256 * 256;
     e.mom_len = e.ml.len();                      // incl. lagged {sum q_r^2, sum q_e^2} of the previous apply
 
-#define DM(ptr, bytes) if ((rc = dmalloc(e, &ptr, (bytes)))) return fail(rc)
+#define DM(ptr, bytes) if ((rc = core_alloc(e, &ptr, (bytes)))) return fail(rc)
     DM(e.d_y, n * 8); DM(e.d_mu, p * 8); DM(e.d_ustar, p * 8);
     DM(e.d_Gamma, nn * 8); DM(e.d_gw, n * 8); DM(e.d_Wh, nn * 8);
     DM(e.d_Sigma, pp * 8); DM(e.d_Sinv, pp * 8); DM(e.d_sw, p * 8);
     DM(e.d_shift64, P * 8);
-    {
-        char* t;
-        DM(t, P * e.esz); e.d_shiftT = t;
-        DM(t, n * e.esz); e.d_yT = t;
-        DM(t, n * e.esz); e.d_gwT = t;
-        DM(t, (size_t)e.kn * 4 * e.esz); e.d_rowc = t;
-        DM(t, (size_t)e.rpad * e.ktot * e.esz); e.d_W = t;
-        DM(t, (size_t)e.rpad * e.ktot * e.esz); e.d_Wf = t;
-        DM(t, (size_t)e.rpad * e.esz); e.d_bias = t;
-        if (cfg->dtype == CESX_F32) {          // (the chained layout of kernels_update4.hip: 18 + kn / 16 tiles of 16 KiB)
-            DM(t, std::max((size_t)e.rpad * e.ktot * 4, (size_t)(18 + e.kn / 16) * 16384)); e.d_Wq = t;
-        }
-        DM(t, (size_t)e.rpad * e.kp * e.esz); e.d_Wfwd = t;
-        DM(t, (size_t)e.rpad * e.kp * e.esz); e.d_Wfwd_f = t;
-        DM(t, (size_t)e.rpad * e.esz); e.d_bfwd = t;
-    }
-    for (GramPart& gp : e.gp)
+    DM(e.d_shiftT, P * e.esz); DM(e.d_yT, n * e.esz); DM(e.d_gwT, n * e.esz);
+    DM(e.d_rowc, (size_t)e.kn * 4 * e.esz);
+    DM(e.d_W, (size_t)e.rpad * e.ktot * e.esz); DM(e.d_Wf, (size_t)e.rpad * e.ktot * e.esz);
+    DM(e.d_bias, (size_t)e.rpad * e.esz);
+    if (cfg->dtype == CESX_F32)          // (the chained layout of kernels_update4.hip: 18 + kn / 16 tiles of 16 KiB)
+        DM(e.d_Wq, std::max((size_t)e.rpad * e.ktot * 4, (size_t)(18 + e.kn / 16) * 16384));
+    DM(e.d_Wfwd, (size_t)e.rpad * e.kp * e.esz); DM(e.d_Wfwd_f, (size_t)e.rpad * e.kp * e.esz);
+    DM(e.d_bfwd, (size_t)e.rpad * e.esz);
+    for (GramPart& gp : e.gram)
         if ((rc = gram_part_alloc(e, gp))) return fail(rc);
     DM(e.d_metric_part, ((size_t)((e.J + 31) / 32) + 8) * 2 * 8);
     DM(e.d_metric_sums, 2 * 8);
@@ -303,7 +305,7 @@ static int create_impl(const cesx_config* cfg, cesx_handle* out) {
         for (int k = 0; k < 2; ++k) { DM(e.d_ns_x[0][k], nn * 8); DM(e.d_ns_x[1][k], pp * 8); }
         for (int k = 0; k < 3; ++k) DM(e.d_ns_r[k], (size_t)mx * mx * 8);
         DM(e.d_ns_parts, 2 * nb16 * nb16 * 8);
-        { char* t; DM(t, 64); e.d_ns_skip = reinterpret_cast<int*>(t); }
+        DM(e.d_ns_skip, 64);
     }
     {   // spectral rule (kernels_dense.hip, spec_square_kernel): {log accumulator, weight, flag, pad} + 2 x per-workgroup partial sums
         const size_t nb16 = ((size_t)n + 15) / 16;
@@ -350,24 +352,6 @@ void cesx_destroy(cesx_handle h) {
     if (!h) return;
     Engine& e = *reinterpret_cast<Engine*>(h);
     DeviceGuard dg(e.cfg.device);
-    void* ptrs[] = {e.d_y, e.d_mu, e.d_ustar, e.d_Gamma, e.d_gw, e.d_Wh, e.d_Sigma, e.d_Sinv, e.d_sw,
-                    e.d_shift64, e.d_shiftT, e.d_yT, e.d_gwT, e.d_W, e.d_Wf, e.d_Lwork, e.d_Wwh, e.d_Wwh_f, e.d_Gw, e.d_sums_w,
-                    e.d_bias, e.d_Wfwd, e.d_Wfwd_f, e.d_bfwd, e.d_metric_part, e.d_metric_sums,
-                    e.d_rowc,
-                    e.d_colsum_part, e.d_mom,
-                    e.d_sums, e.d_ubar, e.d_gbar, e.d_m, e.d_dg,
-                    e.d_C, e.d_L, e.d_Cug, e.d_See, e.d_Srr, e.d_K, e.d_Kp, e.d_M, e.d_P, e.d_PK,
-                    e.d_t1, e.d_t2, e.d_t3, e.d_t4, e.d_spec, e.d_ns_x[0][0], e.d_ns_x[0][1], e.d_ns_x[1][0], e.d_ns_x[1][1], e.d_ns_r[0], e.d_ns_r[1], e.d_ns_r[2],
-                    e.d_ns_parts, e.d_ns_skip, e.d_mv, e.d_part, e.d_scal, e.d_absmax,
-                    e.d_absmax_part, e.d_clk, e.d_cholflag, e.d_lag, e.d_A64, e.d_b64, e.d_lvec, e.d_Wq, e.d_ticket,
-                    e.d_mh_W, e.d_mh_Wf, e.d_mh_Li, e.d_mh_Li_f, e.d_mh_lb, e.d_mh_w, e.d_mh_xi, e.d_mh_phi, e.d_mh_cnt,
-                    e.d_gp_A, e.d_gp_c, e.d_gp_Z, e.d_gp_par, e.d_gp_mw, e.d_gp_alpha, e.d_gp_Li, e.d_gp_ws, e.d_gp_LSi,
-                    e.d_gpd_B, e.d_gpd_Bt, e.d_gpd_g0, e.d_gpd_y, e.d_gpd_Gam,
-                    e.d_gf_X, e.d_gf_Y, e.d_gf_Xs, e.d_gf_r, e.d_gf_t, e.d_gf_alpha, e.d_gf_A, e.d_gf_W, e.d_gf_Ki, e.d_gf_Ld, e.d_gf_part,
-                    e.d_gf_theta, e.d_gf_out, e.d_gf_idx, e.d_gf_status, e.d_dc_mat, e.d_dc_idx, e.d_l9_t};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    for (GramPart& gp : e.gp) gram_part_free(gp);
     for (int w = 0; w < 2; ++w)
         for (auto& pr : e.prof_ev[w]) { if (pr.first) (void)hipEventDestroy(pr.first); if (pr.second) (void)hipEventDestroy(pr.second); }
     for (auto ev : e.prof_pool) (void)hipEventDestroy(ev);
@@ -378,10 +362,7 @@ void cesx_destroy(cesx_handle h) {
         if (ev) (void)hipEventDestroy(ev);
     if (e.side) (void)hipStreamDestroy(e.side);
     if (e.comm) (void)cesx_comm_destroy(h);
-    for (void* q : e.d_xi)
-        if (q) (void)hipFree(q);
-    if (e.d_xi_tmp) (void)hipFree(e.d_xi_tmp);
-    delete &e;
+    delete &e;      // (the device memory: Engine::core and the stage structs free theirs, on the engine's device)
 }
 
 int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const double* mu,
@@ -402,9 +383,9 @@ int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const 
     //  the handle WITHOUT a problem -- cesx_moments* / cesx_apply then return CESX_ESTATE -- instead of half of the new one)
     const bool whiten = !is_diagonal(n, Gamma);
     e.problem_set = false;
-    e.mh_kind = -1;                // (a new problem drops the MH proposal: include/cesx.h)
-    e.mh_started = false;
-    e.gpd_k = 0;                   // (... and the dense descriptor of CESX_GP_DENSE)
+    // a new problem drops the MH proposal (include/cesx.h) and the dense descriptor of CESX_GP_DENSE: both are images of the
+    // problem.  The GP image, the fit problem and the three forward maps (lineal, Darcy, Lorenz '96) stay installed.
+    e.mh.drop(); e.gpd.drop();
     e.whiten = false;
     e.gw_src = nullptr;
     // the problem as given, for the one mode that factors Sigma_j = Gamma + B diag(v_j) B^T itself (kernels_gpdense.hip)
@@ -434,9 +415,9 @@ int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const 
                 fm[e.cfg.dtype == CESX_F32 ? wf_index(i, k, nkt) : wd_index(i, k, nkt)] = v;
             }
         // (each buffer checked on its own: a second call finds what an earlier, failed one did allocate)
-        if (!e.d_Wwh) { char* t; int rc; if ((rc = dmalloc(e, &t, len * e.esz))) return rc; e.d_Wwh = t; }
-        if (!e.d_Wwh_f) { char* t; int rc; if ((rc = dmalloc(e, &t, len * e.esz))) return rc; e.d_Wwh_f = t; }
-        if (!e.d_Gw) CESX_HIP(hipMalloc(&e.d_Gw, (size_t)n * (size_t)e.J * e.esz));
+        if (!e.d_Wwh) TRY(core_alloc(e, &e.d_Wwh, len * e.esz));
+        if (!e.d_Wwh_f) TRY(core_alloc(e, &e.d_Wwh_f, len * e.esz));
+        if (!e.d_Gw) TRY(core_alloc(e, &e.d_Gw, (size_t)n * (size_t)e.J * e.esz, false));
         TRY(upload_T(e, e.d_Wwh, rm.data(), len)); TRY(upload_T(e, e.d_Wwh_f, fm.data(), len));
     }
     TRY(upload(e, e.d_y, yi.data(), n * 8)); TRY(upload(e, e.d_Gamma, Gi.data(), (size_t)n * n * 8));
@@ -660,7 +641,7 @@ int cesx_apply(cesx_handle h, const cesx_step_params* prm, const double* mom, co
     // the chained form reads its noise from memory: a block neither injected nor drawn ahead goes into an engine buffer,
     // allocated here -- nothing is allocated once K2 is enqueued
     if (hk == UpdateKernel::Update4 && !xi && prefetched_block(e, prm->step_index) < 0 && plan.route == DenseRoute::Tail && !e.d_xi_tmp)
-        CESX_HIP(hipMalloc(&e.d_xi_tmp, (size_t)e.p * (size_t)e.J * e.esz));
+        TRY(core_alloc(e, &e.d_xi_tmp, (size_t)e.p * (size_t)e.J * e.esz, false));
     TRY(launch_dense(e, K2, plan));
     TRY(run_update_main(e, *prm, U, G, xi, Unext, s));
     // (Moving this last small kernel to the side stream was tried: the event record + wait pair costs
@@ -805,7 +786,7 @@ int cesx_prefetch_noise(cesx_handle h, uint64_t step_index, void* stream) {
     if (std::getenv("CESX_NO_NOISE_PREFETCH")) return CESX_OK;
     e.xi_lookahead = !(std::getenv("CESX_NOISE_LOOKAHEAD") && std::atoi(std::getenv("CESX_NOISE_LOOKAHEAD")) == 0);
     for (int b = 0; b < (e.xi_lookahead ? 2 : 1); ++b)
-        if (!e.d_xi[b]) CESX_HIP(hipMalloc(&e.d_xi[b], (size_t)e.p * (size_t)e.J * e.esz));
+        if (!e.d_xi[b]) TRY(core_alloc(e, &e.d_xi[b], (size_t)e.p * (size_t)e.J * e.esz, false));
     // The draw itself is enqueued by cesx_chol_async on the side stream, behind chol(C): no extra
     // cross-stream event (each costs ~6 us of GPU idle time), and it runs while the caller's stream
     // is in the tail of the second Gram launch and the latency-bound start of K2.
@@ -855,7 +836,7 @@ int cesx_forward_apply(cesx_handle h, const void* U, void* G, void* stream) {
 static unsigned mh_step_word(uint64_t step_index) { return (unsigned)(step_index | 0x80000000ull); }
 
 // a lower-triangular p x p fp64 matrix (row-major), zero padded into the update kernels' [rpad][kp] layouts, engine dtype
-static int mh_upload_tri(Engine& e, const double* M, void** rm_dev, void** fm_dev) {
+static int mh_upload_tri(Engine& e, const double* M, DevBuf<void>& rm_dev, DevBuf<void>& fm_dev) {
     const size_t len = (size_t)e.rpad * e.kp;
     std::vector<double> rm(len, 0.0), fm(len, 0.0);
     const int nkt = e.kp / 16;
@@ -865,23 +846,22 @@ static int mh_upload_tri(Engine& e, const double* M, void** rm_dev, void** fm_de
             rm[(size_t)i * e.kp + k] = v;
             fm[e.cfg.dtype == CESX_F32 ? wf_index(i, k, nkt) : wd_index(i, k, nkt)] = v;
         }
-    char* t;
-    if (!*rm_dev) { TRY(dmalloc(e, &t, len * e.esz)); *rm_dev = t; }
-    if (!*fm_dev) { TRY(dmalloc(e, &t, len * e.esz)); *fm_dev = t; }
-    TRY(upload_T(e, *rm_dev, rm.data(), len));
-    return upload_T(e, *fm_dev, fm.data(), len);
+    TRY_BUF(rm_dev.ensure(len * e.esz)); TRY_BUF(fm_dev.ensure(len * e.esz));
+    TRY(upload_T(e, rm_dev, rm.data(), len));
+    return upload_T(e, fm_dev, fm.data(), len);
 }
 
 // phi of the states X with their forward map G (cesx_mh_start: into the engine's phi; cesx_mh_accept: the test and U := X)
 static int mh_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s) {
     WHITEN(e, G, s, true);
     // a dense prior: w = L_Sigma^{-1} X - L_Sigma^{-1} mu, one triangular product (the kernel skips the zero blocks)
-    if (e.mh_dense_prior)
-        TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.d_mh_Li, .Wf = e.d_mh_Li_f, .ktot = e.kp, .bias = e.d_mh_lb,
-                                          .src = {{X, e.p, 0, 1}}, .nsrc = 1, .out = e.d_mh_w}, s));
+    if (e.mh.dense_prior)
+        TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.Li, .Wf = e.mh.Li_f, .ktot = e.kp, .bias = e.mh.lb,
+                                          .src = {{X, e.p, 0, 1}}, .nsrc = 1, .out = e.mh.w}, s));
     return launch_mh_score(e, start, X, G, U, logu, step, s);
 }
 
+// Failure rule: from the synchronise until the last upload the handle has NO proposal; a failure leaves it so.  The buffers are kept.
 int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
@@ -896,35 +876,32 @@ int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) 
     SET_DEVICE(e);
     FLUSH(e);
     CESX_HIP(hipDeviceSynchronize());          // (the images below may be read by launches still in flight)
-    e.mh_kind = -1;
-    e.mh_started = false;
+    e.mh.drop();
     const double b = kind == CESX_MH_PCN ? std::sqrt(beta) : 1.0;          // ces/sample.py:202: sqrt(beta), not beta
     std::vector<double> bS(S, S + (size_t)p * p);
     for (double& v : bS) v *= b;
-    TRY(mh_upload_tri(e, bS.data(), &e.d_mh_W, &e.d_mh_Wf));
-    e.mh_dense_prior = kind == CESX_MH_RW && !e.diag_sigma;
-    char* t;
+    TRY(mh_upload_tri(e, bS.data(), e.mh.W, e.mh.Wf));
+    e.mh.dense_prior = kind == CESX_MH_RW && !e.diag_sigma;
     if (!e.diag_sigma) {                       // gp_score_kernel's fp64 L_Sigma^{-1} (RW and pCN: ces/sample.py:57 / :96)
-        if (!e.d_gp_LSi) TRY(dmalloc(e, &e.d_gp_LSi, (size_t)p * p * 8));
-        TRY(upload(e, e.d_gp_LSi, e.h_LSi.data(), (size_t)p * p * 8));
+        TRY_BUF(e.mh.LSi.ensure((size_t)p * p * 8));
+        TRY(upload(e, e.mh.LSi, e.h_LSi.data(), (size_t)p * p * 8));
     }
-    if (e.mh_dense_prior) {
-        TRY(mh_upload_tri(e, e.h_LSi.data(), &e.d_mh_Li, &e.d_mh_Li_f));
+    if (e.mh.dense_prior) {
+        TRY(mh_upload_tri(e, e.h_LSi.data(), e.mh.Li, e.mh.Li_f));
         std::vector<double> lb(e.rpad, 0.0);
         for (int i = 0; i < p; ++i) {
             double acc = 0.0;
             for (int k = 0; k <= i; ++k) acc += e.h_LSi[(size_t)i * p + k] * e.h_mu[k];
             lb[i] = -acc;
         }
-        if (!e.d_mh_lb) { TRY(dmalloc(e, &t, (size_t)e.rpad * e.esz)); e.d_mh_lb = t; }
-        TRY(upload_T(e, e.d_mh_lb, lb.data(), e.rpad));
-        if (!e.d_mh_w) { TRY(dmalloc(e, &t, (size_t)p * (size_t)e.J * e.esz)); e.d_mh_w = t; }
+        TRY_BUF(e.mh.lb.ensure((size_t)e.rpad * e.esz));
+        TRY(upload_T(e, e.mh.lb, lb.data(), e.rpad));
+        TRY_BUF(e.mh.w.ensure((size_t)p * (size_t)e.J * e.esz));
     }
-    if (e.cfg.dtype == CESX_F64 && !e.d_mh_xi) { TRY(dmalloc(e, &t, (size_t)p * (size_t)e.J * 8)); e.d_mh_xi = t; }
-    if (!e.d_mh_phi) TRY(dmalloc(e, &e.d_mh_phi, (size_t)e.J * 8));
-    if (!e.d_mh_cnt) TRY(dmalloc(e, &e.d_mh_cnt, (size_t)e.J * 8));
-    e.mh_a = kind == CESX_MH_PCN ? std::sqrt(1.0 - beta * beta) : 1.0;
-    e.mh_kind = kind;
+    if (e.cfg.dtype == CESX_F64) TRY_BUF(e.mh.xi.ensure((size_t)p * (size_t)e.J * 8));
+    TRY_BUF(e.mh.phi.ensure((size_t)e.J * 8)); TRY_BUF(e.mh.cnt.ensure((size_t)e.J * 8));
+    e.mh.a = kind == CESX_MH_PCN ? std::sqrt(1.0 - beta * beta) : 1.0;
+    e.mh.kind = kind;
     return CESX_OK;
 }
 
@@ -932,12 +909,12 @@ int cesx_mh_start(cesx_handle h, const void* U, const void* G, void* stream) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U || !G) { e.err = "cesx_mh_start: null pointer"; return CESX_EINVAL; }
-    if (e.mh_kind < 0 || !e.problem_set) { e.err = "cesx_mh_start: no proposal (cesx_mh_set_proposal after cesx_set_problem)"; return CESX_ESTATE; }
+    if (e.mh.none() || !e.problem_set) { e.err = "cesx_mh_start: no proposal (cesx_mh_set_proposal after cesx_set_problem)"; return CESX_ESTATE; }
     SET_DEVICE(e);
     FLUSH(e);
     TRY(mh_score(e, true, U, G, nullptr, nullptr, 0u, (hipStream_t)stream));
-    e.mh_started = true;
-    e.mh_steps = 0;
+    e.mh.started = true;
+    e.mh.steps = 0;
     return CESX_OK;
 }
 
@@ -947,18 +924,18 @@ int cesx_mh_propose(cesx_handle h, uint64_t step_index, const void* U, const voi
     if (!U || !P) { e.err = "cesx_mh_propose: null pointer"; return CESX_EINVAL; }
     if (U == P) { e.err = "cesx_mh_propose: P must not alias U"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull) { e.err = "cesx_mh_propose: MH step indices are limited to 2^31"; return CESX_EINVAL; }
-    if (e.mh_kind < 0) { e.err = "cesx_mh_propose: cesx_mh_set_proposal has not been called"; return CESX_ESTATE; }
+    if (e.mh.none()) { e.err = "cesx_mh_propose: cesx_mh_set_proposal has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     FLUSH(e);
     hipStream_t s = (hipStream_t)stream;
     const unsigned sw = mh_step_word(step_index);
     // fp64: the block is drawn into the engine's buffer first (update3_kernel reads every segment from memory)
     if (!xi && e.cfg.dtype == CESX_F64) {
-        TRY(launch_noise(e, sw, e.d_mh_xi, s));
-        xi = e.d_mh_xi;
+        TRY(launch_noise(e, sw, e.mh.xi, s));
+        xi = e.mh.xi;
     }
-    return launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.d_mh_W, .Wf = e.d_mh_Wf, .ktot = e.kp,
-                                         .src = {{xi, e.p, xi ? 0 : 1, 1}}, .nsrc = 1, .add1 = {U, nullptr, e.mh_a}, .out = P,
+    return launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.W, .Wf = e.mh.Wf, .ktot = e.kp,
+                                         .src = {{xi, e.p, xi ? 0 : 1, 1}}, .nsrc = 1, .add1 = {U, nullptr, e.mh.a}, .out = P,
                                          .step_index = sw}, s);
 }
 
@@ -967,11 +944,11 @@ int cesx_mh_accept(cesx_handle h, uint64_t step_index, void* U, const void* P, c
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U || !P || !GP) { e.err = "cesx_mh_accept: null pointer"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull) { e.err = "cesx_mh_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
-    if (e.mh_kind < 0 || !e.mh_started) { e.err = "cesx_mh_accept: cesx_mh_start has not been called"; return CESX_ESTATE; }
+    if (e.mh.none() || !e.mh.started) { e.err = "cesx_mh_accept: cesx_mh_start has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     FLUSH(e);
     TRY(mh_score(e, false, P, GP, U, logu, mh_step_word(step_index), (hipStream_t)stream));
-    ++e.mh_steps;
+    ++e.mh.steps;
     return CESX_OK;
 }
 
@@ -979,21 +956,22 @@ int cesx_mh_stats(cesx_handle h, unsigned long long* steps, double* rate, unsign
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!steps || !rate) { e.err = "cesx_mh_stats: null pointer"; return CESX_EINVAL; }
-    if (!e.mh_started) { e.err = "cesx_mh_stats: cesx_mh_start has not been called"; return CESX_ESTATE; }
+    if (!e.mh.started) { e.err = "cesx_mh_stats: cesx_mh_start has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     std::vector<unsigned long long> c((size_t)e.J);
     CESX_HIP(hipDeviceSynchronize());
-    CESX_HIP(hipMemcpy(c.data(), e.d_mh_cnt, (size_t)e.J * 8, hipMemcpyDeviceToHost));
+    CESX_HIP(hipMemcpy(c.data(), e.mh.cnt, (size_t)e.J * 8, hipMemcpyDeviceToHost));
     unsigned long long sum = 0;
     for (unsigned long long v : c) sum += v;
-    *steps = e.mh_steps;
-    *rate = e.mh_steps ? (double)sum / ((double)e.mh_steps * (double)e.J) : 0.0;
+    *steps = e.mh.steps;
+    *rate = e.mh.steps ? (double)sum / ((double)e.mh.steps * (double)e.J) : 0.0;
     if (per_chain) std::memcpy(per_chain, c.data(), (size_t)e.J * 8);
     return CESX_OK;
 }
 
 // ---- Emulate: GP prediction and the GP sampler over the columns (ces/emulate.py, ces/sample.py:17-119; kernels_gp.hip) ----
 
+// Failure rule: an argument error leaves the OLD image; behind the synchronise the old image is dropped, and a failure then leaves none.
 int cesx_gp_set(cesx_handle h, const cesx_gp_desc* d) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
@@ -1006,9 +984,7 @@ int cesx_gp_set(cesx_handle h, const cesx_gp_desc* d) {
     SET_DEVICE(e);
     FLUSH(e);
     CESX_HIP(hipDeviceSynchronize());          // (the old image may be read by launches still in flight)
-    double** bufs[] = {&e.d_gp_A, &e.d_gp_c, &e.d_gp_Z, &e.d_gp_par, &e.d_gp_mw, &e.d_gp_alpha, &e.d_gp_Li};
-    for (double** b : bufs) if (*b) { CESX_HIP(hipFree(*b)); *b = nullptr; }
-    e.gp_n = 0;
+    e.gp.drop();
     const size_t li_len = (size_t)NB * (NB + 1) / 2 * 256;
     std::vector<double> par((size_t)n * 4), alpha((size_t)n * Jp, 0.0), Li((size_t)n * li_len, 0.0);
     for (int i = 0; i < n; ++i) {
@@ -1026,15 +1002,15 @@ int cesx_gp_set(cesx_handle h, const cesx_gp_desc* d) {
                     *o++ = row < Jt && col <= row ? L[(size_t)row * Jt + col] : 0.0;
                 }
     }
-    TRY(dmalloc(e, &e.d_gp_A, (size_t)n * p * p * 8)); TRY(upload(e, e.d_gp_A, d->A, (size_t)n * p * p * 8));
-    TRY(dmalloc(e, &e.d_gp_c, (size_t)p * 8)); TRY(upload(e, e.d_gp_c, d->c, (size_t)p * 8));
-    TRY(dmalloc(e, &e.d_gp_Z, (size_t)n * Jt * p * 8)); TRY(upload(e, e.d_gp_Z, d->Z, (size_t)n * Jt * p * 8));
-    TRY(dmalloc(e, &e.d_gp_par, par.size() * 8)); TRY(upload(e, e.d_gp_par, par.data(), par.size() * 8));
-    TRY(dmalloc(e, &e.d_gp_mw, (size_t)n * p * 8)); TRY(upload(e, e.d_gp_mw, d->mw, (size_t)n * p * 8));
-    TRY(dmalloc(e, &e.d_gp_alpha, alpha.size() * 8)); TRY(upload(e, e.d_gp_alpha, alpha.data(), alpha.size() * 8));
-    TRY(dmalloc(e, &e.d_gp_Li, Li.size() * 8)); TRY(upload(e, e.d_gp_Li, Li.data(), Li.size() * 8));
-    e.gp_Jt = Jt; e.gp_Jp = Jp; e.gp_li_len = li_len;
-    e.gp_n = n;
+    TRY_BUF(e.gp.A.alloc((size_t)n * p * p * 8)); TRY(upload(e, e.gp.A, d->A, (size_t)n * p * p * 8));
+    TRY_BUF(e.gp.c.alloc((size_t)p * 8)); TRY(upload(e, e.gp.c, d->c, (size_t)p * 8));
+    TRY_BUF(e.gp.Z.alloc((size_t)n * Jt * p * 8)); TRY(upload(e, e.gp.Z, d->Z, (size_t)n * Jt * p * 8));
+    TRY_BUF(e.gp.par.alloc(par.size() * 8)); TRY(upload(e, e.gp.par, par.data(), par.size() * 8));
+    TRY_BUF(e.gp.mw.alloc((size_t)n * p * 8)); TRY(upload(e, e.gp.mw, d->mw, (size_t)n * p * 8));
+    TRY_BUF(e.gp.alpha.alloc(alpha.size() * 8)); TRY(upload(e, e.gp.alpha, alpha.data(), alpha.size() * 8));
+    TRY_BUF(e.gp.Li.alloc(Li.size() * 8)); TRY(upload(e, e.gp.Li, Li.data(), Li.size() * 8));
+    e.gp.Jt = Jt; e.gp.Jp = Jp; e.gp.li_len = li_len;
+    e.gp.n = n;
     return CESX_OK;
 }
 
@@ -1042,12 +1018,13 @@ int cesx_gp_predict(cesx_handle h, const void* X, double* mean, double* var, int
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!X || !mean) { e.err = "cesx_gp_predict: null pointer"; return CESX_EINVAL; }
-    if (e.gp_n < 1) { e.err = "cesx_gp_predict: cesx_gp_set has not been called"; return CESX_ESTATE; }
+    if (e.gp.none()) { e.err = "cesx_gp_predict: cesx_gp_set has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     FLUSH(e);
     return launch_gp_predict(e, X, mean, var, nugget != 0, (hipStream_t)stream);
 }
 
+// Failure rule: from the synchronise until the last upload the handle has NO descriptor; a failure leaves it so.  The buffers are kept.
 int cesx_gp_dense_set(cesx_handle h, const cesx_gp_dense_desc* d) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
@@ -1064,20 +1041,20 @@ int cesx_gp_dense_set(cesx_handle h, const cesx_gp_dense_desc* d) {
     SET_DEVICE(e);
     FLUSH(e);
     CESX_HIP(hipDeviceSynchronize());          // (the old image may be read by launches still in flight)
-    e.gpd_k = 0;
+    e.gpd.drop();
     // B for the largest k once: a later descriptor of the same engine fits
-    if (!e.d_gpd_B) TRY(dmalloc(e, &e.d_gpd_B, (size_t)n * n * 8));
-    if (!e.d_gpd_Bt) TRY(dmalloc(e, &e.d_gpd_Bt, (size_t)n * n * 8));
-    if (!e.d_gpd_g0) TRY(dmalloc(e, &e.d_gpd_g0, (size_t)n * 8));
-    if (!e.d_gpd_y) TRY(dmalloc(e, &e.d_gpd_y, (size_t)n * 8));
-    if (!e.d_gpd_Gam) TRY(dmalloc(e, &e.d_gpd_Gam, (size_t)n * n * 8));
-    TRY(upload(e, e.d_gpd_B, B.data(), B.size() * 8)); TRY(upload(e, e.d_gpd_Bt, Bt.data(), Bt.size() * 8));
-    TRY(upload(e, e.d_gpd_g0, g0.data(), (size_t)n * 8));
-    TRY(upload(e, e.d_gpd_y, e.h_y_raw.data(), (size_t)n * 8));
-    TRY(upload(e, e.d_gpd_Gam, e.h_Gamma_raw.data(), (size_t)n * n * 8));
+    TRY_BUF(e.gpd.B.ensure((size_t)n * n * 8));
+    TRY_BUF(e.gpd.Bt.ensure((size_t)n * n * 8));
+    TRY_BUF(e.gpd.g0.ensure((size_t)n * 8));
+    TRY_BUF(e.gpd.y.ensure((size_t)n * 8));
+    TRY_BUF(e.gpd.Gam.ensure((size_t)n * n * 8));
+    TRY(upload(e, e.gpd.B, B.data(), B.size() * 8)); TRY(upload(e, e.gpd.Bt, Bt.data(), Bt.size() * 8));
+    TRY(upload(e, e.gpd.g0, g0.data(), (size_t)n * 8));
+    TRY(upload(e, e.gpd.y, e.h_y_raw.data(), (size_t)n * 8));
+    TRY(upload(e, e.gpd.Gam, e.h_Gamma_raw.data(), (size_t)n * n * 8));
     TRY(gp_dense_prepare(e, n, k));
-    e.gpd_logdet = d->logdet ? 1 : 0;
-    e.gpd_k = k;
+    e.gpd.logdet = d->logdet ? 1 : 0;
+    e.gpd.k = k;
     return CESX_OK;
 }
 
@@ -1085,24 +1062,24 @@ int cesx_mh_phi(cesx_handle h, double* phi_host) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!phi_host) { e.err = "cesx_mh_phi: null pointer"; return CESX_EINVAL; }
-    if (!e.mh_started) { e.err = "cesx_mh_phi: no start (cesx_mh_start / cesx_gp_start) has been called"; return CESX_ESTATE; }
+    if (!e.mh.started) { e.err = "cesx_mh_phi: no start (cesx_mh_start / cesx_gp_start) has been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     CESX_HIP(hipDeviceSynchronize());
-    CESX_HIP(hipMemcpy(phi_host, e.d_mh_phi, (size_t)e.J * 8, hipMemcpyDeviceToHost));
+    CESX_HIP(hipMemcpy(phi_host, e.mh.phi, (size_t)e.J * 8, hipMemcpyDeviceToHost));
     return CESX_OK;
 }
 
 static int gp_check_mode(Engine& e, int mode, const double* mean, const double* var) {
     if (mode == CESX_GP_DENSE) {
-        if (e.gpd_k < 1) { e.err = "cesx_gp: CESX_GP_DENSE needs a descriptor (cesx_gp_dense_set after cesx_set_problem)"; return CESX_ESTATE; }
+        if (e.gpd.none()) { e.err = "cesx_gp: CESX_GP_DENSE needs a descriptor (cesx_gp_dense_set after cesx_set_problem)"; return CESX_ESTATE; }
         if (!mean || !var) { e.err = "cesx_gp: null pointer"; return CESX_EINVAL; }
-        if (e.gp_n != e.gpd_k) { e.err = "cesx_gp: the emulator's n_gp differs from the descriptor's k"; return CESX_EINVAL; }
+        if (e.gp.n != e.gpd.k) { e.err = "cesx_gp: the emulator's n_gp differs from the descriptor's k"; return CESX_EINVAL; }
         return CESX_OK;
     }
     if (mode != CESX_GP_GAMMA && mode != CESX_GP_VAR && mode != CESX_GP_GAMMA_VAR) { e.err = "cesx_gp: unknown likelihood mode"; return CESX_EINVAL; }
     if (!mean || (mode != CESX_GP_GAMMA && !var)) { e.err = "cesx_gp: null pointer"; return CESX_EINVAL; }
     if (mode != CESX_GP_GAMMA && e.whiten) { e.err = "cesx_gp: the variance modes need a diagonal Gamma"; return CESX_EINVAL; }
-    if (e.gp_n != e.n) { e.err = "cesx_gp: the emulator's n_gp differs from n_obs"; return CESX_EINVAL; }
+    if (e.gp.n != e.n) { e.err = "cesx_gp: the emulator's n_gp differs from n_obs"; return CESX_EINVAL; }
     return CESX_OK;
 }
 
@@ -1110,14 +1087,14 @@ int cesx_gp_start(cesx_handle h, int mode, const void* U, const double* mean, co
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U) { e.err = "cesx_gp_start: null pointer"; return CESX_EINVAL; }
-    if (e.mh_kind < 0 || !e.problem_set) { e.err = "cesx_gp_start: no proposal (cesx_mh_set_proposal after cesx_set_problem)"; return CESX_ESTATE; }
+    if (e.mh.none() || !e.problem_set) { e.err = "cesx_gp_start: no proposal (cesx_mh_set_proposal after cesx_set_problem)"; return CESX_ESTATE; }
     TRY(gp_check_mode(e, mode, mean, var));
     SET_DEVICE(e);
     FLUSH(e);
     if (mode == CESX_GP_DENSE) TRY(launch_gp_score_dense(e, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
     else TRY(launch_gp_score(e, mode, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
-    e.mh_started = true;
-    e.mh_steps = 0;
+    e.mh.started = true;
+    e.mh.steps = 0;
     return CESX_OK;
 }
 
@@ -1127,13 +1104,13 @@ int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U, const 
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U || !P) { e.err = "cesx_gp_accept: null pointer"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull) { e.err = "cesx_gp_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
-    if (e.mh_kind < 0 || !e.mh_started) { e.err = "cesx_gp_accept: cesx_gp_start has not been called"; return CESX_ESTATE; }
+    if (e.mh.none() || !e.mh.started) { e.err = "cesx_gp_accept: cesx_gp_start has not been called"; return CESX_ESTATE; }
     TRY(gp_check_mode(e, mode, mean, var));
     SET_DEVICE(e);
     FLUSH(e);
     if (mode == CESX_GP_DENSE) TRY(launch_gp_score_dense(e, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
     else TRY(launch_gp_score(e, mode, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
-    ++e.mh_steps;
+    ++e.mh.steps;
     return CESX_OK;
 }
 
@@ -1367,33 +1344,26 @@ int cesx_debug_dense(cesx_handle h, double* ubar, double* gbar, double* C, doubl
 
 // ---- Emulate: training the GPs, batched likelihood and gradient (ces_amd/emulate.py train_gps(device=True); kernels_gpfit.hip) ----
 
-static int gpfit_free(Engine& e) {
-    e.gf_n = 0;
-    void** bufs[] = {(void**)&e.d_gf_X, (void**)&e.d_gf_Y, (void**)&e.d_gf_Xs, (void**)&e.d_gf_r, (void**)&e.d_gf_t, (void**)&e.d_gf_alpha,
-                     (void**)&e.d_gf_A, (void**)&e.d_gf_W, (void**)&e.d_gf_Ki, (void**)&e.d_gf_Ld, (void**)&e.d_gf_part, (void**)&e.d_gf_theta,
-                     (void**)&e.d_gf_out, (void**)&e.d_gf_idx, (void**)&e.d_gf_status};
-    for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
-    return CESX_OK;
-}
-
 static int gpfit_alloc(Engine& e, const cesx_gpfit_desc* d, int Jp, int nl, int ntheta, int ntile) {
     const size_t n = (size_t)d->n_gp, Jt = (size_t)d->J_t, p = (size_t)e.p, J2 = (size_t)Jp * Jp;
-    TRY(dmalloc(e, &e.d_gf_X, Jt * p * 8)); TRY(upload(e, e.d_gf_X, d->X, Jt * p * 8));
-    TRY(dmalloc(e, &e.d_gf_Y, n * Jt * 8)); TRY(upload(e, e.d_gf_Y, d->Y, n * Jt * 8));
-    TRY(dmalloc(e, &e.d_gf_Xs, n * Jp * p * 8));
-    TRY(dmalloc(e, &e.d_gf_r, n * Jp * 8)); TRY(dmalloc(e, &e.d_gf_t, n * Jp * 8)); TRY(dmalloc(e, &e.d_gf_alpha, n * Jp * 8));
-    TRY(dmalloc(e, &e.d_gf_A, n * J2 * 8)); TRY(dmalloc(e, &e.d_gf_W, n * J2 * 8)); TRY(dmalloc(e, &e.d_gf_Ki, n * J2 * 8));
-    TRY(dmalloc(e, &e.d_gf_Ld, n * Jp * 16 * 8));
-    TRY(dmalloc(e, &e.d_gf_part, n * ntile * (size_t)(nl + 2) * 8));
-    TRY(dmalloc(e, &e.d_gf_theta, n * ntheta * 8)); TRY(dmalloc(e, &e.d_gf_out, n * (size_t)(2 + ntheta) * 8));
-    TRY(dmalloc(e, &e.d_gf_idx, n * 4)); TRY(dmalloc(e, &e.d_gf_status, n * 4));
+    TRY_BUF(e.gf.X.alloc(Jt * p * 8)); TRY(upload(e, e.gf.X, d->X, Jt * p * 8));
+    TRY_BUF(e.gf.Y.alloc(n * Jt * 8)); TRY(upload(e, e.gf.Y, d->Y, n * Jt * 8));
+    TRY_BUF(e.gf.Xs.alloc(n * Jp * p * 8));
+    TRY_BUF(e.gf.r.alloc(n * Jp * 8)); TRY_BUF(e.gf.t.alloc(n * Jp * 8)); TRY_BUF(e.gf.alpha.alloc(n * Jp * 8));
+    TRY_BUF(e.gf.A.alloc(n * J2 * 8)); TRY_BUF(e.gf.W.alloc(n * J2 * 8)); TRY_BUF(e.gf.Ki.alloc(n * J2 * 8));
+    TRY_BUF(e.gf.Ld.alloc(n * Jp * 16 * 8));
+    TRY_BUF(e.gf.part.alloc(n * ntile * (size_t)(nl + 2) * 8));
+    TRY_BUF(e.gf.theta.alloc(n * ntheta * 8)); TRY_BUF(e.gf.out.alloc(n * (size_t)(2 + ntheta) * 8));
+    TRY_BUF(e.gf.idx.alloc(n * 4)); TRY_BUF(e.gf.status.alloc(n * 4));
     return CESX_OK;
 }
 
+// Failure rule: the old fit problem is dropped before the arguments are looked at (a bad descriptor drops it too); a failed
+// allocation or upload leaves none and nothing allocated.
 int cesx_gpfit_set(cesx_handle h, const cesx_gpfit_desc* d) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
-    e.gf_n = 0;                                // whatever fails below, the handle is left without a fit problem
+    e.gf.n = 0;                                // whatever fails below, the handle is left without a fit problem
     if (!d || d->struct_bytes != sizeof(cesx_gpfit_desc)) { e.err = "cesx_gpfit_set: bad cesx_gpfit_desc"; return CESX_EINVAL; }
     if (!d->X || !d->Y) { e.err = "cesx_gpfit_set: null pointer"; return CESX_EINVAL; }
     if (d->n_gp < 1 || d->n_gp > 65535 || d->J_t < 1 || d->J_t > 16384) { e.err = "cesx_gpfit_set: 1 <= n_gp <= 65535 and 1 <= J_t <= 16384"; return CESX_EINVAL; }
@@ -1402,49 +1372,49 @@ int cesx_gpfit_set(cesx_handle h, const cesx_gpfit_desc* d) {
     SET_DEVICE(e);
     FLUSH(e);
     CESX_HIP(hipDeviceSynchronize());          // (an evaluation of the old problem may still be in flight)
-    gpfit_free(e);
+    e.gf.drop();
     const int Jp = (d->J_t + 15) / 16 * 16, nl = d->ard ? e.p : 1;
     const int ntheta = nl + 2 + (d->mean == CESX_GPFIT_MEAN_ZERO ? 0 : d->mean == CESX_GPFIT_MEAN_CONSTANT ? 1 : e.p + 1);
     const int ntile = gpfit_tiles(Jp);
     const int rc = gpfit_alloc(e, d, Jp, nl, ntheta, ntile);
-    if (rc != CESX_OK) { gpfit_free(e); return rc; }          // nothing is committed before everything is
-    e.gf_Jt = d->J_t; e.gf_Jp = Jp; e.gf_family = d->family; e.gf_ard = d->ard ? 1 : 0; e.gf_mean = d->mean;
-    e.gf_nl = nl; e.gf_ntheta = ntheta; e.gf_ntile = ntile;
-    e.h_gf_out.assign((size_t)d->n_gp * (2 + ntheta), 0.0);
-    e.gf_n = d->n_gp;
+    if (rc != CESX_OK) { e.gf.drop(); return rc; }          // nothing is committed before everything is
+    e.gf.Jt = d->J_t; e.gf.Jp = Jp; e.gf.family = d->family; e.gf.ard = d->ard ? 1 : 0; e.gf.mean = d->mean;
+    e.gf.nl = nl; e.gf.ntheta = ntheta; e.gf.ntile = ntile;
+    e.gf.h_out.assign((size_t)d->n_gp * (2 + ntheta), 0.0);
+    e.gf.n = d->n_gp;
     return CESX_OK;
 }
 
 int cesx_gpfit_ntheta(cesx_handle h) {
     if (!h) return -1;
     Engine& e = *reinterpret_cast<Engine*>(h);
-    return e.gf_n > 0 ? e.gf_ntheta : -1;
+    return e.gf.none() ? -1 : e.gf.ntheta;
 }
 
 int cesx_gpfit_eval(cesx_handle h, int n_active, const int32_t* idx, const double* theta, double* lml, double* grad,
                     int32_t* status, void* stream) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
-    if (e.gf_n < 1) { e.err = "cesx_gpfit_eval: cesx_gpfit_set has not been called"; return CESX_ESTATE; }
+    if (e.gf.none()) { e.err = "cesx_gpfit_eval: cesx_gpfit_set has not been called"; return CESX_ESTATE; }
     if (!idx || !theta || !lml || !grad || !status) { e.err = "cesx_gpfit_eval: null pointer"; return CESX_EINVAL; }
-    if (n_active < 1 || n_active > e.gf_n) { e.err = "cesx_gpfit_eval: 1 <= n_active <= n_gp"; return CESX_EINVAL; }
+    if (n_active < 1 || n_active > e.gf.n) { e.err = "cesx_gpfit_eval: 1 <= n_active <= n_gp"; return CESX_EINVAL; }
     {
-        std::vector<char> seen((size_t)e.gf_n, 0);          // (two entries for one GP would share its workspace)
+        std::vector<char> seen((size_t)e.gf.n, 0);          // (two entries for one GP would share its workspace)
         for (int i = 0; i < n_active; ++i) {
-            if (idx[i] < 0 || idx[i] >= e.gf_n || seen[(size_t)idx[i]]) { e.err = "cesx_gpfit_eval: idx out of range or repeated"; return CESX_EINVAL; }
+            if (idx[i] < 0 || idx[i] >= e.gf.n || seen[(size_t)idx[i]]) { e.err = "cesx_gpfit_eval: idx out of range or repeated"; return CESX_EINVAL; }
             seen[(size_t)idx[i]] = 1;
         }
     }
     SET_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
-    const size_t nt = (size_t)e.gf_ntheta, no = 2 + nt;
-    CESX_HIP(hipMemcpyAsync(e.d_gf_idx, idx, (size_t)n_active * 4, hipMemcpyHostToDevice, s));
-    CESX_HIP(hipMemcpyAsync(e.d_gf_theta, theta, (size_t)n_active * nt * 8, hipMemcpyHostToDevice, s));
+    const size_t nt = (size_t)e.gf.ntheta, no = 2 + nt;
+    CESX_HIP(hipMemcpyAsync(e.gf.idx, idx, (size_t)n_active * 4, hipMemcpyHostToDevice, s));
+    CESX_HIP(hipMemcpyAsync(e.gf.theta, theta, (size_t)n_active * nt * 8, hipMemcpyHostToDevice, s));
     TRY(launch_gpfit_eval(e, n_active, s));
-    CESX_HIP(hipMemcpyAsync(e.h_gf_out.data(), e.d_gf_out, (size_t)n_active * no * 8, hipMemcpyDeviceToHost, s));
+    CESX_HIP(hipMemcpyAsync(e.gf.h_out.data(), e.gf.out, (size_t)n_active * no * 8, hipMemcpyDeviceToHost, s));
     CESX_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < n_active; ++i) {
-        const double* o = e.h_gf_out.data() + (size_t)i * no;
+        const double* o = e.gf.h_out.data() + (size_t)i * no;
         lml[i] = o[0];
         status[i] = o[1] == 0.0 ? CESX_OK : CESX_ENOTPD;
         std::memcpy(grad + (size_t)i * nt, o + 2, nt * 8);
@@ -1455,14 +1425,14 @@ int cesx_gpfit_eval(cesx_handle h, int n_active, const int32_t* idx, const doubl
 int cesx_gpfit_factors(cesx_handle h, int i, double* alpha, double* Li) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
-    if (e.gf_n < 1) { e.err = "cesx_gpfit_factors: cesx_gpfit_set has not been called"; return CESX_ESTATE; }
-    if (i < 0 || i >= e.gf_n || !alpha || !Li) { e.err = "cesx_gpfit_factors: bad GP index or null pointer"; return CESX_EINVAL; }
+    if (e.gf.none()) { e.err = "cesx_gpfit_factors: cesx_gpfit_set has not been called"; return CESX_ESTATE; }
+    if (i < 0 || i >= e.gf.n || !alpha || !Li) { e.err = "cesx_gpfit_factors: bad GP index or null pointer"; return CESX_EINVAL; }
     SET_DEVICE(e);
-    const size_t Jt = (size_t)e.gf_Jt, Jp = (size_t)e.gf_Jp;
+    const size_t Jt = (size_t)e.gf.Jt, Jp = (size_t)e.gf.Jp;
     std::vector<double> W(Jp * Jp);
     CESX_HIP(hipDeviceSynchronize());
-    CESX_HIP(hipMemcpy(alpha, e.d_gf_alpha + (size_t)i * Jp, Jt * 8, hipMemcpyDeviceToHost));
-    CESX_HIP(hipMemcpy(W.data(), e.d_gf_W + (size_t)i * Jp * Jp, Jp * Jp * 8, hipMemcpyDeviceToHost));
+    CESX_HIP(hipMemcpy(alpha, e.gf.alpha + (size_t)i * Jp, Jt * 8, hipMemcpyDeviceToHost));
+    CESX_HIP(hipMemcpy(W.data(), e.gf.W + (size_t)i * Jp * Jp, Jp * Jp * 8, hipMemcpyDeviceToHost));
     for (size_t r = 0; r < Jt; ++r)                         // L^{-1} = W^T: the engine keeps the upper-triangular L^{-T}
         for (size_t c = 0; c < Jt; ++c) Li[r * Jt + c] = c <= r ? W[c * Jp + r] : 0.0;
     return CESX_OK;
@@ -1470,6 +1440,7 @@ int cesx_gpfit_factors(cesx_handle h, int i, double* alpha, double* Li) {
 
 // ---- Darcy forward map over the columns (ces_amd/darcy.py; kernels_darcy.hip) ----
 
+// Failure rule: an argument error leaves the OLD map; behind the synchronise there is none until everything is uploaded.
 int cesx_darcy_set(cesx_handle h, const cesx_darcy_desc* d) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
@@ -1494,16 +1465,14 @@ int cesx_darcy_set(cesx_handle h, const cesx_darcy_desc* d) {
     }
     SET_DEVICE(e);
     CESX_HIP(hipDeviceSynchronize());          // (the old image may be read by launches still in flight)
-    e.dc_K = 0;
+    e.dc.drop();
     TRY(darcy_prepare(e, K));
-    if (e.d_dc_mat) { CESX_HIP(hipFree(e.d_dc_mat)); e.d_dc_mat = nullptr; }
-    if (e.d_dc_idx) { CESX_HIP(hipFree(e.d_dc_idx)); e.d_dc_idx = nullptr; }
-    TRY(dmalloc(e, &e.d_dc_mat, (size_t)4 * KK * 8));
-    TRY(dmalloc(e, &e.d_dc_idx, idx.size() * 4));
+    TRY_BUF(e.dc.mat.alloc((size_t)4 * KK * 8));
+    TRY_BUF(e.dc.idx.alloc(idx.size() * 4));
     const double* mats[4] = {d->coef, d->D, d->S, d->R};
-    for (int k = 0; k < 4; ++k) TRY(upload(e, e.d_dc_mat + (size_t)k * KK, mats[k], (size_t)KK * 8));
-    TRY(upload(e, e.d_dc_idx, idx.data(), idx.size() * 4));
-    e.dc_K = K;
+    for (int k = 0; k < 4; ++k) TRY(upload(e, e.dc.mat + (size_t)k * KK, mats[k], (size_t)KK * 8));
+    TRY(upload(e, e.dc.idx, idx.data(), idx.size() * 4));
+    e.dc.K = K;
     return CESX_OK;
 }
 
@@ -1511,13 +1480,14 @@ int cesx_darcy_apply(cesx_handle h, const void* U, void* G, int32_t* status, voi
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U || !G) { e.err = "cesx_darcy_apply: null pointer"; return CESX_EINVAL; }
-    if (e.dc_K < 4) { e.err = "cesx_darcy_apply: cesx_darcy_set has not been called"; return CESX_ESTATE; }
+    if (e.dc.none()) { e.err = "cesx_darcy_apply: cesx_darcy_set has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     return launch_darcy(e, U, G, status, (hipStream_t)stream);
 }
 
 // ---- Lorenz '96 forward map over the columns (ces_amd/models.py; kernels_l96.hip) ----
 
+// Failure rule: ANY failure leaves the OLD map installed -- the new sample times are allocated and uploaded before the old are released.
 int cesx_lorenz_set(cesx_handle h, const cesx_l96_desc* d) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
@@ -1551,13 +1521,12 @@ int cesx_lorenz_set(cesx_handle h, const cesx_l96_desc* d) {
     if (d->max_attempts < 1) { e.err = "cesx_lorenz_set: max_attempts < 1"; return CESX_EINVAL; }
     SET_DEVICE(e);
     CESX_HIP(hipDeviceSynchronize());          // (the old sample times may be read by launches still in flight)
-    double* tnew = nullptr;
-    TRY(dmalloc(e, &tnew, (size_t)d->n_t * 8));
-    if (int rc = upload(e, tnew, d->t, (size_t)d->n_t * 8)) { (void)hipFree(tnew); return rc; }
-    if (e.d_l9_t) (void)hipFree(e.d_l9_t);
-    e.d_l9_t = tnew;
-    e.l9 = *d;
-    e.l9.t = nullptr;
+    DevBuf<double> tnew;
+    TRY_BUF(tnew.alloc((size_t)d->n_t * 8));
+    TRY(upload(e, tnew, d->t, (size_t)d->n_t * 8));
+    e.l9.t = std::move(tnew);
+    e.l9.desc = *d;
+    e.l9.desc.t = nullptr;
     return CESX_OK;
 }
 
@@ -1566,7 +1535,7 @@ int cesx_lorenz_apply(cesx_handle h, const void* U, const double* W_in, void* G,
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U || !W_in || !G || !W_out) { e.err = "cesx_lorenz_apply: null pointer"; return CESX_EINVAL; }
     if (G == U) { e.err = "cesx_lorenz_apply: G must not alias U"; return CESX_EINVAL; }
-    if (e.l9.n_slow < 4) { e.err = "cesx_lorenz_apply: cesx_lorenz_set has not been called"; return CESX_ESTATE; }
+    if (e.l9.none()) { e.err = "cesx_lorenz_apply: cesx_lorenz_set has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     return launch_l96(e, U, W_in, G, W_out, info, (hipStream_t)stream);
 }

@@ -217,12 +217,12 @@ int darcy_prepare(Engine& e, int K) {
 int launch_darcy(Engine& e, const void* U, void* G, int* status, hipStream_t s) {
     DarcyArgs a{};
     a.U = U; a.G = G; a.status = status; a.J = e.J;
-    a.K = e.dc_K; a.p = e.p; a.n_obs = e.n; a.S = darcy_stride(e.dc_K);
-    const int KK = e.dc_K * e.dc_K;
-    a.coef = e.d_dc_mat; a.D = e.d_dc_mat + KK; a.Sm = e.d_dc_mat + 2 * KK; a.R = e.d_dc_mat + 3 * KK;
-    a.scatter = e.d_dc_idx; a.obs = e.d_dc_idx + e.p;
+    a.K = e.dc.K; a.p = e.p; a.n_obs = e.n; a.S = darcy_stride(e.dc.K);
+    const int KK = e.dc.K * e.dc.K;
+    a.coef = e.dc.mat; a.D = e.dc.mat + KK; a.Sm = e.dc.mat + 2 * KK; a.R = e.dc.mat + 3 * KK;
+    a.scatter = e.dc.idx; a.obs = e.dc.idx + e.p;
     if (e.J >= (1LL << 31)) { e.err = "cesx_darcy_apply: too many particles for one launch"; return CESX_EUNSUPPORTED; }
-    const size_t lds = darcy_lds(e.dc_K);
+    const size_t lds = darcy_lds(e.dc.K);
     auto kern = e.cfg.dtype == CESX_F32 ? darcy_kernel<float> : darcy_kernel<double>;
     hipLaunchKernelGGL(kern, dim3((unsigned)e.J), dim3(DARCY_THREADS), lds, s, a);      // (J >= 1: cesx_create)
     CESX_HIP(hipGetLastError());

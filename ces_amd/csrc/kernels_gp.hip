@@ -142,13 +142,13 @@ template <typename T>
 static int gp_predict_t(Engine& e, const void* X, double* mean, double* var, bool nugget, hipStream_t s) {
     GpArgs<T> a{};
     a.X = (const T*)X; a.M = e.J; a.p = e.p;
-    a.Jt = e.gp_Jt; a.Jp = e.gp_Jp; a.li_len = e.gp_li_len;
-    a.A = e.d_gp_A; a.c = e.d_gp_c; a.Z = e.d_gp_Z; a.par = e.d_gp_par; a.mw = e.d_gp_mw; a.alpha = e.d_gp_alpha; a.Li = e.d_gp_Li;
+    a.Jt = e.gp.Jt; a.Jp = e.gp.Jp; a.li_len = e.gp.li_len;
+    a.A = e.gp.A; a.c = e.gp.c; a.Z = e.gp.Z; a.par = e.gp.par; a.mw = e.gp.mw; a.alpha = e.gp.alpha; a.Li = e.gp.Li;
     a.mean = mean; a.var = var; a.nugget = nugget ? 1 : 0;
-    if ((e.J + GP_T - 1) / GP_T * (long long)e.gp_n >= (1LL << 31)) { e.err = "cesx_gp_predict: too many (GP, tile) pairs"; return CESX_EUNSUPPORTED; }
+    if ((e.J + GP_T - 1) / GP_T * (long long)e.gp.n >= (1LL << 31)) { e.err = "cesx_gp_predict: too many (GP, tile) pairs"; return CESX_EUNSUPPORTED; }
     a.ntiles = (int)((e.J + GP_T - 1) / GP_T);
-    a.nwork = a.ntiles * e.gp_n;
-    const size_t panel = (size_t)(e.p + e.gp_Jp) * GP_T;                  // doubles
+    a.nwork = a.ntiles * e.gp.n;
+    const size_t panel = (size_t)(e.p + e.gp.Jp) * GP_T;                  // doubles
     if (panel * 8 <= GP_LDS_MAX) {
         auto kern = gp_predict_kernel<T, true>;
         CESX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(panel * 8)));
@@ -157,12 +157,11 @@ static int gp_predict_t(Engine& e, const void* X, double* mean, double* var, boo
         // the panels in global memory: at most 256 MiB of them, the grid strides over the tiles
         const long long slots = std::max(1LL, std::min<long long>((long long)a.nwork, std::min<long long>(1024, (32LL << 20) / (long long)panel)));
         const size_t need = (size_t)slots * panel;
-        if (e.gp_ws_len < need) {
-            if (e.d_gp_ws) { CESX_HIP(hipStreamSynchronize(s)); CESX_HIP(hipFree(e.d_gp_ws)); e.d_gp_ws = nullptr; e.gp_ws_len = 0; }
-            CESX_HIP(hipMalloc(reinterpret_cast<void**>(&e.d_gp_ws), need * 8));
-            e.gp_ws_len = need;
+        if (e.gp.ws.bytes < need * 8) {
+            if (e.gp.ws) CESX_HIP(hipStreamSynchronize(s));      // (a launch of this stream may still read the old one)
+            TRY_BUF(e.gp.ws.alloc(need * 8, false));
         }
-        a.ws = e.d_gp_ws;
+        a.ws = e.gp.ws;
         hipLaunchKernelGGL((gp_predict_kernel<T, false>), dim3((unsigned)slots), dim3(GP_THREADS), 0, s, a);
     }
     CESX_HIP(hipGetLastError());
@@ -232,7 +231,7 @@ static int gp_score_t(Engine& e, int mode, bool start, const void* X, const doub
     a.mean = mean; a.var = var; a.n = e.n; a.M = e.J;
     a.y = e.d_y; a.gw = e.d_gw; a.gam = e.d_Gamma; a.Lg = e.whiten ? e.d_Wh : nullptr;
     a.mode = mode;
-    a.X = (const T*)X; a.mu = e.d_mu; a.sw = e.d_sw; a.LSi = e.diag_sigma ? nullptr : e.d_gp_LSi; a.p = e.p;
+    a.X = (const T*)X; a.mu = e.d_mu; a.sw = e.d_sw; a.LSi = e.diag_sigma ? nullptr : e.mh.LSi.get(); a.p = e.p;
     a.U = (T*)U; a.c = mh_chains(e, start, logu, step);
     hipLaunchKernelGGL((gp_score_kernel<T>), dim3((unsigned)((e.J + GPS_THREADS - 1) / GPS_THREADS)), dim3(GPS_THREADS), 0, s, a);
     CESX_HIP(hipGetLastError());

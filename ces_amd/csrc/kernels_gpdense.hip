@@ -132,13 +132,13 @@ template <typename T>
 static int gp_score_dense_t(Engine& e, bool start, const void* X, const double* mean, const double* var, void* U,
                             const double* logu, unsigned step, hipStream_t s) {
     GpDenseArgs<T> a{};
-    a.mean = mean; a.var = var; a.n = e.n; a.k = e.gpd_k; a.M = e.J;
-    a.B = e.d_gpd_B; a.Bt = e.d_gpd_Bt; a.g0 = e.d_gpd_g0; a.y = e.d_gpd_y; a.Gam = e.d_gpd_Gam;
-    a.logdet = e.gpd_logdet;
-    a.X = (const T*)X; a.mu = e.d_mu; a.sw = e.d_sw; a.LSi = e.diag_sigma ? nullptr : e.d_gp_LSi; a.p = e.p;
+    a.mean = mean; a.var = var; a.n = e.n; a.k = e.gpd.k; a.M = e.J;
+    a.B = e.gpd.B; a.Bt = e.gpd.Bt; a.g0 = e.gpd.g0; a.y = e.gpd.y; a.Gam = e.gpd.Gam;
+    a.logdet = e.gpd.logdet;
+    a.X = (const T*)X; a.mu = e.d_mu; a.sw = e.d_sw; a.LSi = e.diag_sigma ? nullptr : e.mh.LSi.get(); a.p = e.p;
     a.U = (T*)U; a.c = mh_chains(e, start, logu, step);
     if (e.J >= (1LL << 31)) { e.err = "cesx_gp: too many chains for one dense launch"; return CESX_EUNSUPPORTED; }
-    hipLaunchKernelGGL((gp_score_dense_kernel<T>), dim3((unsigned)e.J), dim3(GPD_THREADS), gp_dense_lds(e.n, e.gpd_k), s, a);
+    hipLaunchKernelGGL((gp_score_dense_kernel<T>), dim3((unsigned)e.J), dim3(GPD_THREADS), gp_dense_lds(e.n, e.gpd.k), s, a);
     CESX_HIP(hipGetLastError());
     return CESX_OK;
 }

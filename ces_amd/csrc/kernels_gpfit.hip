@@ -439,12 +439,12 @@ void gpfit_final_kernel(const GpFitArgs a) {
 
 int launch_gpfit_eval(Engine& e, int n_active, hipStream_t s) {
     GpFitArgs a{};
-    a.Jt = e.gf_Jt; a.Jp = e.gf_Jp; a.NB = e.gf_Jp / 16; a.p = e.p;
-    a.family = e.gf_family; a.ard = e.gf_ard; a.mean = e.gf_mean; a.nl = e.gf_nl; a.ntheta = e.gf_ntheta;
-    a.ntile = e.gf_ntile; a.nacc = e.gf_nl + 2;
-    a.idx = e.d_gf_idx; a.theta = e.d_gf_theta; a.X = e.d_gf_X; a.Y = e.d_gf_Y;
-    a.Xs = e.d_gf_Xs; a.res = e.d_gf_r; a.tv = e.d_gf_t; a.alpha = e.d_gf_alpha;
-    a.A = e.d_gf_A; a.W = e.d_gf_W; a.Ki = e.d_gf_Ki; a.Ld = e.d_gf_Ld; a.part = e.d_gf_part; a.status = e.d_gf_status; a.out = e.d_gf_out;
+    a.Jt = e.gf.Jt; a.Jp = e.gf.Jp; a.NB = e.gf.Jp / 16; a.p = e.p;
+    a.family = e.gf.family; a.ard = e.gf.ard; a.mean = e.gf.mean; a.nl = e.gf.nl; a.ntheta = e.gf.ntheta;
+    a.ntile = e.gf.ntile; a.nacc = e.gf.nl + 2;
+    a.idx = e.gf.idx; a.theta = e.gf.theta; a.X = e.gf.X; a.Y = e.gf.Y;
+    a.Xs = e.gf.Xs; a.res = e.gf.r; a.tv = e.gf.t; a.alpha = e.gf.alpha;
+    a.A = e.gf.A; a.W = e.gf.W; a.Ki = e.gf.Ki; a.Ld = e.gf.Ld; a.part = e.gf.part; a.status = e.gf.status; a.out = e.gf.out;
     const unsigned ny = (unsigned)n_active, NB = (unsigned)a.NB;
     const dim3 blk(GF_THREADS);
     hipLaunchKernelGGL(gpfit_prep_kernel, dim3((a.Jp + GF_THREADS - 1) / GF_THREADS, ny), blk, 0, s, a);

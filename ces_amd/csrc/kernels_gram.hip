@@ -736,7 +736,7 @@ int plan_gram_parts(Engine& e) {
     const bool slim_side = e.J == e.Jg && potrf_ld(e.p) <= 256;
     e.center_u_wgs = slim_side ? 8 : 256;       // (16 x 1024 threads do NOT get placed on the 8 free CUs: measured)
     for (int part = 0; part < 2; ++part) {
-        GramPlan& pl = e.gp[part].plan;
+        GramPlan& pl = e.gram[part].plan;
         const int budget = part == 0 ? e.num_cus : e.num_cus - (slim_side ? e.num_cus / 32 : e.num_cus / 8);
         auto plan = [&](int min_types) {
             return make_gram_plan(e.P, tile, gram_nbw(dtype), gram_max_stage_rows(), part + 1, pbU, min_types, budget, ntiles);
@@ -751,7 +751,7 @@ int plan_gram_parts(Engine& e) {
         if (pl.max_rb * tile > gram_max_stage_rows()) { e.err = "gram plan exceeds LDS"; return CESX_EINVAL; }
     }
     // MFMA cycles of the second Gram launch's busiest SIMD, roughly: blocks x tiles x MFMAs per block and tile x 64 / SIMDs
-    const double cyc = (double)e.gp[1].plan.nblocks * (double)ntiles * (dtype == CESX_F32 ? 16.0 : 4.0) * 64.0 /
+    const double cyc = (double)e.gram[1].plan.nblocks * (double)ntiles * (dtype == CESX_F32 ? 16.0 : 4.0) * 64.0 /
                        (4.0 * std::max(1, e.num_cus));
     e.gram_b_short = cyc < 60e-6 * 2.3e9;
     return CESX_OK;
@@ -761,26 +761,18 @@ int gram_part_alloc(Engine& e, GramPart& gp) {
     const GramPlan& pl = gp.plan;
     int rc;
     for (const GramPart::Table& t : gp.tables()) {
-        if ((rc = dmalloc(e, t.dev, t.host->size() * 4))) return rc;
+        if ((rc = core_alloc(e, t.dev, t.host->size() * 4))) return rc;
         CESX_HIP(hipMemcpy(*t.dev, t.host->data(), t.host->size() * 4, hipMemcpyHostToDevice));
     }
-    char* slabs;
-    if ((rc = dmalloc(e, &slabs, (size_t)std::max(pl.total_slabs, 1) * pl.tile * pl.tile * e.esz))) return rc;
-    gp.d_slabs = slabs;
-    return dmalloc(e, &gp.d_rowsum_part, (size_t)pl.total_rs * e.P * 8);
-}
-
-void gram_part_free(GramPart& gp) {
-    for (const GramPart::Table& t : gp.tables()) (void)hipFree(*t.dev);      // (hipFree(nullptr) is a no-op)
-    (void)hipFree(gp.d_slabs);
-    (void)hipFree(gp.d_rowsum_part);
+    if ((rc = core_alloc(e, &gp.d_slabs, (size_t)std::max(pl.total_slabs, 1) * pl.tile * pl.tile * e.esz))) return rc;
+    return core_alloc(e, &gp.d_rowsum_part, (size_t)pl.total_rs * e.P * 8);
 }
 
 // ---------------------------------------------------------------------------
 // host: launches
 // ---------------------------------------------------------------------------
 GramKernel pick_gram_kernel(const Engine& e, int part, const void* U, const void* G) {
-    const GramPlan& pl = e.gp[part].plan;
+    const GramPlan& pl = e.gram[part].plan;
     // (a tiny problem can have all its blocks in part 0; the reduce still writes part 1's share of the buffer: row sums
     //  it owns and the lagged tail)
     if (pl.nblocks == 0) return GramKernel::None;
@@ -799,7 +791,7 @@ GramKernel pick_gram_kernel(const Engine& e, int part, const void* U, const void
 // the fp64 slab reduce of a part into L.mom
 template <typename T>
 static int launch_gram_reduce_t(Engine& e, const GramLaunch& L) {
-    GramPart& gp = e.gp[L.part];
+    GramPart& gp = e.gram[L.part];
     const GramPlan& pl = gp.plan;
     const long long ngroups = (long long)pl.nblocks * pl.tile * pl.tile / Mfma<T>::VEC;
     const int row_lo = std::min(pl.own_lo * pl.tile, e.P), row_hi = std::min(pl.own_hi * pl.tile, e.P);
@@ -822,7 +814,7 @@ static int launch_gram_reduce(Engine& e, const GramLaunch& L) {
 
 template <typename T>
 static int launch_gram1_t(Engine& e, const GramLaunch& L, bool aligned) {
-    const int rows = e.gp[L.part].plan.max_rb * e.gp[L.part].plan.tile;
+    const int rows = e.gram[L.part].plan.max_rb * e.gram[L.part].plan.tile;
     return launch_gram_kernel<T>(e, L, aligned ? gram_kernel<T, true> : gram_kernel<T, false>, GRAM_THREADS,
                                  2 * rows * ROW_STRIDE + rows * 16, false);
 }

@@ -326,13 +326,13 @@ static void l96_launch_T(const L96Args& a, size_t lds, hipStream_t s) {
 }
 
 int launch_l96(Engine& e, const void* U, const double* W_in, void* G, double* W_out, int* info, hipStream_t s) {
-    const cesx_l96_desc& d = e.l9;
+    const cesx_l96_desc& d = e.l9.desc;
     L96Args a{};
     a.U = U; a.W_in = W_in; a.G = G; a.W_out = W_out; a.info = info; a.J = e.J;
     a.n_slow = d.n_slow; a.n_fast = d.n_fast; a.n_state = d.n_slow * (d.n_fast + 1); a.n_obs = d.n_obs; a.stat_mode = d.stat_mode;
     for (int k = 0; k < 4; ++k) { a.par_row[k] = d.par_row[k]; a.par_fixed[k] = d.par_fixed[k]; }
     a.T = d.T; a.max_step = d.max_step; a.rtol = d.rtol; a.atol = d.atol;
-    a.n_t = d.n_t; a.t = e.d_l9_t;
+    a.n_t = d.n_t; a.t = e.l9.t;
     a.first_kept = d.n_t - d.window_samples; a.window = d.window_samples;
     a.max_attempts = d.max_attempts;
     if (e.J >= (1LL << 31)) { e.err = "cesx_lorenz_apply: too many particles for one launch"; return CESX_EUNSUPPORTED; }

@@ -125,12 +125,12 @@ template <typename T>
 static int mh_score_t(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step,
                       hipStream_t s) {
     constexpr int V = MhVec<T>::V, BN = 64 * V;
-    const bool rw = e.mh_kind == CESX_MH_RW;
+    const bool rw = e.mh.kind == CESX_MH_RW;
     MhArgs<T> a{};
     a.G = (const T*)G; a.y = e.d_y; a.gw = e.d_gw; a.n = e.n;
-    a.X = (const T*)(e.mh_dense_prior ? e.d_mh_w : X);
-    a.mu = rw && !e.mh_dense_prior ? e.d_mu : nullptr;
-    a.sw = rw && !e.mh_dense_prior ? e.d_sw : nullptr;
+    a.X = (const T*)(e.mh.dense_prior ? e.mh.w.get() : X);
+    a.mu = rw && !e.mh.dense_prior ? e.d_mu : nullptr;
+    a.sw = rw && !e.mh.dense_prior ? e.d_sw : nullptr;
     a.nx = rw ? e.p : 0;
     a.P = (const T*)X; a.U = (T*)U; a.p = e.p;
     a.J = e.J; a.c = mh_chains(e, start, logu, step);

@@ -10,6 +10,7 @@ from scipy import stats
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_emulate_host import Enka, build_gps, gold_call, gold_prior, gold_problem, load_gold  # noqa: E402
+from gp_cases import random_gps  # noqa: E402,F401  (test_gpu_emulate_edges.py takes it from here)
 
 pytestmark = pytest.mark.gpu
 FAMILIES = ["RBF", "Matern12", "Matern32", "Matern52"]
@@ -31,21 +32,6 @@ def np_predict(enka, gps, X, nugget=True):
         vars_.append(kern.variance - (W * W).sum(0) + (m.likelihood.variance if nugget else 0.0))
         scale.append(np.abs(Ks * a).sum(1) + np.abs(Z @ img["mw"][i]) + abs(img["par"][i, 2]))
     return np.array(means), np.array(vars_), np.array(scale), img["par"][:, 0]
-
-
-def random_gps(rng, p, n, Jt, family, scaled=False, mean="Linear", lik=1e-4):
-    U = rng.standard_normal((p, Jt))
-    G = np.vstack([np.sin(U[i % p]) + 0.1 * i for i in range(n)])
-    enka = Enka(p, n, U, G)
-    X = U.T
-    if scaled:
-        enka.scale = {"mean": U.mean(axis=1)[:, None], "cov": 2.0 * np.linalg.cholesky(np.cov(U))}
-        enka.scaled = True
-        X = np.linalg.solve(enka.scale["cov"], U - enka.scale["mean"]).T
-    hyp = dict(ls=0.6 + 0.5 * rng.random((n, p)), var=0.5 + rng.random(n), lik=lik * (1 + rng.random(n)),
-               mA=0.3 * rng.standard_normal((n, p)), mb=rng.standard_normal(n))
-    enka.gpmodels = build_gps(X, G, hyp, family, mean)
-    return enka
 
 
 def device_predict(enka, X, nugget=True, var=True, dtype="float64"):

@@ -15,6 +15,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_emulate_host import Enka  # noqa: E402
+from gp_cases import fit_problem  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 FAMILIES = ["RBF", "Matern12", "Matern32", "Matern52"]
@@ -53,10 +54,7 @@ def test_the_cases_cover_what_they_must():
 
 
 def _problem(rng, Jt, p, n=N_GP):
-    X = rng.standard_normal((Jt, p))
-    W = rng.standard_normal((p, n))
-    Y = (np.sin(X @ W) + 0.2 * (X ** 2) @ np.abs(W) + 0.05 * rng.standard_normal((Jt, n))).T
-    return X, Y
+    return fit_problem(rng, Jt, p, n)
 
 
 def _thetas(rng, n, p, ard, mean, sn2=None):

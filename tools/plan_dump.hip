@@ -15,6 +15,10 @@
 #include <cstdio>
 #include <dlfcn.h>
 using namespace cesx;
+namespace cesx {      // devbuf.h's seam: this tool has no device and never allocates (gram_part_alloc is linked in, not called)
+int dev_alloc(void**, size_t, bool) { return 1; }
+void dev_free(void*) {}
+}
 #ifndef DENSE_PLAN_FN      // (a tree without the export: a stand-in of this signature, defined in front of this file)
 static int dense_plan_fn(const int32_t* facts, int32_t* plan) {
     static int (*fn)(const int32_t*, int32_t*) = nullptr;
@@ -116,7 +120,7 @@ static int dump_engine(int argc, char** argv) {
     printf("engine p %d n %d J %lld Jg %lld f64 %d cus %d: rc %d center_u_wgs %d gram_b_short %d\n", e.p, e.n, (long long)e.J,
            (long long)e.Jg, e.cfg.dtype == CESX_F64, e.num_cus, rc, e.center_u_wgs, (int)e.gram_b_short);
     for (int part = 0; part < 2; ++part) {
-        const GramPlan& pl = e.gp[part].plan;
+        const GramPlan& pl = e.gram[part].plan;
         printf(" part %d: tile %d nbr %d nblocks %d ntypes %d max_rb %d nbw %d wgs %d slabs %d rs %d own [%d, %d)\n", part, pl.tile,
                pl.nbr, pl.nblocks, pl.ntypes, pl.max_rb, pl.nbw, pl.total_wgs, pl.total_slabs, pl.total_rs, pl.own_lo, pl.own_hi);
         table("type_hdr", pl.type_hdr); table("rows", pl.rows); table("wblk", pl.wblk); table("blk_rc", pl.blk_rc);
