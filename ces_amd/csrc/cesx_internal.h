@@ -480,6 +480,7 @@ struct Engine {
     GpFitState gf;                     // GP training (cesx_gpfit_*, kernels_gpfit.hip)
     DarcyState dc;                     // Darcy forward map (cesx_darcy_*, kernels_darcy.hip)
     L96State l9;                       // Lorenz '96 forward map (cesx_lorenz_*, kernels_l96.hip)
+    L63State l6;                       // Lorenz '63 forward map (cesx_lorenz_three_*, kernels_l63.hip)
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -775,6 +776,10 @@ int launch_darcy(Engine& e, const void* U, void* G, int* status, hipStream_t s);
 // parameters the descriptor's map takes from U; G = the last window's statistics (engine dtype), W_out = the state at t[-1]
 // (may be W_in), info ([4][J] int32 or nullptr) = status, accepted steps, attempted steps, 0
 int launch_l96(Engine& e, const void* U, const double* W_in, void* G, double* W_out, int* info, hipStream_t s);
+
+// kernels_l63.hip: per column, RK45 of the installed Lorenz '63 model from W_in (3 x J fp64), one particle per lane; G = the
+// nine means of the last window (engine dtype), W_out = the state at t[-1] (may be W_in), info as launch_l96 writes it
+int launch_l63(Engine& e, const void* U, const double* W_in, void* G, double* W_out, int* info, hipStream_t s);
 
 // kernels_gpfit.hip: lml, gradient and status of the GPs gf.idx[0 .. n_active) at gf.theta into gf.out
 int launch_gpfit_eval(Engine& e, int n_active, hipStream_t s);

@@ -1,4 +1,4 @@
-// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gf, dc, l9).  Each owns its
+// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gf, dc, l9, l6).  Each owns its
 // device memory (DevBuf: freed with the struct), says what "nothing installed" is, and has one drop() that establishes it.
 // drop() releases the buffers whose size comes from the installed descriptor and keeps the ones sized by the engine's
 // shape alone (allocated on first use, reused by every later install).  No hip/ header: tools/devbuf_check.cpp runs these
@@ -95,6 +95,14 @@ struct L96State {
     DevBuf<double> t;                  // [n_t] the sample times
     bool none() const { return desc.n_slow == 0; }
     void drop() { desc = cesx_l96_desc{}; t.reset(); }
+};
+
+// ---- Lorenz '63 forward map over the columns (cesx_lorenz_three_*, kernels_l63.hip); state of its own, as the Lorenz '96 map's ----
+struct L63State {
+    cesx_l63_desc desc{};              // the installed descriptor (n_t 0: none; its t points nowhere: the member t)
+    DevBuf<double> t;                  // [n_t] the sample times
+    bool none() const { return desc.n_t == 0; }
+    void drop() { desc = cesx_l63_desc{}; t.reset(); }
 };
 
 }  // namespace cesx

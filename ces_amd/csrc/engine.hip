@@ -384,7 +384,7 @@ int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const 
     const bool whiten = !is_diagonal(n, Gamma);
     e.problem_set = false;
     // a new problem drops the MH proposal (include/cesx.h) and the dense descriptor of CESX_GP_DENSE: both are images of the
-    // problem.  The GP image, the fit problem and the three forward maps (lineal, Darcy, Lorenz '96) stay installed.
+    // problem.  The GP image, the fit problem and the four forward maps (lineal, Darcy, Lorenz '96, Lorenz '63) stay installed.
     e.mh.drop(); e.gpd.drop();
     e.whiten = false;
     e.gw_src = nullptr;
@@ -1538,6 +1538,54 @@ int cesx_lorenz_apply(cesx_handle h, const void* U, const double* W_in, void* G,
     if (e.l9.none()) { e.err = "cesx_lorenz_apply: cesx_lorenz_set has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     return launch_l96(e, U, W_in, G, W_out, info, (hipStream_t)stream);
+}
+
+// ---- Lorenz '63 forward map over the columns (ces_amd/models.py; kernels_l63.hip) ----
+
+// Failure rule as cesx_lorenz_set's: ANY failure leaves the OLD map installed.
+int cesx_lorenz_three_set(cesx_handle h, const cesx_l63_desc* d) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!d || d->struct_bytes != sizeof(cesx_l63_desc)) { e.err = "cesx_lorenz_three_set: bad cesx_l63_desc"; return CESX_EINVAL; }
+    if (e.n != 9) { e.err = "cesx_lorenz_three_set: the handle's n_obs is not 9 (x, y, z, x^2, y^2, z^2, xy, xz, yz)"; return CESX_EINVAL; }
+    for (int k = 0; k < 3; ++k) {
+        if (d->par_row[k] < -1 || d->par_row[k] >= e.p) { e.err = "cesx_lorenz_three_set: par_row out of range"; return CESX_EINVAL; }
+        for (int m = 0; m < k; ++m)
+            if (d->par_row[k] >= 0 && d->par_row[k] == d->par_row[m]) { e.err = "cesx_lorenz_three_set: par_row repeated"; return CESX_EINVAL; }
+        if (d->par_row[k] < 0 && !std::isfinite(d->par_fixed[k])) { e.err = "cesx_lorenz_three_set: a fixed parameter is not finite"; return CESX_EINVAL; }
+    }
+    if (!std::isfinite(d->t0) || !std::isfinite(d->T) || !(d->t0 < d->T)) { e.err = "cesx_lorenz_three_set: t0 < T must be finite"; return CESX_EINVAL; }
+    if (!(d->max_step > 0.0) || !(d->rtol > 0.0) || !(d->atol > 0.0) || !std::isfinite(d->rtol) || !std::isfinite(d->atol)) {
+        e.err = "cesx_lorenz_three_set: max_step, rtol and atol must be positive"; return CESX_EINVAL;
+    }
+    if (d->n_t < 2 || !d->t) { e.err = "cesx_lorenz_three_set: no sample times"; return CESX_EINVAL; }
+    for (int k = 0; k < d->n_t; ++k)
+        if (!(d->t[k] >= d->t0 && d->t[k] <= d->T) || (k && d->t[k] < d->t[k - 1])) {
+            e.err = "cesx_lorenz_three_set: t is not non-decreasing within [t0, T]"; return CESX_EINVAL;
+        }
+    if (d->window_samples < 1 || (d->n_t - 1) % d->window_samples != 0) {
+        e.err = "cesx_lorenz_three_set: n_t - 1 is not a positive multiple of window_samples"; return CESX_EINVAL;
+    }
+    if (d->max_attempts < 1) { e.err = "cesx_lorenz_three_set: max_attempts < 1"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    CESX_HIP(hipDeviceSynchronize());          // (the old sample times may be read by launches still in flight)
+    DevBuf<double> tnew;
+    TRY_BUF(tnew.alloc((size_t)d->n_t * 8));
+    TRY(upload(e, tnew, d->t, (size_t)d->n_t * 8));
+    e.l6.t = std::move(tnew);
+    e.l6.desc = *d;
+    e.l6.desc.t = nullptr;
+    return CESX_OK;
+}
+
+int cesx_lorenz_three_apply(cesx_handle h, const void* U, const double* W_in, void* G, double* W_out, int32_t* info, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U || !W_in || !G || !W_out) { e.err = "cesx_lorenz_three_apply: null pointer"; return CESX_EINVAL; }
+    if (G == U) { e.err = "cesx_lorenz_three_apply: G must not alias U"; return CESX_EINVAL; }
+    if (e.l6.none()) { e.err = "cesx_lorenz_three_apply: cesx_lorenz_three_set has not been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    return launch_l63(e, U, W_in, G, W_out, info, (hipStream_t)stream);
 }
 
 }  // extern "C"

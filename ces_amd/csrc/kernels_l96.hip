@@ -27,6 +27,7 @@
 // a particle's result does not depend on J, on its column or on its neighbours.  Termination is bounded: status 1 h < min_step
 // (scipy's failure), 2 non-finite state or error norm, 3 max_attempts reached; such a particle's outputs are NaN.
 #include "cesx_internal.h"
+#include "rk45_tables.h"
 
 namespace cesx {
 
@@ -43,25 +44,6 @@ struct L96Args {
     int window;
     long long max_attempts;
 };
-
-// Dormand-Prince 5(4): data of the method (scipy/integrate/_ivp/rk.py RK45.A / B / E / P)
-__device__ constexpr double L96_A[6][5] = {
-    {0, 0, 0, 0, 0},
-    {1.0 / 5, 0, 0, 0, 0},
-    {3.0 / 40, 9.0 / 40, 0, 0, 0},
-    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0},
-    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0},
-    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
-__device__ constexpr double L96_B[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
-__device__ constexpr double L96_E[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
-__device__ constexpr double L96_P[7][4] = {
-    {1, -8048581381.0 / 2820520608.0, 8663915743.0 / 2820520608.0, -12715105075.0 / 11282082432.0},
-    {0, 0, 0, 0},
-    {0, 131558114200.0 / 32700410799.0, -68118460800.0 / 10900136933.0, 87487479700.0 / 32700410799.0},
-    {0, -1754552775.0 / 470086768.0, 14199869525.0 / 1410260304.0, -10690763975.0 / 1880347072.0},
-    {0, 127303824393.0 / 49829197408.0, -318862633887.0 / 49829197408.0, 701980252875.0 / 199316789632.0},
-    {0, -282668133.0 / 205662961.0, 2019193451.0 / 616988883.0, -1453857185.0 / 822651844.0},
-    {0, 40617522.0 / 29380423.0, -110615467.0 / 29380423.0, 69997945.0 / 29380423.0}};
 
 // the same value in every lane: butterfly, then lane 0's (the control flow that follows must be wave-uniform)
 __device__ __forceinline__ double l96_wave_sum(double v) {
@@ -194,7 +176,7 @@ void l96_kernel(const L96Args a) {
                 for (int e = 0; e < E; ++e) {
                     double dy = 0.0;
 #pragma unroll
-                    for (int m = 0; m < s; ++m) dy += L96_A[s][m] * K[m][e];
+                    for (int m = 0; m < s; ++m) dy += RK45_A[s][m] * K[m][e];
                     yn[e] = y[e] + dy * h;
                 }
                 l96_rhs<E>(buf, yn, K[s], ks, lane, ns, nf, nst, q);
@@ -203,7 +185,7 @@ void l96_kernel(const L96Args a) {
             for (int e = 0; e < E; ++e) {
                 double dy = 0.0;
 #pragma unroll
-                for (int m = 0; m < 6; ++m) dy += L96_B[m] * K[m][e];
+                for (int m = 0; m < 6; ++m) dy += RK45_B[m] * K[m][e];
                 yn[e] = y[e] + h * dy;
             }
             l96_rhs<E>(buf, yn, K[6], ks, lane, ns, nf, nst, q);
@@ -212,7 +194,7 @@ void l96_kernel(const L96Args a) {
             for (int e = 0; e < E; ++e) {
                 double er = 0.0;
 #pragma unroll
-                for (int m = 0; m < 7; ++m) er += L96_E[m] * K[m][e];
+                for (int m = 0; m < 7; ++m) er += RK45_E[m] * K[m][e];
                 const double w = (er * h) / (atol + fmax(fabs(y[e]), fabs(yn[e])) * rtol);
                 ss += w * w;
                 bad += yn[e] - yn[e];                     // 0, or NaN for a state that is not finite
@@ -245,7 +227,7 @@ void l96_kernel(const L96Args a) {
                 for (int c = 0; c < 4; ++c) {
                     double qc = 0.0;
 #pragma unroll
-                    for (int m = 0; m < 7; ++m) qc += K[m][e] * L96_P[m][c];
+                    for (int m = 0; m < 7; ++m) qc += K[m][e] * RK45_P[m][c];
                     d += qc * pw[c];
                 }
                 ys[e] = h * d + y[e];

@@ -33,10 +33,12 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats", "cesx_mh_phi",
            "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_dense_set",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
-           "cesx_darcy_set", "cesx_darcy_apply", "cesx_lorenz_set", "cesx_lorenz_apply")
+           "cesx_darcy_set", "cesx_darcy_apply", "cesx_lorenz_set", "cesx_lorenz_apply",
+           "cesx_lorenz_three_set", "cesx_lorenz_three_apply")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
               2: "a state or an error norm was not finite",
               3: "max_attempts steps were attempted"}
+L63_STATUS = L96_STATUS                # cesx_lorenz_three_apply reports a particle as cesx_lorenz_apply does
 GPFIT_MEANS = {"zero": 0, "constant": 1, "linear": 2}   # CESX_GPFIT_MEAN_*
 GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2, "dense": 3}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR / _DENSE: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
 GP_DENSE_NMAX = 128                                   # CESX_GP_DENSE_NMAX
@@ -105,6 +107,31 @@ def l96_desc_struct(desc):
     d.T, d.max_step, d.rtol, d.atol = float(desc["T"]), float(desc["max_step"]), float(desc["rtol"]), float(desc["atol"])
     d.n_t, d.t = t.size, t.ctypes.data
     d.spinup_samples, d.window_samples = int(desc["spinup_samples"]), int(desc["window_samples"])
+    d.max_attempts = int(desc.get("max_attempts", 1000000))
+    return d, t
+
+
+class L63Desc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("par_row", C.c_int32 * 3), ("par_fixed", C.c_double * 3),
+                ("par_log", C.c_int32 * 3), ("t0", C.c_double), ("T", C.c_double), ("max_step", C.c_double),
+                ("rtol", C.c_double), ("atol", C.c_double), ("n_t", C.c_int32), ("t", C.c_void_p),
+                ("window_samples", C.c_int32), ("max_attempts", C.c_int64)]
+
+
+def l63_desc_struct(desc):
+    """``desc`` (the dict ``ces_amd.models.lorenz63.device_descriptor`` returns) as a cesx_l63_desc, and the array its ``t``
+    points into (keep it alive for the call)."""
+    t = np.ascontiguousarray(np.asarray(desc["t"], dtype=np.float64).reshape(-1))
+    d = L63Desc()
+    d.struct_bytes = C.sizeof(L63Desc)
+    for k in range(3):
+        d.par_row[k] = int(desc["par_row"][k])
+        d.par_fixed[k] = float(desc["par_fixed"][k])
+        d.par_log[k] = int(desc["par_log"][k])
+    d.t0, d.T = float(desc["t0"]), float(desc["T"])
+    d.max_step, d.rtol, d.atol = float(desc["max_step"]), float(desc["rtol"]), float(desc["atol"])
+    d.n_t, d.t = t.size, t.ctypes.data
+    d.window_samples = int(desc["window_samples"])
     d.max_attempts = int(desc.get("max_attempts", 1000000))
     return d, t
 
@@ -237,6 +264,8 @@ def load_library(path=None):
     lib.cesx_darcy_apply.argtypes = [vp, vp, vp, vp, vp]
     lib.cesx_lorenz_set.argtypes = [vp, C.POINTER(L96Desc)]
     lib.cesx_lorenz_apply.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.cesx_lorenz_three_set.argtypes = [vp, C.POINTER(L63Desc)]
+    lib.cesx_lorenz_three_apply.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     if lib.cesx_abi_version() != ABI_VERSION:
         raise ImportError("libcesx.so ABI %d != binding ABI %d" % (lib.cesx_abi_version(), ABI_VERSION))
     if path == LIB_PATH:
@@ -1084,6 +1113,36 @@ class Engine:
             self._check(self.lib.cesx_lorenz_apply(self._h, U.data_ptr(), W.data_ptr(), out.data_ptr(), W_out.data_ptr(),
                                                 info.data_ptr(), self._stream()))
             self._keep_l96 = (U, W, out, W_out, info)
+        return out, W_out, info
+
+    # -- Lorenz '63 forward map over the columns (include/cesx.h, cesx_lorenz_three_*; ces_amd/models.py builds the descriptor) --
+    def l63_set(self, desc):
+        """Install a Lorenz '63 map: ``desc`` as ``ces_amd.models.lorenz63.device_descriptor`` returns it
+        (cesx_lorenz_three_set; the engine keeps its own copy).  Returns the token that identifies the installed map."""
+        d, t = l63_desc_struct(desc)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_lorenz_three_set(self._h, C.byref(d)))
+        del t
+        self._l63_token = object()
+        return self._l63_token
+
+    def l63_apply(self, U, W, out=None, W_out=None):
+        """(G (9, J) engine dtype, W_out (3, J) fp64, info (4, J) int32) of the installed map for the parameter columns of
+        ``U`` started from the columns of ``W`` (cesx_lorenz_three_apply).  ``W_out`` may be ``W``.  Nothing is read back:
+        ``info[0]`` holds each particle's status (0, or a key of ``L63_STATUS``; such a particle's outputs are NaN)."""
+        if self.__dict__.get("_l63_token") is None:
+            raise CesxError(ESTATE, "l63_apply: l63_set has not been called")
+        if W.dtype != torch.float64 or tuple(W.shape) != (3, self.J) or not W.is_contiguous():
+            raise ValueError("l63_apply: W must be a contiguous float64 tensor of shape %s" % ((3, self.J),))
+        out = self.empty(self.n_obs) if out is None else out
+        W_out = torch.empty((3, self.J), dtype=torch.float64, device=self.device) if W_out is None else W_out
+        if W_out.dtype != torch.float64 or tuple(W_out.shape) != (3, self.J) or not W_out.is_contiguous():
+            raise ValueError("l63_apply: W_out must be a contiguous float64 tensor of shape %s" % ((3, self.J),))
+        info = torch.empty((4, self.J), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_lorenz_three_apply(self._h, U.data_ptr(), W.data_ptr(), out.data_ptr(), W_out.data_ptr(),
+                                                         info.data_ptr(), self._stream()))
+            self._keep_l63 = (U, W, out, W_out, info)
         return out, W_out, info
 
     def profile_enable(self, on=True):

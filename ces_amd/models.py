@@ -5,8 +5,9 @@
 'pde'`` (an ODE solved per particle from a carried state, then summarised into
 observables: ces/calibrate.py:132-168 and ces/utils.py:124-455).  These are host
 code in the reference and the default here (BASELINE.json north_star); the
-two-scale Lorenz '96 family also offers the whole ensemble on the device
-(``set_solver(device=True)`` -> ``forward_pde_device``, cesx_lorenz_*).  The classes keep the reference's names,
+Lorenz '63 pair and the two-scale Lorenz '96 family also offer the whole ensemble on the device
+(``set_solver(device=True)`` -> ``forward_pde_device``, cesx_lorenz_three_* / cesx_lorenz_*), which ``sampling.run`` and
+``MCMC.model_mh(chains=)`` take.  The classes keep the reference's names,
 attributes, call conventions and default arguments so that its notebooks
 (examples/notebooks/{linear,lorenz63}.ipynb) run against ``ces_amd.calibrate``
 unchanged; the right-hand sides are written in vectorised numpy rather than
@@ -27,7 +28,8 @@ class lorenz63(object):
     """Lorenz '63 with (r, b) as parameters, sigma = 10 fixed (ces/utils.py:124-194).
 
     ``solve`` integrates with ``scipy.integrate.odeint`` over the time vector the driver
-    passes (ces/calibrate.py:145); ``statistics`` returns the 9 first and second moments
+    passes (ces/calibrate.py:145) -- with ``solve_ivp`` once ``set_solver`` (build-only) has been
+    called; ``statistics`` returns the 9 first and second moments
     over the LAST window of ``l_window * freq`` samples (the sample at t[0] is dropped,
     ces/utils.py:191-193)."""
 
@@ -53,9 +55,27 @@ class lorenz63(object):
     def __call__(self, w, t, r=28., b=8. / 3):
         return self.model(w, t, 10., r, b)
 
+    def set_solver(self, method="RK45", dt=np.inf, rtol=1e-3, atol=1e-6, device=False):
+        """Build-only (the reference has none): after a call ``solve`` integrates with ``scipy.integrate.solve_ivp`` over
+        ``[t[0], t[-1]]`` (``max_step=dt``) instead of ``odeint``.  ``device=True``: the model also offers
+        ``forward_pde_device``, the whole ensemble integrated on the device (cesx_lorenz_three_*,
+        ces_amd/csrc/kernels_l63.hip: scipy's RK45 restated, one particle per lane).  ``solve`` and ``statistics`` stay the
+        host path either way."""
+        if device and method != "RK45":
+            raise ValueError("lorenz63.set_solver: device=True integrates with RK45 only, not %r" % (method,))
+        self.method, self.dt, self.rtol, self.atol = method, dt, rtol, atol
+        self.solve_init = True
+        if device:
+            self.forward_pde_device = self._forward_pde_device
+        else:
+            self.__dict__.pop("forward_pde_device", None)
+
     def solve(self, w0, t, args=()):
         from scipy import integrate
-        return integrate.odeint(self, w0, t, args=args)
+        if not self.solve_init:
+            return integrate.odeint(self, w0, t, args=args)
+        return integrate.solve_ivp(lambda tt, y: self(y, tt, *args), [t[0], t[-1]], w0, t_eval=t, method=self.method,
+                                   max_step=self.dt, rtol=self.rtol, atol=self.atol).y.T
 
     def statistics(self, ws):
         x, y, z = ws[:, 0], ws[:, 1], ws[:, 2]
@@ -63,6 +83,88 @@ class lorenz63(object):
         win = int(self.l_window * self.freq)
         # adjacent windows over samples 1.. ; the last one is the observable
         return feats[:, 1:].reshape(self.n_obs, -1, win).mean(axis=2)[:, -1]
+
+    # ---- build-only hook: the whole ensemble on the device (cesx_lorenz_three_*) ----
+    n_params = 2
+    DEVICE_PAR_ROW = (-1, 0, 1)                        # the row of U each of (sigma, r, b) is read from, or -1 ...
+    DEVICE_PAR_FIXED = (10., 0., 0.)                   # ... and its fixed value (``__call__`` passes sigma = 10)
+    DEVICE_PAR_LOG = (0, 0, 0)                         # 1: the row holds the parameter's logarithm
+    device_max_attempts = 1000000                      # attempted steps after which a particle ends with status 3
+
+    def device_descriptor(self, t, p=None, n_obs=None):
+        """What cesx_lorenz_three_set takes (include/cesx.h), as a dict built in numpy.  ``ValueError`` with the reason
+        wherever only the host path (``solve`` + ``statistics``, enka.G_pde_ens) applies."""
+        host = "; integrate on the host (model.solve, enka.G_pde_ens) instead"
+        if "forward_pde_device" not in self.__dict__:
+            raise ValueError("lorenz63 forward_pde_device: set_solver(device=True) has not been called" + host)
+        if self.method != "RK45":
+            raise ValueError("lorenz63 forward_pde_device: method %r is not RK45" % (self.method,) + host)
+        if t is None:
+            raise ValueError("lorenz63 forward_pde_device: no sample times t" + host)
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        if n_obs is not None and int(n_obs) != 9:
+            raise ValueError("lorenz63 forward_pde_device: the model's n_obs = 9 differs from the engine's n_obs = %d"
+                             % (n_obs,) + host)
+        if p is not None and int(p) != self.n_params:
+            raise ValueError("lorenz63 forward_pde_device: the model's p = %d differs from the engine's p = %d"
+                             % (self.n_params, p) + host)
+        dt, rtol, atol = float(self.dt), float(self.rtol), float(self.atol)
+        if not dt > 0 or not (rtol > 0 and np.isfinite(rtol)) or not (atol > 0 and np.isfinite(atol)):
+            raise ValueError("lorenz63 forward_pde_device: dt = %r, rtol = %r and atol = %r must be positive"
+                             % (self.dt, self.rtol, self.atol) + host)
+        if t.size < 2 or not np.all(np.isfinite(t)) or np.any(np.diff(t) <= 0):
+            # (solve_ivp: "Values in t_eval are not properly sorted")
+            raise ValueError("lorenz63 forward_pde_device: t must increase" + host)
+        win = int(self.l_window * self.freq)
+        if win != self.l_window * self.freq or win < 1:
+            raise ValueError("lorenz63 forward_pde_device: l_window * freq must be a whole sample count" + host)
+        if t.size - 1 < win or (t.size - 1) % win:
+            # (the reshape of ``statistics`` raises there)
+            raise ValueError("lorenz63 forward_pde_device: the %d samples after the first do not fill whole windows of %d"
+                             % (t.size - 1, win) + host)
+        return dict(n_obs=9, p=int(self.n_params), par_row=np.asarray(self.DEVICE_PAR_ROW, dtype=np.int32),
+                    par_fixed=np.asarray(self.DEVICE_PAR_FIXED, dtype=np.float64),
+                    par_log=np.asarray(self.DEVICE_PAR_LOG, dtype=np.int32),
+                    t0=float(t[0]), T=float(t[-1]), max_step=dt, rtol=rtol, atol=atol, t=t,
+                    window_samples=win, max_attempts=int(self.device_max_attempts))
+
+    def _fingerprint(self, t):
+        return (type(self).__name__, tuple(self.DEVICE_PAR_ROW), tuple(float(v) for v in self.DEVICE_PAR_FIXED),
+                tuple(self.DEVICE_PAR_LOG), self.method, float(self.dt), float(self.rtol), float(self.atol),
+                float(self.l_window), float(self.freq), int(self.device_max_attempts),
+                np.asarray(t, dtype=np.float64).tobytes())
+
+    def invalidate_device(self):
+        """Forget the map installed in an engine: the next ``forward_pde_device`` builds and installs the descriptor again."""
+        self._dev_fp = None
+        self._dev_token = 0
+
+    def ensure_installed(self, engine, t):
+        """Make THIS model the Lorenz '63 map installed in ``engine``: installed once, again when any field of the descriptor
+        changed or another model installed its own on the same engine (``invalidate_device()`` forces it)."""
+        fp = self._fingerprint(t)
+        if (getattr(self, "_dev_fp", None) != fp
+                or getattr(engine, "_l63_token", None) is not getattr(self, "_dev_token", 0)):
+            desc = self.device_descriptor(t, engine.p, engine.n_obs)
+            self._dev_token = engine.l63_set(desc)
+            self._dev_fp = fp
+
+    def _forward_pde_device(self, engine, U_dev, W_dev, t, out=None, W_out=None, check=True):
+        """(G (9, J), W_next (3, J) fp64) on the device: every column of ``U_dev`` integrated from its column of ``W_dev``
+        over ``t`` (what enka.G_pde does per particle).  ``check`` (default): read the status words -- synchronises -- and
+        raise ``ValueError`` naming the first particle that failed.  ``check=False`` reads nothing back: a failed particle's
+        outputs are NaN (``MCMC.model_mh(chains=)`` rejects such a proposal)."""
+        self.ensure_installed(engine, t)
+        G, W_next, info = engine.l63_apply(U_dev, W_dev, out=out, W_out=W_out)
+        if check:
+            status = info[0].cpu().numpy()
+            bad = np.flatnonzero(status)
+            if bad.size:
+                from .engine import L63_STATUS
+                j = int(bad[0])
+                raise ValueError("lorenz63 forward_pde_device: particle %d failed with status %d: %s"
+                                 % (j, status[j], L63_STATUS.get(int(status[j]), "unknown")))
+        return G, W_next
 
 
 class lorenz63_log(lorenz63):
@@ -77,6 +179,8 @@ class lorenz63_log(lorenz63):
 
     def __call__(self, w, t, log_r=np.log(28.), log_b=np.log(8. / 3)):
         return self.model(w, t, 10., log_r, log_b)
+
+    DEVICE_PAR_LOG = (0, 1, 1)                         # r = exp(U[0]), b = exp(U[1])
 
     def grad_logjacobian(self, params):
         return -np.exp(-params)
@@ -251,20 +355,22 @@ class lorenz96(object):
             self._dev_token = engine.l96_set(desc)
             self._dev_fp = fp
 
-    def _forward_pde_device(self, engine, U_dev, W_dev, t, out=None, W_out=None):
+    def _forward_pde_device(self, engine, U_dev, W_dev, t, out=None, W_out=None, check=True):
         """(G (n_obs, J), W_next (n_state, J) fp64) on the device: every column of ``U_dev`` integrated from its column of
         ``W_dev`` over ``t`` (what enka.G_pde does per particle).  ``ValueError`` names the first particle that failed --
         the exception the host path ends in (``statistics``' reshape of a truncated solution).  Reads the status words:
-        synchronises."""
+        synchronises.  ``check=False`` reads nothing back and raises nothing: a failed particle's outputs are NaN
+        (``MCMC.model_mh(chains=)`` rejects such a proposal)."""
         self.ensure_installed(engine, t)
         G, W_next, info = engine.l96_apply(U_dev, W_dev, out=out, W_out=W_out)
-        status = info[0].cpu().numpy()
-        bad = np.flatnonzero(status)
-        if bad.size:
-            from .engine import L96_STATUS
-            j = int(bad[0])
-            raise ValueError("lorenz96 forward_pde_device: particle %d failed with status %d: %s"
-                             % (j, status[j], L96_STATUS.get(int(status[j]), "unknown")))
+        if check:
+            status = info[0].cpu().numpy()
+            bad = np.flatnonzero(status)
+            if bad.size:
+                from .engine import L96_STATUS
+                j = int(bad[0])
+                raise ValueError("lorenz96 forward_pde_device: particle %d failed with status %d: %s"
+                                 % (j, status[j], L96_STATUS.get(int(status[j]), "unknown")))
         return G, W_next
 
     def grad_logjacobian(self, params):

@@ -11,7 +11,10 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          of the engine's (p, M) layout, the proposal an update launch, then for model_mh the forward map
                          ``model.forward_device`` and ``mh_accept_kernel``, for gp_mh the batched GP prediction
                          ``gp_predict_kernel`` (fp64, MFMA) and ``gp_score_kernel``.  model_mh needs a model with
-                         ``forward_device`` (``ces_amd.utils.lineal``); gp_mh needs this package's ``emulate.GPR`` models,
+                         ``forward_device`` (``ces_amd.utils.lineal``) or, ``type == 'pde'``, ``forward_pde_device``
+                         (``ces_amd.models`` lorenz63 / lorenz96 after ``set_solver(device=True)``: every chain integrates
+                         from ``model.wt`` over ``model.t``; a proposal whose integration fails scores NaN and is
+                         rejected, a start state that fails raises ``ValueError``); gp_mh needs this package's ``emulate.GPR`` models,
                          one per output, and keeps ``separable`` and ``noise_compounded`` with a dense Gamma and no
                          ``pca_tools`` on the host (ValueError).  Both need a prior with ``.mean`` / ``.cov`` (a frozen
                          ``scipy.stats.multivariate_normal``).
@@ -312,10 +315,11 @@ class MCMC(object):
 
     def _model_mh_device(self, model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, kwargs):
         from .utils import hook_takes_out
-        if getattr(model, "type", None) == "pde" or not hasattr(model, "forward_device"):
+        pde = getattr(model, "type", None) == "pde"
+        if not hasattr(model, "forward_pde_device" if pde else "forward_device"):
             raise ValueError("chains=: the device path evaluates the forward map on the GPU through model.forward_device, "
-                             "which %r does not offer ('pde' models keep their forward map on the host); run model_mh "
-                             "without chains=" % (model,))
+                             "which %r does not offer (a 'pde' model offers it as forward_pde_device after "
+                             "set_solver(device=True)); run model_mh without chains=" % (model,))
         p, n = enka.p, enka.n_obs
 
         def scales_of(update):                            # exactly as the reference forms them (:122-129)
@@ -324,6 +328,33 @@ class MCMC(object):
             else:
                 scales = delta * np.eye(p)
             return np.linalg.cholesky(prior.cov) if update == "pCN" else scales
+
+        def bind_pde(eng, M):
+            # ces/sample.py:133-137, :170-173: every evaluation starts from model.wt at model.t; the start states W are
+            # resident and never advanced (the reference keeps w_mcmc fixed), the end states go to a scratch buffer
+            import torch
+            ns = int(model.n_state)
+            wt = np.asarray(model.wt, dtype=np.float64).reshape(ns)
+            W = torch.as_tensor(np.ascontiguousarray(np.tile(wt, M).reshape(M, ns).T), device=eng.device)
+            W_scratch = torch.empty_like(W)
+            G, GP = eng.empty(n), eng.empty(n)
+
+            def fwd(u, out):
+                # check=False: nothing is read back; a state whose integration fails has NaN observables
+                model.forward_pde_device(eng, u, W, model.t, out=out, W_out=W_scratch, check=False)
+
+            def score_start(U):
+                fwd(U, G)
+                bad = torch.nonzero(torch.isnan(G).any(dim=0)).reshape(-1)
+                if bad.numel():
+                    raise ValueError("chains=: the forward model failed at the start state of chain %d (its integration "
+                                     "did not finish: no phi to compare a proposal with)" % int(bad[0]))
+                eng.mh_start(U, G)
+
+            def score_accept(step, U, P, logu):       # phi(P) NaN for a failed integration: the test rejects (mh_test)
+                fwd(P, GP)
+                eng.mh_accept(step, U, P, GP, logu=logu)
+            return score_start, score_accept
 
         def bind(eng, M):
             takes_out = hook_takes_out(model.forward_device)
@@ -344,7 +375,7 @@ class MCMC(object):
                 eng.mh_accept(step, U, P, GP, logu=logu)
             return score_start, score_accept
 
-        self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi=True)
+        self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_pde if pde else bind, resume_keeps_start_phi=True)
 
     def _gp_mh_device(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
         import torch
