@@ -477,6 +477,7 @@ struct Engine {
     MhState mh;                        // Metropolis-Hastings over the columns (cesx_mh_*, kernels_mh.hip)
     GpState gp;                        // GP emulator over the columns (cesx_gp_*, kernels_gp.hip)
     GpDenseState gpd;                  // the dense per-chain Sigma of CESX_GP_DENSE (cesx_gp_dense_set, kernels_gpdense.hip)
+    GpProjState gpp;                   // Sigma projected to k x k of CESX_GP_PROJ (cesx_gp_proj_set, kernels_gpproj.hip)
     GpFitState gf;                     // GP training (cesx_gpfit_*, kernels_gpfit.hip)
     DarcyState dc;                     // Darcy forward map (cesx_darcy_*, kernels_darcy.hip)
     L96State l9;                       // Lorenz '96 forward map (cesx_lorenz_*, kernels_l96.hip)
@@ -765,6 +766,11 @@ int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double
 int gp_dense_prepare(Engine& e, int n, int k);
 int launch_gp_score_dense(Engine& e, bool start, const void* X, const double* mean, const double* var, void* U,
                           const double* logu, unsigned step, hipStream_t s);
+// kernels_gpproj.hip: the same for CESX_GP_PROJ -- I_k + R diag(var_j) R^T factored per chain by a sub-wave group of lanes;
+// mean and var are (gpp.k x J).  gp_proj_prepare: once per installed descriptor (the kernels' dynamic LDS limit for k)
+int gp_proj_prepare(Engine& e, int k);
+int launch_gp_score_proj(Engine& e, bool start, const void* X, const double* mean, const double* var, void* U,
+                         const double* logu, unsigned step, hipStream_t s);
 
 // kernels_darcy.hip: G = the installed Darcy map of the columns of U (engine dtype in and out, fp64 inside); status (J int32,
 // or nullptr): 0, the 1-based column of the zero pivot of a particle whose outputs are NaN, or minus the column that held a

@@ -1,4 +1,4 @@
-// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gf, dc, l9, l6).  Each owns its
+// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gpp, gf, dc, l9, l6).  Each owns its
 // device memory (DevBuf: freed with the struct), says what "nothing installed" is, and has one drop() that establishes it.
 // drop() releases the buffers whose size comes from the installed descriptor and keeps the ones sized by the engine's
 // shape alone (allocated on first use, reused by every later install).  No hip/ header: tools/devbuf_check.cpp runs these
@@ -56,6 +56,17 @@ struct GpDenseState {
     DevBuf<double> y, Gam;             // [n], [n][n] the unwhitened problem on the device
     bool none() const { return k == 0; }
     void drop() { k = 0; }             // every buffer is sized by the engine: kept
+};
+
+// ---- Sigma projected to k x k of CESX_GP_PROJ (cesx_gp_proj_set, kernels_gpproj.hip) ----
+struct GpProjState {
+    int k = 0, logdet = 0;             // the order of R (0: no descriptor; cesx_set_problem drops it), the log det term
+    double c_perp = 0.0;               // |(I - Q Q^T) r0|^2, the part of the quadratic form no chain changes
+    double half_logdet_gamma = 0.0;    // sum log diag(L_Gamma)
+    DevBuf<double> R, Rt;              // R [k][k] (zero below the diagonal) and its transpose; both KMAX x KMAX: every k fits
+    DevBuf<double> a0;                 // [k] Q^T r0
+    bool none() const { return k == 0; }
+    void drop() { k = 0; }             // every buffer is sized by CESX_GP_PROJ_KMAX: kept
 };
 
 // ---- GP training: batched likelihood and gradient (cesx_gpfit_*, kernels_gpfit.hip) ----

@@ -383,9 +383,9 @@ int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const 
     //  the handle WITHOUT a problem -- cesx_moments* / cesx_apply then return CESX_ESTATE -- instead of half of the new one)
     const bool whiten = !is_diagonal(n, Gamma);
     e.problem_set = false;
-    // a new problem drops the MH proposal (include/cesx.h) and the dense descriptor of CESX_GP_DENSE: both are images of the
-    // problem.  The GP image, the fit problem and the four forward maps (lineal, Darcy, Lorenz '96, Lorenz '63) stay installed.
-    e.mh.drop(); e.gpd.drop();
+    // a new problem drops the MH proposal (include/cesx.h) and the descriptors of CESX_GP_DENSE and CESX_GP_PROJ: all are images
+    // of the problem.  The GP image, the fit problem and the four forward maps (lineal, Darcy, Lorenz '96, Lorenz '63) stay installed.
+    e.mh.drop(); e.gpd.drop(); e.gpp.drop();
     e.whiten = false;
     e.gw_src = nullptr;
     // the problem as given, for the one mode that factors Sigma_j = Gamma + B diag(v_j) B^T itself (kernels_gpdense.hip)
@@ -1058,6 +1058,46 @@ int cesx_gp_dense_set(cesx_handle h, const cesx_gp_dense_desc* d) {
     return CESX_OK;
 }
 
+// Failure rule: as cesx_gp_dense_set's.
+int cesx_gp_proj_set(cesx_handle h, const cesx_gp_proj_desc* d) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!d || d->struct_bytes != sizeof(cesx_gp_proj_desc)) { e.err = "cesx_gp_proj_set: bad cesx_gp_proj_desc"; return CESX_EINVAL; }
+    if (d->k < 1 || d->k > CESX_GP_PROJ_KMAX) { e.err = "cesx_gp_proj_set: k must be in 1 .. 128 (the factor of I + S lives in LDS)"; return CESX_EINVAL; }
+    if (!d->R || !d->a0) { e.err = "cesx_gp_proj_set: null pointer"; return CESX_EINVAL; }
+    const int k = d->k;
+    // R with its zeros below the diagonal (only the upper triangle is read) and its transpose
+    std::vector<double> R((size_t)k * k, 0.0), Rt((size_t)k * k, 0.0);
+    bool finite = std::isfinite(d->c_perp) && std::isfinite(d->half_logdet_gamma);
+    for (int i = 0; i < k; ++i) {
+        finite = finite && std::isfinite(d->a0[i]);
+        for (int t = i; t < k; ++t) {
+            const double r = d->R[(size_t)i * k + t];
+            finite = finite && std::isfinite(r);
+            R[(size_t)i * k + t] = Rt[(size_t)t * k + i] = r;
+        }
+    }
+    if (!finite) { e.err = "cesx_gp_proj_set: a non-finite entry in R, a0, c_perp or half_logdet_gamma"; return CESX_EINVAL; }
+    if (d->c_perp < 0.0) { e.err = "cesx_gp_proj_set: c_perp must be >= 0"; return CESX_EINVAL; }
+    if (!e.problem_set) { e.err = "cesx_gp_proj_set: cesx_set_problem has not been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    CESX_HIP(hipDeviceSynchronize());          // (the old image may be read by launches still in flight)
+    e.gpp.drop();
+    // for the largest k once: a later descriptor fits
+    const size_t kmax = CESX_GP_PROJ_KMAX;
+    TRY_BUF(e.gpp.R.ensure(kmax * kmax * 8));
+    TRY_BUF(e.gpp.Rt.ensure(kmax * kmax * 8));
+    TRY_BUF(e.gpp.a0.ensure(kmax * 8));
+    TRY(upload(e, e.gpp.R, R.data(), R.size() * 8)); TRY(upload(e, e.gpp.Rt, Rt.data(), Rt.size() * 8));
+    TRY(upload(e, e.gpp.a0, d->a0, (size_t)k * 8));
+    TRY(gp_proj_prepare(e, k));
+    e.gpp.c_perp = d->c_perp; e.gpp.half_logdet_gamma = d->half_logdet_gamma;
+    e.gpp.logdet = d->logdet ? 1 : 0;
+    e.gpp.k = k;
+    return CESX_OK;
+}
+
 int cesx_mh_phi(cesx_handle h, double* phi_host) {
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
@@ -1076,6 +1116,12 @@ static int gp_check_mode(Engine& e, int mode, const double* mean, const double* 
         if (e.gp.n != e.gpd.k) { e.err = "cesx_gp: the emulator's n_gp differs from the descriptor's k"; return CESX_EINVAL; }
         return CESX_OK;
     }
+    if (mode == CESX_GP_PROJ) {
+        if (e.gpp.none()) { e.err = "cesx_gp: CESX_GP_PROJ needs a descriptor (cesx_gp_proj_set after cesx_set_problem)"; return CESX_ESTATE; }
+        if (!mean || !var) { e.err = "cesx_gp: null pointer"; return CESX_EINVAL; }
+        if (e.gp.n != e.gpp.k) { e.err = "cesx_gp: the emulator's n_gp differs from the descriptor's k"; return CESX_EINVAL; }
+        return CESX_OK;
+    }
     if (mode != CESX_GP_GAMMA && mode != CESX_GP_VAR && mode != CESX_GP_GAMMA_VAR) { e.err = "cesx_gp: unknown likelihood mode"; return CESX_EINVAL; }
     if (!mean || (mode != CESX_GP_GAMMA && !var)) { e.err = "cesx_gp: null pointer"; return CESX_EINVAL; }
     if (mode != CESX_GP_GAMMA && e.whiten) { e.err = "cesx_gp: the variance modes need a diagonal Gamma"; return CESX_EINVAL; }
@@ -1092,6 +1138,7 @@ int cesx_gp_start(cesx_handle h, int mode, const void* U, const double* mean, co
     SET_DEVICE(e);
     FLUSH(e);
     if (mode == CESX_GP_DENSE) TRY(launch_gp_score_dense(e, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
+    else if (mode == CESX_GP_PROJ) TRY(launch_gp_score_proj(e, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
     else TRY(launch_gp_score(e, mode, true, U, mean, var, nullptr, nullptr, 0u, (hipStream_t)stream));
     e.mh.started = true;
     e.mh.steps = 0;
@@ -1109,6 +1156,7 @@ int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U, const 
     SET_DEVICE(e);
     FLUSH(e);
     if (mode == CESX_GP_DENSE) TRY(launch_gp_score_dense(e, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    else if (mode == CESX_GP_PROJ) TRY(launch_gp_score_proj(e, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
     else TRY(launch_gp_score(e, mode, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
     ++e.mh.steps;
     return CESX_OK;

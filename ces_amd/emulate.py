@@ -20,7 +20,9 @@ The GP (the notebooks' ``emulate(enki)`` needs GPflow 1.x; this is its exact-GPR
   gradient, the positive parameters through softplus with a 1e-6 floor (GPflow 1.x's default ``positive`` transform as far
   as can be told without GPflow).  ``train_gps(enka, kernel='Matern32', ...)`` is the notebook's ``emulate(enki)``.
 
-Build-only: ``predict_gps(..., device=True)`` evaluates the GPs on the GPU (``cesx_gp_predict``, kernels_gp.hip);
+Build-only: ``predict_gps(..., device=True)`` evaluates the GPs on the GPU (``cesx_gp_predict``, kernels_gp.hip), with
+``pca_tools`` the k GPs there and the back-projection on the host; ``project_sigma`` is the host reduction behind
+``gp_mh(chains=, pca_tools=, sigma_form='projected')``;
 ``train_gps(..., device=True)`` fits all emulators at once, the same ``ScipyOptimizer`` per GP, the likelihood and its
 gradient of every GP in one batched GPU evaluation per optimiser step (``fit_lockstep``, ``cesx_gpfit_eval``,
 kernels_gpfit.hip).
@@ -28,6 +30,7 @@ kernels_gpfit.hip).
 import threading
 
 import numpy as np
+from scipy import linalg as sla
 from scipy import optimize
 
 try:
@@ -661,9 +664,41 @@ def device_image(enka, gpmodels):
     return dict(n=n, Jt=Jt, p=p, A=A, c=c, Z=Z, family=fam, par=par, mw=mw, alpha=alpha, Li=Li)
 
 
+def project_sigma(Gamma, VD_k, mG, y):
+    """The host reduction behind ``gp_mh(chains=, pca_tools=, sigma_form='projected')`` (mode CESX_GP_PROJ, include/cesx.h),
+    once per problem.  With Gamma = L L^T, W = L^{-1} VD_k = Q R (thin QR) and r0 = L^{-1} (mG - y):
+        Sigma(v) = L (I + Q R diag(v) R^T Q^T) L^T,    L^{-1} d(m) = Q (a0 + R m) + r_perp,    a0 = Q^T r0,
+    returns ``(R (k, k) upper triangular, a0 (k,), c_perp = |r_perp|^2, half_logdet_gamma = sum log diag(L))``.
+    r_perp = (I - Q Q^T) r0 is formed with one re-orthogonalisation pass.  A rank-deficient VD_k needs no special case (Q is
+    orthonormal all the same).  Raises ValueError for non-finite inputs and for a Gamma that is not positive definite."""
+    Gamma = np.asarray(Gamma, dtype=np.float64)
+    n = Gamma.shape[0]
+    VD_k = np.asarray(VD_k, dtype=np.float64)
+    if Gamma.shape != (n, n) or VD_k.ndim != 2 or VD_k.shape[0] != n or not 1 <= VD_k.shape[1] <= n:
+        raise ValueError("project_sigma: Gamma %s and VD_k %s do not go together as (n, n) and (n, k <= n)" % (Gamma.shape, VD_k.shape))
+    mG, y = np.asarray(mG, dtype=np.float64).reshape(-1), np.asarray(y, dtype=np.float64).reshape(-1)
+    if mG.shape != (n,) or y.shape != (n,):
+        raise ValueError("project_sigma: mG and y must hold n = %d values" % n)
+    for name, arr in (("Gamma", Gamma), ("VD_k", VD_k), ("mG", mG), ("y", y)):
+        if not np.all(np.isfinite(arr)):
+            raise ValueError("project_sigma: %s has a non-finite entry" % name)
+    try:
+        L = np.linalg.cholesky(Gamma)
+    except np.linalg.LinAlgError:
+        raise ValueError("project_sigma: Gamma is not positive definite")
+    W = sla.solve_triangular(L, VD_k, lower=True)
+    r0 = sla.solve_triangular(L, mG - y, lower=True)
+    Q, R = np.linalg.qr(W)
+    a0 = Q.T @ r0
+    rp = r0 - Q @ a0
+    fix = Q.T @ rp                                         # the re-orthogonalisation pass
+    a0, rp = a0 + fix, rp - Q @ fix
+    return np.triu(R), a0, float(rp @ rp), float(np.log(np.diag(L)).sum())
+
+
 def _predict_gps_device(enka, X, gpmodels, kwargs):
-    if kwargs.get('separable', False) or kwargs.get('pca_tools', None) is not None:
-        raise ValueError("predict_gps(device=True): separable and pca_tools run on the host")
+    if kwargs.get('separable', False):
+        raise ValueError("predict_gps(device=True): separable runs on the host")
     from . import engine as _engine
     img = device_image(enka, gpmodels)
     X = np.asarray(X, dtype=np.float64)
@@ -673,4 +708,9 @@ def _predict_gps_device(enka, X, gpmodels, kwargs):
     eng.gp_set(img)
     Xd = eng.to_device(np.ascontiguousarray(X.T), p, "gp_X")
     mean, var = eng.gp_predict(Xd, nugget=kwargs.get('nugget', True), var=True)
-    return [mean.cpu().numpy(), var.cpu().numpy()]
+    gpmeans, gpvars = mean.cpu().numpy(), var.cpu().numpy()
+    if kwargs.get('pca_tools', None) is not None:          # the back-projection of the host path (ces/emulate.py:74-77)
+        pca_tools = kwargs.get('pca_tools')
+        gpmeans = pca_tools['VD_k'].dot(gpmeans) + pca_tools['mG']
+        gpvars = pca_tools['VD_k'].dot(np.diag(gpvars.flatten())).dot(pca_tools['VD_k'].T)
+    return [gpmeans, gpvars]

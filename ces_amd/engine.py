@@ -18,7 +18,7 @@ OK, EINVAL, ENOTPD, EHIP, ESTATE, EUNSUPPORTED, ENOCONV = 0, 1, 2, 3, 4, 5, 6
 F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
-ABI_VERSION = 4
+ABI_VERSION = 5
 MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
@@ -31,7 +31,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_profile_clock", "cesx_calibrate_mfma", "cesx_profile_gap", "cesx_moments_rest_lineal", "cesx_copy_cols_async",
            "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count",
            "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats", "cesx_mh_phi",
-           "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_dense_set",
+           "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_dense_set", "cesx_gp_proj_set",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_lorenz_set", "cesx_lorenz_apply",
            "cesx_lorenz_three_set", "cesx_lorenz_three_apply")
@@ -40,8 +40,9 @@ L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's 
               3: "max_attempts steps were attempted"}
 L63_STATUS = L96_STATUS                # cesx_lorenz_three_apply reports a particle as cesx_lorenz_apply does
 GPFIT_MEANS = {"zero": 0, "constant": 1, "linear": 2}   # CESX_GPFIT_MEAN_*
-GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2, "dense": 3}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR / _DENSE: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
+GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2, "dense": 3, "proj": 4}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR / _DENSE / _PROJ: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
 GP_DENSE_NMAX = 128                                   # CESX_GP_DENSE_NMAX
+GP_PROJ_KMAX = 128                                    # CESX_GP_PROJ_KMAX
 
 
 class Config(C.Structure):
@@ -72,6 +73,11 @@ class GpDesc(C.Structure):
 
 class GpDenseDesc(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("k", C.c_int32), ("logdet", C.c_int32), ("B", C.c_void_p), ("g0", C.c_void_p)]
+
+
+class GpProjDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("k", C.c_int32), ("logdet", C.c_int32), ("R", C.c_void_p), ("a0", C.c_void_p),
+                ("c_perp", C.c_double), ("half_logdet_gamma", C.c_double)]
 
 
 class GpFitDesc(C.Structure):
@@ -255,6 +261,7 @@ def load_library(path=None):
     lib.cesx_gp_start.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.cesx_gp_accept.argtypes = [vp, i32, u64, vp, vp, vp, vp, vp, vp]
     lib.cesx_gp_dense_set.argtypes = [vp, C.POINTER(GpDenseDesc)]
+    lib.cesx_gp_proj_set.argtypes = [vp, C.POINTER(GpProjDesc)]
     lib.cesx_mh_phi.argtypes = [vp, dp]
     lib.cesx_gpfit_set.argtypes = [vp, C.POINTER(GpFitDesc)]
     lib.cesx_gpfit_ntheta.argtypes = [vp]
@@ -964,6 +971,21 @@ class Engine:
                         None if g0 is None else g0.ctypes.data)
         with torch.cuda.device(self.device):
             self._check(self.lib.cesx_gp_dense_set(self._h, C.byref(d)))
+
+    def gp_proj_set(self, R, a0, c_perp, half_logdet_gamma, logdet=False):
+        """The descriptor of mode 'proj' (cesx_gp_proj_set), as ``ces_amd.emulate.project_sigma`` returns it: R (k, k) upper
+        triangular, a0 (k,), c_perp >= 0 and half_logdet_gamma; logdet: add 1/2 log det Sigma.  Needs the problem; a later
+        set_problem drops it.  In mode 'proj' gp_start / gp_accept take (k, J) mean and variance rows; n_obs is free."""
+        R = np.ascontiguousarray(np.asarray(R, dtype=np.float64))
+        if R.ndim != 2 or R.shape[0] != R.shape[1]:
+            raise ValueError("gp_proj_set: R has shape %s, expected (k, k)" % (R.shape,))
+        a0 = np.ascontiguousarray(np.asarray(a0, dtype=np.float64).reshape(-1))
+        if a0.shape != (R.shape[0],):
+            raise ValueError("gp_proj_set: a0 has %d values, expected %d" % (a0.size, R.shape[0]))
+        d = GpProjDesc(C.sizeof(GpProjDesc), R.shape[0], 1 if logdet else 0, R.ctypes.data if R.size else None,
+                       a0.ctypes.data if a0.size else None, float(c_perp), float(half_logdet_gamma))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_proj_set(self._h, C.byref(d)))
 
     def gp_predict(self, X, nugget=True, var=True, out=None):
         """(mean, var) float64 device tensors (n_gp, J) of the installed GPs at the columns of X (cesx_gp_predict);

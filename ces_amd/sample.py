@@ -24,6 +24,10 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          one wave (``gp_score_dense_kernel``, n <= 128), with 1/2 log det Sigma when
                          ``noise_compounded``.  ``pca_tools=dict(VD_k=np.eye(n), mG=np.zeros((n, 1)))`` gives the dense
                          compounded likelihood ``Gamma + diag(gvars)`` of :50-51 on the device.
+  kwarg ``sigma_form``   with ``chains=``: 'dense' (default, the route above) or 'projected' -- needs ``pca_tools`` and
+                         ``Gamma``; the same likelihood with Sigma projected to k x k (``emulate.project_sigma`` once on the
+                         host, then ``gp_score_proj_kernel``: a k x k Cholesky per chain, several chains per wave), for any
+                         n_obs and k <= 128.
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -78,6 +82,9 @@ class MCMC(object):
                               "not installed; ces/sample.py fails when it imports gpflow, :8)")
         if kwargs.get("chains", None) is not None:
             return self._gp_mh_device(enka, n_mcmc, prior, delta, enka_scaling, kwargs)
+        if kwargs.get("sigma_form", None) is not None:
+            raise ValueError("sigma_form=%r chooses between the device kernels of chains=M; the host path has one form"
+                             % (kwargs.get("sigma_form"),))
         from . import emulate
         if enka_scaling:
             scales = delta * np.linalg.cholesky(np.cov(enka.Ustar))
@@ -390,13 +397,19 @@ class MCMC(object):
         pca = kwargs.get("pca_tools", None)
         Gamma = kwargs.get("Gamma", None)
         n_gp, VD_k, mG, logdet = n, None, None, False
+        form = kwargs.get("sigma_form", "dense")
+        if form not in ("dense", "projected"):
+            raise ValueError("chains=: unknown sigma_form %r ('dense' or 'projected')" % (form,))
+        if form == "projected" and pca is None:
+            raise ValueError("chains=: sigma_form='projected' projects the Sigma of pca_tools to k x k and needs pca_tools")
         if pca is not None:                               # Sigma = Gamma + VD_k diag(gvars) VD_k^T (:52-53), dense per chain
             if Gamma is None:
                 raise ValueError("chains=: pca_tools needs Gamma (the reference adds the (n, n) gvars of pca_tools to it, "
                                  "ces/sample.py:52-53, and cannot run without)")
-            if n > _engine.GP_DENSE_NMAX:
+            if form == "dense" and n > _engine.GP_DENSE_NMAX:
                 raise ValueError("chains=: pca_tools factors an n x n Sigma per chain in LDS, n_obs <= %d (got %d)"
-                                 % (_engine.GP_DENSE_NMAX, n) + host)
+                                 % (_engine.GP_DENSE_NMAX, n) + host + ", or pass sigma_form='projected' (k <= %d, any n_obs)"
+                                 % _engine.GP_PROJ_KMAX)
             VD_k = np.asarray(pca["VD_k"], dtype=np.float64)
             if VD_k.ndim != 2 or VD_k.shape[0] != n or not 1 <= VD_k.shape[1] <= n:
                 raise ValueError("chains=: pca_tools['VD_k'] has shape %s, expected (n_obs, k) = (%d, k <= %d)"
@@ -410,6 +423,12 @@ class MCMC(object):
                 raise ValueError("chains=: %d GPs for the k = %d columns of pca_tools['VD_k']" % (len(gpmodels), n_gp))
             logdet = bool(kwargs.get("noise_compounded", False))      # (:69-72)
             mode, G = "dense", np.asarray(Gamma, dtype=np.float64).reshape(n, n)
+            if form == "projected":
+                if n_gp > _engine.GP_PROJ_KMAX:
+                    raise ValueError("chains=: sigma_form='projected' factors a k x k matrix per chain in LDS, k <= %d (got %d)"
+                                     % (_engine.GP_PROJ_KMAX, n_gp) + host)
+                mode = "proj"
+                proj = emulate.project_sigma(G, VD_k, mG, np.asarray(self.y_obs, dtype=np.float64).reshape(n))
         elif len(gpmodels) != n:
             raise ValueError("chains=: %d GPs for n_obs = %d" % (len(gpmodels), n) + host)
         elif Gamma is None:                               # Sigma = diag(gvars) (:48-49)
@@ -435,6 +454,8 @@ class MCMC(object):
             eng.gp_set(img)
             if mode == "dense":
                 eng.gp_dense_set(VD_k, mG, logdet)
+            elif mode == "proj":
+                eng.gp_proj_set(*proj, logdet)
             nugget, want_var = kwargs.get("nugget", True), mode != "gamma"
             rows = lambda: torch.empty((n_gp, M), dtype=torch.float64, device=eng.device)    # noqa: E731
             mean_u, mean_p = rows(), rows()

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CESX_ABI_VERSION 4
+#define CESX_ABI_VERSION 5
 
 /* status codes */
 #define CESX_OK            0
@@ -561,6 +561,7 @@ int cesx_gp_predict(cesx_handle h, const void* X_dev, double* mean_dev, double* 
 #define CESX_GP_VAR        1
 #define CESX_GP_GAMMA_VAR  2
 #define CESX_GP_DENSE      3
+#define CESX_GP_PROJ       4
 int cesx_gp_start(cesx_handle h, int mode, const void* U_dev, const double* mean_dev, const double* var_dev, void* stream);
 int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev, const void* P_dev, const double* mean_dev,
                    const double* var_dev, const double* logu_dev, void* stream);
@@ -585,6 +586,32 @@ typedef struct {
    cesx_set_problem drops the descriptor, as it drops the proposal.  cesx_gp_start / cesx_gp_accept in mode CESX_GP_DENSE
    return CESX_ESTATE without one, and need var_dev and n_gp == k. */
 int cesx_gp_dense_set(cesx_handle h, const cesx_gp_dense_desc* desc);
+/* CESX_GP_PROJ: the likelihood of CESX_GP_DENSE with Sigma_j projected to k x k, for any n_obs.  With Gamma = L L^T,
+   W = L^{-1} B = Q R (thin QR, R k x k upper triangular) and r0 = L^{-1} (g0 - y):
+       Sigma_j = L (I_n + Q S_j Q^T) L^T,  S_j = R diag(v_j) R^T,   a_j = a0 + R m_j,  a0 = Q^T r0,  c_perp = |(I - Q Q^T) r0|^2
+       d^T Sigma_j^{-1} d = c_perp + a_j^T (I_k + S_j)^{-1} a_j,      log det Sigma_j = 2 sum log diag(L) + log det (I_k + S_j)
+   I_k + S_j has eigenvalues >= 1 and every term of the quadratic form is a sum of squares: nothing cancels, however large
+   B diag(v) B^T is beside Gamma.  The caller reduces the problem once on the host (ces_amd.emulate.project_sigma) and hands
+   R, a0 and the two scalars over; y and Gamma of cesx_set_problem are NOT read in this mode (they are baked into the
+   descriptor), and n_obs carries no limit.  Per chain one sub-wave group of lanes factors I_k + S_j (Cholesky, resident
+   in LDS) and scores, all in fp64 in one fixed order -- two calls are bit-identical and a chain's phi does not depend on
+   J_local, on its column, on its place in the wave or on its neighbours.  A pivot that is not > 0 or not finite makes phi
+   NaN: the test rejects, a start state stays stuck.  Limits: 1 <= k <= CESX_GP_PROJ_KMAX. */
+#define CESX_GP_PROJ_KMAX 128
+typedef struct {
+    uint32_t struct_bytes;    /* sizeof(cesx_gp_proj_desc) */
+    int32_t k;                /* GPs = the order of R */
+    int32_t logdet;           /* != 0: add half_logdet_gamma + 1/2 log det (I_k + S_j) (noise_compounded) */
+    const double* R;          /* [k][k] row-major; only the upper triangle is read */
+    const double* a0;         /* [k] */
+    double c_perp;            /* >= 0 */
+    double half_logdet_gamma; /* sum log diag(L) = 1/2 log det Gamma */
+} cesx_gp_proj_desc;
+/* Copies the descriptor (host fp64); replaces an earlier one.  CESX_EINVAL (text in cesx_last_error) for k < 1,
+   k > CESX_GP_PROJ_KMAX, a null pointer, a non-finite entry or c_perp < 0 -- the installed descriptor stays; CESX_ESTATE
+   without a problem.  A later cesx_set_problem drops the descriptor.  cesx_gp_start / cesx_gp_accept in mode CESX_GP_PROJ
+   return CESX_ESTATE without one, and need var_dev and n_gp == k. */
+int cesx_gp_proj_set(cesx_handle h, const cesx_gp_proj_desc* desc);
 
 /* ---- Emulate: training the GPs on device (ces_amd/emulate.py train_gps(device=True)) --------------------
    The log marginal likelihood of n_gp exact GPs on SHARED training inputs X and its gradient, all GPs of a call in the same
