@@ -777,6 +777,14 @@ int launch_gp_score_proj(Engine& e, bool start, const void* X, const double* mea
 // non-finite entry.  darcy_prepare: once per installed map (the kernels' dynamic LDS limit for this K)
 int darcy_prepare(Engine& e, int K);
 int launch_darcy(Engine& e, const void* U, void* G, int* status, hipStream_t s);
+// kernels_darcy_stream.hip: the same map with the banded LU streamed through a live window in LDS and an HBM workspace
+// (DarcyState::ws, one slot per workgroup in flight), for Nmesh up to darcy_stream_kmax().  darcy_stream_prepare: once per
+// installed map (the dynamic LDS limit for this K; auto_grid = the workgroups the device holds at once)
+int darcy_stream_kmax();
+size_t darcy_stream_lds(int K);
+size_t darcy_stream_slot_bytes(int K);
+int darcy_stream_prepare(Engine& e, int K, int* auto_grid);
+int launch_darcy_stream(Engine& e, const void* U, void* G, int* status, hipStream_t s);
 
 // kernels_l96.hip: per column, RK45 of the installed two-scale Lorenz '96 model from W_in (n_state x J fp64) with the
 // parameters the descriptor's map takes from U; G = the last window's statistics (engine dtype), W_out = the state at t[-1]

@@ -91,13 +91,16 @@ struct GpFitState {
     }
 };
 
-// ---- Darcy forward map over the columns (cesx_darcy_*, kernels_darcy.hip); state of its own: the lineal map is untouched ----
+// ---- Darcy forward map over the columns (cesx_darcy_*, kernels_darcy.hip, kernels_darcy_stream.hip); state of its own: the lineal map is untouched ----
 struct DarcyState {
     int K = 0;                         // Nmesh of the installed map (0: none)
+    bool streamed = false;             // installed by cesx_darcy_set_streamed: cesx_darcy_apply launches kernels_darcy_stream.hip
+    int slots = 0;                     // streamed: workspace slots = the largest grid an apply launches (0: resident)
     DevBuf<double> mat;                // [4][K][K] coef (K folded in, entry 0 zero), D, S, R, row-major
     DevBuf<int> idx;                   // [p] scatter, then [n] obs_index
+    DevBuf<double> ws;                 // streamed: [slots][n][2 m + 1] the finished rows of U, one slot per workgroup in flight
     bool none() const { return K == 0; }
-    void drop() { K = 0; mat.reset(); idx.reset(); }
+    void drop() { K = 0; streamed = false; slots = 0; mat.reset(); idx.reset(); ws.reset(); }
 };
 
 // ---- Lorenz '96 forward map over the columns (cesx_lorenz_*, kernels_l96.hip); state of its own, as the Darcy map's ----

@@ -1486,42 +1486,74 @@ int cesx_gpfit_factors(cesx_handle h, int i, double* alpha, double* Li) {
     return CESX_OK;
 }
 
-// ---- Darcy forward map over the columns (ces_amd/darcy.py; kernels_darcy.hip) ----
+// ---- Darcy forward map over the columns (ces_amd/darcy.py; kernels_darcy.hip, kernels_darcy_stream.hip) ----
 
 // Failure rule: an argument error leaves the OLD map; behind the synchronise there is none until everything is uploaded.
-int cesx_darcy_set(cesx_handle h, const cesx_darcy_desc* d) {
-    if (!h) return CESX_EINVAL;
-    Engine& e = *reinterpret_cast<Engine*>(h);
-    if (!d || d->struct_bytes != sizeof(cesx_darcy_desc)) { e.err = "cesx_darcy_set: bad cesx_darcy_desc"; return CESX_EINVAL; }
-    if (!d->coef || !d->scatter || !d->D || !d->S || !d->R || !d->obs_index) { e.err = "cesx_darcy_set: null pointer"; return CESX_EINVAL; }
-    if (d->K < 4) { e.err = "cesx_darcy_set: K < 4 (a not-a-knot spline needs four points)"; return CESX_EINVAL; }
-    if (d->K > 16) { e.err = "cesx_darcy_set: K > 16 (the working band of one particle no longer fits in LDS)"; return CESX_EINVAL; }
+// One body for both kinds: `who` names the entry point in the messages; only the K limit and the workspace differ.
+static int darcy_install(Engine& e, const cesx_darcy_desc* d, const char* who, bool streamed, int max_workgroups) {
+    auto fail = [&](const char* what) { e.err = std::string(who) + ": " + what; return CESX_EINVAL; };
+    if (!d || d->struct_bytes != sizeof(cesx_darcy_desc)) return fail("bad cesx_darcy_desc");
+    if (!d->coef || !d->scatter || !d->D || !d->S || !d->R || !d->obs_index) return fail("null pointer");
+    if (d->K < 4) return fail("K < 4 (a not-a-knot spline needs four points)");
+    if (!streamed && d->K > 16) return fail("K > 16 (the working band of one particle no longer fits in LDS)");
+    if (streamed && d->K > darcy_stream_kmax())
+        return fail(("K > " + std::to_string(darcy_stream_kmax()) + " (the live window of one particle no longer fits in LDS)").c_str());
+    if (streamed && max_workgroups < 0) return fail("max_workgroups < 0");
     const int K = d->K, KK = K * K, p = e.p, n = e.n;
-    if (d->p != p || d->n_obs != n) { e.err = "cesx_darcy_set: p / n_obs differ from the handle's"; return CESX_EINVAL; }
-    if (p > KK) { e.err = "cesx_darcy_set: p exceeds K^2"; return CESX_EINVAL; }
+    if (d->p != p || d->n_obs != n) return fail("p / n_obs differ from the handle's");
+    if (p > KK) return fail("p exceeds K^2");
     std::vector<int> idx((size_t)p + n);
     std::vector<char> seen((size_t)KK, 0);
     for (int q = 0; q < p; ++q) {
         const int s = d->scatter[q];
-        if (s < 0 || s >= KK || seen[s]) { e.err = "cesx_darcy_set: scatter index out of range or repeated"; return CESX_EINVAL; }
+        if (s < 0 || s >= KK || seen[s]) return fail("scatter index out of range or repeated");
         seen[s] = 1; idx[q] = s;
     }
     for (int k = 0; k < n; ++k) {
         const int o = d->obs_index[k];
-        if (o < 0 || o >= KK) { e.err = "cesx_darcy_set: obs_index out of range"; return CESX_EINVAL; }
+        if (o < 0 || o >= KK) return fail("obs_index out of range");
         idx[(size_t)p + k] = o;
     }
     SET_DEVICE(e);
     CESX_HIP(hipDeviceSynchronize());          // (the old image may be read by launches still in flight)
     e.dc.drop();
-    TRY(darcy_prepare(e, K));
+    int slots = 0;
+    if (streamed) {
+        // slots = min(J, max_workgroups or the automatic grid, CESX_DARCY_WS_CAP / bytes per slot), at least one
+        int auto_grid = 0;
+        TRY(darcy_stream_prepare(e, K, &auto_grid));
+        const size_t per = darcy_stream_slot_bytes(K);
+        long long s = std::min<long long>(e.J, max_workgroups > 0 ? max_workgroups : auto_grid);
+        s = std::min<long long>(s, (long long)(CESX_DARCY_WS_CAP / per));
+        slots = (int)std::max<long long>(s, 1);
+        TRY_BUF(e.dc.ws.alloc((size_t)slots * per, false));
+    } else {
+        TRY(darcy_prepare(e, K));
+    }
     TRY_BUF(e.dc.mat.alloc((size_t)4 * KK * 8));
     TRY_BUF(e.dc.idx.alloc(idx.size() * 4));
     const double* mats[4] = {d->coef, d->D, d->S, d->R};
     for (int k = 0; k < 4; ++k) TRY(upload(e, e.dc.mat + (size_t)k * KK, mats[k], (size_t)KK * 8));
     TRY(upload(e, e.dc.idx, idx.data(), idx.size() * 4));
+    e.dc.streamed = streamed; e.dc.slots = slots;
     e.dc.K = K;
     return CESX_OK;
+}
+
+int cesx_darcy_set(cesx_handle h, const cesx_darcy_desc* d) {
+    if (!h) return CESX_EINVAL;
+    return darcy_install(*reinterpret_cast<Engine*>(h), d, "cesx_darcy_set", false, 0);
+}
+
+int cesx_darcy_set_streamed(cesx_handle h, const cesx_darcy_desc* d, int max_workgroups) {
+    if (!h) return CESX_EINVAL;
+    return darcy_install(*reinterpret_cast<Engine*>(h), d, "cesx_darcy_set_streamed", true, max_workgroups);
+}
+
+size_t cesx_darcy_workspace_bytes(cesx_handle h) {
+    if (!h) return 0;
+    const Engine& e = *reinterpret_cast<Engine*>(h);
+    return e.dc.none() || !e.dc.streamed ? 0 : e.dc.ws.bytes;
 }
 
 int cesx_darcy_apply(cesx_handle h, const void* U, void* G, int32_t* status, void* stream) {
@@ -1530,6 +1562,7 @@ int cesx_darcy_apply(cesx_handle h, const void* U, void* G, int32_t* status, voi
     if (!U || !G) { e.err = "cesx_darcy_apply: null pointer"; return CESX_EINVAL; }
     if (e.dc.none()) { e.err = "cesx_darcy_apply: cesx_darcy_set has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
+    if (e.dc.streamed) return launch_darcy_stream(e, U, G, status, (hipStream_t)stream);
     return launch_darcy(e, U, G, status, (hipStream_t)stream);
 }
 

@@ -22,13 +22,18 @@ Same classes and call conventions as the reference (``model``, ``model_trunc``,
 examples/scripts/darcy-flow.py:6-14 runs unchanged.
 
 ``__call__`` evaluates the map on the host, one particle per call, as the
-reference does.  ``forward_device`` (build-only hook, Nmesh 4..16) evaluates the
+reference does.  ``forward_device`` (build-only hook) evaluates the
 same map for every column of a device-resident ensemble in one launch
-(cesx_darcy_apply, ces_amd/csrc/kernels_darcy.hip): everything but the solve is a
+(cesx_darcy_apply): everything but the solve is a
 fixed linear operator or an elementwise ``exp``, so the host hands the engine the
 matrices once (``device_descriptor``) and the kernel runs KL synthesis, the two
 spline maps, the assembly and a banded LU with partial pivoting per particle, all
-in fp64.  With the hook ``sampling.run`` keeps a Darcy ensemble resident
+in fp64.  Two solvers, chosen with ``set_device_solver`` (build-only): ``'resident'``, the
+default (ces_amd/csrc/kernels_darcy.hip, Nmesh 4..16: one particle's whole working
+band in LDS), and ``'streamed'`` (ces_amd/csrc/kernels_darcy_stream.hip, Nmesh 4..64:
+only the live window of the factorisation in LDS, the finished rows of U streamed
+through an HBM workspace; ``device_max_workgroups`` bounds the grid and with it the
+workspace, 0 = automatic).  With the hook ``sampling.run`` keeps a Darcy ensemble resident
 (``noise='device'`` or ``xis=``) and ``MCMC.model_mh(chains=M)`` runs; the
 default host flow is unchanged.
 
@@ -153,6 +158,17 @@ class model(object):
 
     # ---- build-only hook: the whole ensemble on the device (cesx_darcy_*) ----
     DEVICE_NMESH = (4, 16)     # not-a-knot needs four points; beyond 16 one particle's working band no longer fits in LDS
+    DEVICE_NMESH_STREAMED = (4, 64)    # the streamed solver keeps only the live window in LDS (CESX_DARCY_STREAM_KMAX)
+    DEVICE_SOLVERS = ("resident", "streamed")
+    device_solver = "resident"
+    device_max_workgroups = 0  # streamed: the largest grid an apply may launch (one workspace slot each); 0 = automatic
+
+    def set_device_solver(self, kind):
+        """Which kernel ``forward_device`` installs: ``'resident'`` (the default, Nmesh 4..16) or ``'streamed'`` (Nmesh 4..64).
+        Part of the fingerprint: the next ``forward_device`` installs the map again."""
+        if kind not in self.DEVICE_SOLVERS:
+            raise ValueError("darcy set_device_solver: %r is neither 'resident' nor 'streamed'" % (kind,))
+        self.device_solver = kind
 
     def _device_scatter(self):
         """The Nmesh^2 slot of the KL array each parameter lands on (``eval_rf``'s reshape: the identity)."""
@@ -170,8 +186,13 @@ class model(object):
         K = int(self.Nmesh)
         if K != self.Nmesh or K < self.DEVICE_NMESH[0]:
             raise ValueError("darcy forward_device: Nmesh = %r < 4 (or not an integer)" % (self.Nmesh,) + host)
-        if K > self.DEVICE_NMESH[1]:
-            raise ValueError("darcy forward_device: Nmesh = %d > 16 is not supported on the device" % K + host)
+        streamed = self.device_solver == "streamed"
+        if streamed and K > self.DEVICE_NMESH_STREAMED[1]:
+            raise ValueError("darcy forward_device: Nmesh = %d > %d is not supported on the device (streamed solver)"
+                             % (K, self.DEVICE_NMESH_STREAMED[1]) + host)
+        if not streamed and K > self.DEVICE_NMESH[1]:
+            raise ValueError("darcy forward_device: Nmesh = %d > 16 is not supported on the device" % K + host
+                             + " (or set_device_solver('streamed'), Nmesh up to %d)" % self.DEVICE_NMESH_STREAMED[1])
         obs = np.asarray(self.obs_index).reshape(-1)
         if n_obs is not None and obs.size != int(n_obs):
             raise ValueError("darcy forward_device: len(obs_index) = %d differs from the engine's n_obs = %d" % (obs.size, n_obs)
@@ -186,16 +207,20 @@ class model(object):
         eye = np.eye(K)
         centres = np.arange(1, 2 * K, 2) / (2.0 * K)
         nodes = np.linspace(0.0, 1.0, K)
-        return dict(K=K, coef=coef, scatter=scatter.astype(np.int32), D=idctn(eye, axes=[0], norm="ortho"),
+        desc = dict(K=K, coef=coef, scatter=scatter.astype(np.int32), D=idctn(eye, axes=[0], norm="ortho"),
                     S=CubicSpline(centres, eye, axis=0, bc_type="not-a-knot", extrapolate=True)(nodes),
                     R=CubicSpline(nodes, eye, axis=0, bc_type="not-a-knot", extrapolate=True)(centres),
                     obs_index=obs.astype(np.int32))
+        if streamed:
+            desc.update(solver="streamed", max_workgroups=int(self.device_max_workgroups))
+        return desc
 
     def _fingerprint(self):
         rank = getattr(self, "rank", None)
         return (float(self.alpha), float(self.tau), float(self.Nmesh), int(self.p),
                 None if rank is None else np.asarray(rank).tobytes(),
-                None if getattr(self, "obs_index", None) is None else np.asarray(self.obs_index).tobytes())
+                None if getattr(self, "obs_index", None) is None else np.asarray(self.obs_index).tobytes(),
+                self.device_solver, int(self.device_max_workgroups))
 
     def invalidate_device(self):
         """Forget the map installed in an engine: the next ``forward_device`` builds and installs the descriptor again."""
@@ -203,8 +228,8 @@ class model(object):
         self._dev_token = 0
 
     def ensure_installed(self, engine):
-        """Make THIS map the Darcy map installed in ``engine``: installed once, again when alpha, tau, Nmesh, p, rank or
-        obs_index changed or another model installed its map on the same engine (``invalidate_device()`` forces it)."""
+        """Make THIS map the Darcy map installed in ``engine``: installed once, again when alpha, tau, Nmesh, p, rank,
+        obs_index, the device solver or its grid bound changed or another model installed its map on the same engine (``invalidate_device()`` forces it)."""
         fp = self._fingerprint()
         if (getattr(self, "_dev_fp", None) != fp
                 or getattr(engine, "_darcy_token", None) is not getattr(self, "_dev_token", 0)):

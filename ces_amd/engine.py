@@ -18,7 +18,7 @@ OK, EINVAL, ENOTPD, EHIP, ESTATE, EUNSUPPORTED, ENOCONV = 0, 1, 2, 3, 4, 5, 6
 F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
-ABI_VERSION = 5
+ABI_VERSION = 6
 MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
@@ -33,7 +33,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats", "cesx_mh_phi",
            "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_dense_set", "cesx_gp_proj_set",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
-           "cesx_darcy_set", "cesx_darcy_apply", "cesx_lorenz_set", "cesx_lorenz_apply",
+           "cesx_darcy_set", "cesx_darcy_apply", "cesx_darcy_set_streamed", "cesx_darcy_workspace_bytes", "cesx_lorenz_set", "cesx_lorenz_apply",
            "cesx_lorenz_three_set", "cesx_lorenz_three_apply")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
               2: "a state or an error norm was not finite",
@@ -269,6 +269,9 @@ def load_library(path=None):
     lib.cesx_gpfit_factors.argtypes = [vp, i32, vp, vp]
     lib.cesx_darcy_set.argtypes = [vp, C.POINTER(DarcyDesc)]
     lib.cesx_darcy_apply.argtypes = [vp, vp, vp, vp, vp]
+    lib.cesx_darcy_set_streamed.argtypes = [vp, C.POINTER(DarcyDesc), C.c_int]
+    lib.cesx_darcy_workspace_bytes.argtypes = [vp]
+    lib.cesx_darcy_workspace_bytes.restype = C.c_size_t
     lib.cesx_lorenz_set.argtypes = [vp, C.POINTER(L96Desc)]
     lib.cesx_lorenz_apply.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.cesx_lorenz_three_set.argtypes = [vp, C.POINTER(L63Desc)]
@@ -1066,8 +1069,9 @@ class Engine:
 
     # -- Darcy forward map over the columns (include/cesx.h, cesx_darcy_*; ces_amd/darcy.py builds the descriptor) --
     def darcy_set(self, desc):
-        """Install a Darcy map: ``desc`` as ``ces_amd.darcy.model.device_descriptor`` returns it (cesx_darcy_set; the engine
-        keeps its own copy).  Returns the token that identifies the installed map."""
+        """Install a Darcy map: ``desc`` as ``ces_amd.darcy.model.device_descriptor`` returns it (the engine keeps its own
+        copy): cesx_darcy_set, or cesx_darcy_set_streamed with ``desc['max_workgroups']`` when ``desc['solver']`` is
+        ``'streamed'``.  Returns the token that identifies the installed map."""
         K = int(desc["K"])
         mats = {k: np.ascontiguousarray(np.asarray(desc[k], dtype=np.float64)) for k in ("coef", "D", "S", "R")}
         for k, a in mats.items():
@@ -1078,9 +1082,19 @@ class Engine:
         d = DarcyDesc(C.sizeof(DarcyDesc), K, scatter.size, obs.size, mats["coef"].ctypes.data, scatter.ctypes.data,
                       mats["D"].ctypes.data, mats["S"].ctypes.data, mats["R"].ctypes.data, obs.ctypes.data)
         with torch.cuda.device(self.device):
-            self._check(self.lib.cesx_darcy_set(self._h, C.byref(d)))
+            solver = desc.get("solver", "resident")
+            if solver == "streamed":
+                self._check(self.lib.cesx_darcy_set_streamed(self._h, C.byref(d), int(desc.get("max_workgroups", 0))))
+            elif solver == "resident":
+                self._check(self.lib.cesx_darcy_set(self._h, C.byref(d)))
+            else:
+                raise ValueError("darcy_set: solver %r is neither 'resident' nor 'streamed'" % (solver,))
         self._darcy_token = object()
         return self._darcy_token
+
+    def darcy_workspace_bytes(self):
+        """Bytes of HBM workspace the installed Darcy map owns (cesx_darcy_workspace_bytes): 0 unless it is a streamed one."""
+        return int(self.lib.cesx_darcy_workspace_bytes(self._h))
 
     def darcy_apply(self, U, out=None):
         """G (n_obs, J) = the installed Darcy map of the columns of U (cesx_darcy_apply).  Raises ``numpy.linalg.LinAlgError``

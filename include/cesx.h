@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CESX_ABI_VERSION 5
+#define CESX_ABI_VERSION 6
 
 /* status codes */
 #define CESX_OK            0
@@ -384,7 +384,7 @@ int cesx_forward_apply(cesx_handle h, const void* U_dev, void* G_dev, void* stre
    These entry points keep state of their own: the linear map of cesx_forward_set_lineal is untouched. */
 typedef struct {
     uint32_t struct_bytes;    /* sizeof(cesx_darcy_desc) */
-    int32_t K;                /* Nmesh, 4 <= K <= 16 (a not-a-knot spline needs four points; one particle's band must fit in LDS) */
+    int32_t K;                /* Nmesh, 4 <= K <= 16 (a not-a-knot spline needs four points; one particle's band must fit in LDS); up to 64 for cesx_darcy_set_streamed */
     int32_t p, n_obs;         /* must equal the handle's p and n_obs; p <= K^2 */
     const double* coef;       /* [K][K] KL coefficients, ALREADY multiplied by K and with entry [0][0] zeroed */
     const int32_t* scatter;   /* [p] the K^2 slot each parameter lands on, distinct (identity: darcy.model; rank[:p]: model_trunc) */
@@ -396,7 +396,23 @@ typedef struct {
 /* Copies the map (host fp64) into engine-owned memory; replaces an earlier one.  CESX_EINVAL (text in cesx_last_error) for
    K < 4, K > 16, a size mismatch, an index out of range or a repeated scatter index; the installed map is kept then. */
 int cesx_darcy_set(cesx_handle h, const cesx_darcy_desc* desc);
-/* G_dev (n_obs x J_local) = the installed map of the columns of U_dev (p x J_local), both in the engine dtype.  status_dev
+/* The same map for 4 <= K <= CESX_DARCY_STREAM_KMAX, installed for the STREAMED solver (kernels_darcy_stream.hip): the banded LU
+   keeps only its live window -- (m + 2) x (2 m + 2) entries, m = K - 2 -- in LDS, writes every finished row of U (2 m + 1
+   doubles) to an HBM workspace and reads the rows back for the back substitution.  Same descriptor struct, validated exactly
+   as cesx_darcy_set validates it but for the upper limit of K; same arithmetic contract and status words.  One persistent
+   workgroup per particle in flight; the workspace holds one slot of m^2 (2 m + 1) doubles per workgroup (3 844 000 B at K = 64,
+   439 200 B at K = 32):
+       slots = max(1, min(J_local, max_workgroups or the automatic grid, CESX_DARCY_WS_CAP / bytes per slot))
+   max_workgroups: 0 (automatic: what the device holds at once at this K's LDS size) or the largest grid an apply may launch;
+   negative is CESX_EINVAL.  A particle's result depends neither on the grid nor on the slot it ran in.  The failure rule is
+   cesx_darcy_set's; each call replaces the map of the other kind too (one Darcy map per handle). */
+#define CESX_DARCY_STREAM_KMAX 64
+#define CESX_DARCY_WS_CAP ((size_t)1 << 30)   /* bytes: the automatic grid of 256 workgroups at K = 64 (984 064 000 B) stays below it */
+int cesx_darcy_set_streamed(cesx_handle h, const cesx_darcy_desc* desc, int max_workgroups);
+/* Bytes of HBM workspace the installed map owns: slots m^2 (2 m + 1) 8 for a streamed map, 0 for a resident one or none. */
+size_t cesx_darcy_workspace_bytes(cesx_handle h);
+/* Dispatches on the kind of the installed map (resident or streamed).
+   G_dev (n_obs x J_local) = the installed map of the columns of U_dev (p x J_local), both in the engine dtype.  status_dev
    (J_local int32 on the device, or NULL): 0; or c > 0 -- the pivot of column c (1-based) of that particle was exactly zero, its
    system is singular --; or -c -- column c held a NaN or an infinity when its pivot was sought (exp(theta) overflowed: nothing
    is singular, the input left fp64's range).  The outputs of such a particle are NaN, the other particles are unaffected. */

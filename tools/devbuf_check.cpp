@@ -85,6 +85,8 @@ static int fill(GpFitState& s, size_t sz) {
 static int fill(DarcyState& s, size_t sz) {
     s.drop();
     AL(s.mat, 64); AL(s.idx, 9);
+    if (const int rc = s.ws.alloc(90 * sz, false)) return rc;      // (cesx_darcy_set_streamed: the workspace, not zeroed)
+    s.streamed = true; s.slots = 3;
     s.K = 4;
     return 0;
 }
@@ -103,7 +105,7 @@ static void after_drop(const GpDenseState& s, bool full) { REQUIRE(!full || (s.B
 static void after_drop(const GpFitState& s, bool) {
     REQUIRE(!s.X && !s.Y && !s.Xs && !s.r && !s.t && !s.alpha && !s.A && !s.W && !s.Ki && !s.Ld && !s.part && !s.theta && !s.out && !s.idx && !s.status);
 }
-static void after_drop(const DarcyState& s, bool) { REQUIRE(!s.mat && !s.idx); }
+static void after_drop(const DarcyState& s, bool) { REQUIRE(!s.mat && !s.idx && !s.ws && !s.streamed && s.slots == 0); }
 static void after_drop(const L96State& s, bool) { REQUIRE(!s.t); }
 
 template <typename S> static void stage(const char* who) {
