@@ -22,7 +22,7 @@ Build-only extras (not in the reference):
   ``run_eks``            alias of ``sampling.run`` (BASELINE.json's name for it)
 
 ``sampling.run`` keeps the ensemble ON THE DEVICE for the whole loop when it can: the model offers the
-build-only hook ``forward_device(engine, U_dev)`` (``ces_amd.utils.lineal`` does) and the noise does not
+build-only hook ``forward_device(engine, U_dev)`` (``ces_amd.utils`` lineal, lineal_log, elliptic and banana do) and the noise does not
 have to come from numpy's global stream (``self.noise == 'device'`` or ``xis=`` given).  Per iteration
 nothing crosses PCIe but the step's scalars (and the trace, if kept).  Otherwise the reference's data flow
 is kept -- host forward map (``G_ens``), float64 numpy arrays into and out of every update.  For LARGE

@@ -474,6 +474,7 @@ struct Engine {
     // ---- the stages behind Calibrate: each struct owns its device memory and has one drop() (cesx_stages.h) ----
     std::vector<double> h_LSi, h_mu;   // L_Sigma^{-1} and mu of the problem (cesx_set_problem): the dense prior's image
     std::vector<double> h_y_raw, h_Gamma_raw;       // y and Gamma as cesx_set_problem got them (UNWHITENED; Gamma symmetric from its lower triangle)
+    std::vector<double> h_yw, h_gw;                 // host copies of d_y (whitened for a dense Gamma) and d_gw: cesx_mh_run_map passes the problem by value
     MhState mh;                        // Metropolis-Hastings over the columns (cesx_mh_*, kernels_mh.hip)
     GpState gp;                        // GP emulator over the columns (cesx_gp_*, kernels_gp.hip)
     GpDenseState gpd;                  // the dense per-chain Sigma of CESX_GP_DENSE (cesx_gp_dense_set, kernels_gpdense.hip)
@@ -482,6 +483,7 @@ struct Engine {
     DarcyState dc;                     // Darcy forward map (cesx_darcy_*, kernels_darcy.hip)
     L96State l9;                       // Lorenz '96 forward map (cesx_lorenz_*, kernels_l96.hip)
     L63State l6;                       // Lorenz '63 forward map (cesx_lorenz_three_*, kernels_l63.hip)
+    MapState mp;                       // closed-form maps and their fused chain kernel (cesx_map_*, cesx_mh_run_map, kernels_maps.hip)
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -794,6 +796,11 @@ int launch_l96(Engine& e, const void* U, const double* W_in, void* G, double* W_
 // kernels_l63.hip: per column, RK45 of the installed Lorenz '63 model from W_in (3 x J fp64), one particle per lane; G = the
 // nine means of the last window (engine dtype), W_out = the state at t[-1] (may be W_in), info as launch_l96 writes it
 int launch_l63(Engine& e, const void* U, const double* W_in, void* G, double* W_out, int* info, hipStream_t s);
+// kernels_maps.hip: G = the installed closed-form map of every column of U, one column per lane (fp64, rounded on the store);
+// and n_steps Metropolis steps of every chain in one launch for the installed map of a fused kind (include/cesx.h)
+int launch_map_apply(Engine& e, const void* U, void* G, hipStream_t s);
+int launch_mh_run_map(Engine& e, uint64_t step_index, int n_steps, int stride, void* U, void* trace, const void* xi,
+                      const double* logu, hipStream_t s);
 
 // kernels_gpfit.hip: lml, gradient and status of the GPs gf.idx[0 .. n_active) at gf.theta into gf.out
 int launch_gpfit_eval(Engine& e, int n_active, hipStream_t s);

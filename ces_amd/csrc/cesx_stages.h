@@ -1,4 +1,4 @@
-// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gpp, gf, dc, l9, l6).  Each owns its
+// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gpp, gf, dc, l9, l6, mp).  Each owns its
 // device memory (DevBuf: freed with the struct), says what "nothing installed" is, and has one drop() that establishes it.
 // drop() releases the buffers whose size comes from the installed descriptor and keeps the ones sized by the engine's
 // shape alone (allocated on first use, reused by every later install).  No hip/ header: tools/devbuf_check.cpp runs these
@@ -25,6 +25,7 @@ struct MhState {
     DevBuf<double> phi;                // [J] phi of the chains' current states
     DevBuf<unsigned long long> cnt;    // [J] accepted proposals per chain
     DevBuf<double> LSi;                // [p][p] L_Sigma^{-1} of a dense Sigma, fp64: the dense prior's factor as gp_score_kernel reads it
+    std::vector<double> h_bS;          // [p][p] b S on the host: cesx_mh_run_map passes it by value
     bool none() const { return kind < 0; }
     void drop() { kind = -1; started = false; }      // every buffer is sized by the engine: kept
 };
@@ -117,6 +118,14 @@ struct L63State {
     DevBuf<double> t;                  // [n_t] the sample times
     bool none() const { return desc.n_t == 0; }
     void drop() { desc = cesx_l63_desc{}; t.reset(); }
+};
+
+// ---- closed-form maps over the columns (cesx_map_*, cesx_mh_run_map, kernels_maps.hip); state of its own, as the Lorenz maps' ----
+struct MapState {
+    cesx_map_desc desc{};              // the installed descriptor (kind 0: none); passed to the kernels by value: no device memory
+    bool none() const { return desc.kind == 0; }
+    bool fused() const { return desc.kind == CESX_MAP_ELLIPTIC || desc.kind == CESX_MAP_BANANA; }   // cesx_mh_run_map has it
+    void drop() { desc = cesx_map_desc{}; }
 };
 
 }  // namespace cesx

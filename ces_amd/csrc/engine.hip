@@ -435,6 +435,7 @@ int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const 
     TRY(upload(e, e.d_mu, mu, p * 8)); TRY(upload(e, e.d_ustar, ustar, p * 8));
     TRY(upload(e, e.d_Sigma, Sigma, (size_t)p * p * 8)); TRY(upload(e, e.d_Sinv, inv.data(), (size_t)p * p * 8));
     TRY(upload(e, e.d_sw, sw.data(), p * 8));
+    e.h_yw = yi; e.h_gw = gw;
     {
         // K3 through the Cholesky factor where the problem and the shape allow (cesx_internal.h, Engine::chain).  The two layouts
         // of d_Wq share no writer's footprint: a change of layout starts from a zeroed image, with nothing of the engine in flight
@@ -881,6 +882,7 @@ int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) 
     std::vector<double> bS(S, S + (size_t)p * p);
     for (double& v : bS) v *= b;
     TRY(mh_upload_tri(e, bS.data(), e.mh.W, e.mh.Wf));
+    e.mh.h_bS = bS;
     e.mh.dense_prior = kind == CESX_MH_RW && !e.diag_sigma;
     if (!e.diag_sigma) {                       // gp_score_kernel's fp64 L_Sigma^{-1} (RW and pCN: ces/sample.py:57 / :96)
         TRY_BUF(e.mh.LSi.ensure((size_t)p * p * 8));
@@ -1667,6 +1669,49 @@ int cesx_lorenz_three_apply(cesx_handle h, const void* U, const double* W_in, vo
     if (e.l6.none()) { e.err = "cesx_lorenz_three_apply: cesx_lorenz_three_set has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     return launch_l63(e, U, W_in, G, W_out, info, (hipStream_t)stream);
+}
+
+// ---- Closed-form maps over the columns and their fused chain kernel (ces_amd/utils.py; kernels_maps.hip) ----
+
+// Failure rule: ANY failure leaves the OLD map installed.  The descriptor travels by value: nothing in flight reads it.
+int cesx_map_set(cesx_handle h, const cesx_map_desc* d) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!d || d->struct_bytes != (int)sizeof(cesx_map_desc)) { e.err = "cesx_map_set: bad cesx_map_desc"; return CESX_EINVAL; }
+    if (d->kind != CESX_MAP_ELLIPTIC && d->kind != CESX_MAP_BANANA && d->kind != CESX_MAP_EXP) { e.err = "cesx_map_set: unknown map kind"; return CESX_EINVAL; }
+    if (d->kind != CESX_MAP_EXP) {
+        if (e.p != 2 || e.n != 2) { e.err = "cesx_map_set: the elliptic and the banana map need p = n_obs = 2"; return CESX_EINVAL; }
+        if (!std::isfinite(d->prm[0]) || !std::isfinite(d->prm[1])) { e.err = "cesx_map_set: a parameter is not finite"; return CESX_EINVAL; }
+        if (d->kind == CESX_MAP_BANANA && d->prm[0] == 0.0) { e.err = "cesx_map_set: banana needs a != 0"; return CESX_EINVAL; }
+    }
+    e.mp.desc = *d;
+    return CESX_OK;
+}
+
+int cesx_map_apply(cesx_handle h, const void* U, void* G, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U || !G) { e.err = "cesx_map_apply: null pointer"; return CESX_EINVAL; }
+    if (e.mp.none()) { e.err = "cesx_map_apply: cesx_map_set has not been called"; return CESX_ESTATE; }
+    if (G == U && e.mp.desc.kind != CESX_MAP_EXP) { e.err = "cesx_map_apply: G must not alias U"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    return launch_map_apply(e, U, G, (hipStream_t)stream);
+}
+
+int cesx_mh_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride, void* U, void* trace, const void* xi,
+                    const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U) { e.err = "cesx_mh_run_map: null pointer"; return CESX_EINVAL; }
+    if (n_steps < 1 || stride < 1) { e.err = "cesx_mh_run_map: n_steps and stride must be >= 1"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull || step_index + (uint64_t)n_steps > 0x80000000ull) { e.err = "cesx_mh_run_map: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    if (!e.problem_set || e.mh.none() || !e.mh.started) { e.err = "cesx_mh_run_map: cesx_mh_start has not been called (after cesx_set_problem and cesx_mh_set_proposal)"; return CESX_ESTATE; }
+    if (!e.mp.fused()) { e.err = "cesx_mh_run_map: no map of a fused kind is installed (cesx_map_set: CESX_MAP_ELLIPTIC or CESX_MAP_BANANA)"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_mh_run_map(e, step_index, n_steps, stride, U, trace, xi, logu, (hipStream_t)stream));
+    e.mh.steps += (unsigned long long)n_steps;
+    return CESX_OK;
 }
 
 }  // extern "C"

@@ -34,7 +34,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_dense_set", "cesx_gp_proj_set",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_darcy_set_streamed", "cesx_darcy_workspace_bytes", "cesx_lorenz_set", "cesx_lorenz_apply",
-           "cesx_lorenz_three_set", "cesx_lorenz_three_apply")
+           "cesx_lorenz_three_set", "cesx_lorenz_three_apply", "cesx_map_set", "cesx_map_apply", "cesx_mh_run_map")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
               2: "a state or an error norm was not finite",
               3: "max_attempts steps were attempted"}
@@ -43,6 +43,8 @@ GPFIT_MEANS = {"zero": 0, "constant": 1, "linear": 2}   # CESX_GPFIT_MEAN_*
 GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2, "dense": 3, "proj": 4}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR / _DENSE / _PROJ: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
 GP_DENSE_NMAX = 128                                   # CESX_GP_DENSE_NMAX
 GP_PROJ_KMAX = 128                                    # CESX_GP_PROJ_KMAX
+MAP_KINDS = {"elliptic": 1, "banana": 2, "exp": 3}    # CESX_MAP_ELLIPTIC / _BANANA / _EXP (ces_amd.utils elliptic, banana, lineal_log)
+MAP_FUSED = ("elliptic", "banana")                    # the kinds cesx_mh_run_map has a kernel for
 
 
 class Config(C.Structure):
@@ -140,6 +142,10 @@ def l63_desc_struct(desc):
     d.window_samples = int(desc["window_samples"])
     d.max_attempts = int(desc.get("max_attempts", 1000000))
     return d, t
+
+
+class MapDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int), ("kind", C.c_int), ("prm", C.c_double * 8)]
 
 
 class CesxError(RuntimeError):
@@ -276,6 +282,9 @@ def load_library(path=None):
     lib.cesx_lorenz_apply.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.cesx_lorenz_three_set.argtypes = [vp, C.POINTER(L63Desc)]
     lib.cesx_lorenz_three_apply.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.cesx_map_set.argtypes = [vp, C.POINTER(MapDesc)]
+    lib.cesx_map_apply.argtypes = [vp, vp, vp, vp]
+    lib.cesx_mh_run_map.argtypes = [vp, u64, i32, i32, vp, vp, vp, vp, vp]
     if lib.cesx_abi_version() != ABI_VERSION:
         raise ImportError("libcesx.so ABI %d != binding ABI %d" % (lib.cesx_abi_version(), ABI_VERSION))
     if path == LIB_PATH:
@@ -1180,6 +1189,60 @@ class Engine:
                                                          info.data_ptr(), self._stream()))
             self._keep_l63 = (U, W, out, W_out, info)
         return out, W_out, info
+
+    # -- closed-form maps over the columns and their fused chain kernel (include/cesx.h, cesx_map_*, cesx_mh_run_map) --
+    def map_set(self, kind, prm=()):
+        """Install a closed-form map: ``kind`` a key of ``MAP_KINDS`` ('elliptic': prm (x1, x2); 'banana': prm (a, b);
+        'exp': none -- the prologue of ``lineal_log``, for which the (p, J) scratch buffer ``map_scratch`` is allocated
+        here, once) (cesx_map_set).  Returns the token that identifies the installed map."""
+        if kind not in MAP_KINDS:
+            raise ValueError("unknown map kind %r" % (kind,))
+        prm = [float(v) for v in prm]
+        if len(prm) > 8:
+            raise ValueError("map_set: at most 8 parameters")
+        d = MapDesc()
+        d.struct_bytes, d.kind = C.sizeof(MapDesc), MAP_KINDS[kind]
+        for k, v in enumerate(prm):
+            d.prm[k] = v
+        self._check(self.lib.cesx_map_set(self._h, C.byref(d)))
+        if kind == "exp" and self.__dict__.get("map_scratch") is None:
+            self.map_scratch = self.empty(self.p)
+        self.map_kind = kind
+        self._map_token = object()
+        return self._map_token
+
+    def map_apply(self, U, out=None):
+        """G = the installed map of the columns of ``U`` (cesx_map_apply): (n_obs, J), for 'exp' (p, J), engine dtype."""
+        if self.__dict__.get("_map_token") is None:
+            raise CesxError(ESTATE, "map_apply: map_set has not been called")
+        rows = self.p if self.map_kind == "exp" else self.n_obs
+        out = self.empty(rows) if out is None else out
+        for name, t, r in (("U", U, self.p), ("out", out, rows)):
+            if t.dtype != self.torch_dtype or tuple(t.shape) != (r, self.J) or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("map_apply: %s must be a contiguous %s tensor of shape %s" % (name, self.torch_dtype, (r, self.J)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_map_apply(self._h, U.data_ptr(), out.data_ptr(), self._stream()))
+        self._keep_map = (U, out)
+        return out
+
+    def mh_run_map(self, step_index, n_steps, U, stride=1, trace=None, xi=None, logu=None):
+        """``n_steps`` Metropolis steps of every chain in one launch with the installed map of a fused kind
+        (cesx_mh_run_map): ``U`` (p, J) is advanced in place, the engine's phi, counters and step count follow.
+        ``trace`` (n_steps // stride, p, J) engine dtype, or None; ``xi`` (n_steps, p, J) engine dtype and ``logu``
+        (n_steps, J) float64, or None for the device draws of steps ``step_index`` .. ``step_index + n_steps - 1``."""
+        n_steps, stride = int(n_steps), int(stride)
+        for name, t, shape, dt in (("U", U, (self.p, self.J), self.torch_dtype),
+                                   ("trace", trace, (max(n_steps, 0) // max(stride, 1), self.p, self.J), self.torch_dtype),
+                                   ("xi", xi, (n_steps, self.p, self.J), self.torch_dtype),
+                                   ("logu", logu, (n_steps, self.J), torch.float64)):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError("mh_run_map: %s must be a contiguous %s tensor of shape %s" % (name, dt, shape))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_run_map(self._h, int(step_index), n_steps, stride, U.data_ptr(),
+                                                 None if trace is None or trace.numel() == 0 else trace.data_ptr(),
+                                                 None if xi is None else xi.data_ptr(),
+                                                 None if logu is None else logu.data_ptr(), self._stream()))
+        self._keep_mh_run = (U, trace, xi, logu)
 
     def profile_enable(self, on=True):
         """on: False / True, 2 = bind only the events cesx_profile_gap needs, 3 / 4 = the update / the moments

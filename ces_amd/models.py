@@ -12,8 +12,9 @@ attributes, call conventions and default arguments so that its notebooks
 (examples/notebooks/{linear,lorenz63}.ipynb) run against ``ces_amd.calibrate``
 unchanged; the right-hand sides are written in vectorised numpy rather than
 per-variable Python loops.  ``lineal_log``, ``elliptic`` and ``banana`` of
-ces/utils.py are outside the hot-path scope and are
-not shipped.
+ces/utils.py are closed-form maps, not models with carried state: they live in
+ces_amd/utils.py beside ``lineal`` (with their device hook and, for the last two,
+a fused chain kernel), not here.
 
 Parity: every class is checked against outputs of the reference's own
 ``ces/utils.py`` (it imports unmodified in the build container) stored in

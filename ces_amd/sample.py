@@ -28,6 +28,13 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          ``Gamma``; the same likelihood with Sigma projected to k x k (``emulate.project_sigma`` once on the
                          host, then ``gp_score_proj_kernel``: a k x k Cholesky per chain, several chains per wave), for any
                          n_obs and k <= 128.
+  kwarg ``fused``        model_mh with ``chains=``: ``None`` (default) takes the fused chain kernel where the model's map has one
+                         (``ces_amd.utils.elliptic`` and ``banana``: ``mh_run_map_kernel``, one chain per lane, up to
+                         ``FUSED_STEPS_MAX`` Metropolis steps per launch -- proposal, map, phi and test in registers, fp64 for
+                         either engine dtype; an fp32 engine's state is rounded at launch boundaries only) and the step path
+                         (three launches per step) otherwise; ``False`` forces the step path; ``True`` on a model without a
+                         fused kernel raises ``ValueError``.  Both paths draw the same noise and leave the same chains up to
+                         the rounding of a different product order.
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -49,6 +56,12 @@ except Exception:                      # pragma: no cover - tqdm is optional plu
 
 class MCMC(object):
     """Metropolis-Hastings samplers of ces/sample.py (:12-202)."""
+
+    # build-only, model_mh(chains=, fused=): what fused=None resolves to for a model with a fused chain kernel (the measurement
+    # behind it: NOTEBOOK.md, tools/map_mh_bench.py), the longest launch, and the bytes one launch's noise and trace may take
+    FUSED_DEFAULT = True
+    FUSED_STEPS_MAX = 4096
+    FUSED_BUFFER_BYTES = 64 << 20
 
     def __init__(self):
         self.mute_bar = False
@@ -162,6 +175,8 @@ class MCMC(object):
         """
         if kwargs.get("chains", None) is not None:
             return self._model_mh_device(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, kwargs)
+        if kwargs.get("fused", None) is not None:
+            raise ValueError("fused=%r chooses between the device paths of chains=M; the host path has one" % (kwargs.get("fused"),))
         # RW needs the proposal distribution (:122-126)
         if enka_scaling:
             scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(enka.p, enka.p))
@@ -236,7 +251,7 @@ class MCMC(object):
             self._mh_key = key
         return self._mh_eng
 
-    def _mh_device(self, enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi):
+    def _mh_device(self, enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi, fused=False):
         """M = kwargs['chains'] chains on the engine: what ``model_mh(chains=)`` and ``gp_mh(chains=)`` have in common.
 
         Gamma                    the data covariance handed to ``set_problem``
@@ -248,6 +263,8 @@ class MCMC(object):
                                  keeps that phi for the resumed states (ces/sample.py:131-163); its gp_mh scores the resumed
                                  states (:31-39).  True: the first, for ``noise='numpy'`` (``noise='device'`` re-scores the
                                  resumed states either way: the exact resume of model_mh's docstring)
+        fused                    the steps run through ``eng.mh_run_map`` (the fused chain kernel of the map ``bind``
+                                 installed, K Metropolis steps per launch) instead of propose / ``score_accept``
         """
         import torch
         M = kwargs["chains"]
@@ -297,18 +314,44 @@ class MCMC(object):
                 score_start(U)
             base, kept = int(getattr(self, "_mh_next_step", 0)), []
 
-        for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
-            step = base + k
-            xi_t = logu_t = None
-            if self.noise == "numpy":                     # the reference's draws in the reference's order
-                xi = np.random.normal(0, 1, [p, M])       # :199 / :202
-                logu = np.log(np.random.uniform(size=M))  # :188 / :98
-                xi_t = eng.to_device(xi, p, "mh_xi")
-                logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
-            eng.mh_propose(step, U, xi=xi_t, out=P)
-            score_accept(step, U, P, logu_t)
-            if (k + 1) % stride == 0 or k + 1 == n_mcmc:
+        if fused:
+            # launches of at most K_max steps (cesx_mh_run_map): K_max a multiple of the stride -- so that a launch's own count
+            # of kept states continues the run's -- and small enough that one launch's noise and trace stay under the budget.
+            # The trace buffer is allocated once per run; each launch's trace crosses to the host once.
+            esz = eng.np_dtype.itemsize
+            per_step = -(-M * p * esz // stride) + (M * (p * esz + 8) if self.noise == "numpy" else 0)     # trace; xi and log u
+            cap = max(1, min(self.FUSED_STEPS_MAX, self.FUSED_BUFFER_BYTES // per_step))
+            K_max = max(stride, cap // stride * stride)
+            trace = torch.empty((min(K_max, n_mcmc) // stride, p, M), dtype=eng.torch_dtype, device=eng.device)
+            for k0 in tqdm(range(0, n_mcmc, K_max), desc="MCMC samples: ", disable=self.mute_bar):
+                K = min(K_max, n_mcmc - k0)
+                xi_t = logu_t = None
+                if self.noise == "numpy":                 # the step loop's draws in the step loop's order, stacked
+                    xi, logu = np.empty((K, p, M)), np.empty((K, M))
+                    for k in range(K):
+                        xi[k] = np.random.normal(0, 1, [p, M])
+                        logu[k] = np.log(np.random.uniform(size=M))
+                    xi_t = torch.as_tensor(xi, device=eng.device).to(eng.torch_dtype).contiguous()
+                    logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
+                tr = trace[:K // stride]
+                eng.mh_run_map(base + k0, K, U, stride=stride, trace=tr, xi=xi_t, logu=logu_t)
+                if K // stride:
+                    kept.extend(tr.cpu().numpy().astype(np.float64))
+            if n_mcmc % stride and n_mcmc > 0:            # the run's last state, where the stride does not land on it
                 kept.append(eng.to_host(U))
+        else:
+            for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
+                step = base + k
+                xi_t = logu_t = None
+                if self.noise == "numpy":                     # the reference's draws in the reference's order
+                    xi = np.random.normal(0, 1, [p, M])       # :199 / :202
+                    logu = np.log(np.random.uniform(size=M))  # :188 / :98
+                    xi_t = eng.to_device(xi, p, "mh_xi")
+                    logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
+                eng.mh_propose(step, U, xi=xi_t, out=P)
+                score_accept(step, U, P, logu_t)
+                if (k + 1) % stride == 0 or k + 1 == n_mcmc:
+                    kept.append(eng.to_host(U))
         steps, rate, per = eng.mh_stats(per_chain=True)
 
         new = np.stack(kept, axis=1) if kept else np.zeros((p, 0, M))      # (p, n_new, M)
@@ -327,6 +370,16 @@ class MCMC(object):
             raise ValueError("chains=: the device path evaluates the forward map on the GPU through model.forward_device, "
                              "which %r does not offer (a 'pde' model offers it as forward_pde_device after "
                              "set_solver(device=True)); run model_mh without chains=" % (model,))
+        # fused: None -- the fused chain kernel where the model's map kind has one (FUSED_DEFAULT) --, False, True
+        fused = kwargs.get("fused", None)
+        if fused not in (None, False, True):
+            raise ValueError("fused must be None, False or True, got %r" % (fused,))
+        has_fused = (not pde and bool(getattr(model, "fused_kind", False)) and not getattr(model, "flag_noise", False)
+                     and hasattr(model, "ensure_installed"))
+        if fused and not has_fused:
+            raise ValueError("fused=True: %r has no fused chain kernel (ces_amd.utils.elliptic and banana have, noise-free); "
+                             "pass fused=None or False for the step path" % (model,))
+        fused = (has_fused and self.FUSED_DEFAULT) if fused is None else bool(fused)
         p, n = enka.p, enka.n_obs
 
         def scales_of(update):                            # exactly as the reference forms them (:122-129)
@@ -366,6 +419,8 @@ class MCMC(object):
         def bind(eng, M):
             takes_out = hook_takes_out(model.forward_device)
             G, GP = eng.empty(n), eng.empty(n)
+            if fused:                                     # (a resume that scores no start state: the map is installed all the same)
+                model.ensure_installed(eng)
 
             def fwd(u, out):
                 if takes_out:
@@ -382,7 +437,8 @@ class MCMC(object):
                 eng.mh_accept(step, U, P, GP, logu=logu)
             return score_start, score_accept
 
-        self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_pde if pde else bind, resume_keeps_start_phi=True)
+        self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_pde if pde else bind, resume_keeps_start_phi=True,
+                        fused=fused)
 
     def _gp_mh_device(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
         import torch

@@ -1,8 +1,12 @@
-"""Forward maps of the hot-path configs (ces/utils.py:5-31).
+"""Forward maps evaluated in closed form (ces/utils.py:5-122).
 
-``lineal`` is the forward map of the path BASELINE.json names (configs 1-3) and the
-one with a device hook; the other forward models of ces/utils.py (host code, SURVEY.md
-8f rank 4) live in ces_amd/models.py and are re-exported here, so that
+``lineal`` is the forward map of the path BASELINE.json names (configs 1-3); ``lineal_log``, ``elliptic`` and ``banana``
+(ces/utils.py:33-122) are the maps of the reference's linear.ipynb and elliptic.ipynb.  All four offer the build-only
+device hook ``forward_device(engine, U_dev, out=None)``: ``lineal`` through the map installed in the engine
+(cesx_forward_*), the other three through the engine's map stage (cesx_map_*, ces_amd/csrc/kernels_maps.hip; ``lineal_log``
+as exp(U) into an engine-owned buffer, then its installed lineal map).  ``elliptic`` and ``banana`` also have a fused chain
+kernel (cesx_mh_run_map: K Metropolis steps per launch), which ``MCMC.model_mh(chains=M)`` takes.  The other forward models
+of ces/utils.py live in ces_amd/models.py and are re-exported here, so that
 ``import ces_amd.utils as utils`` offers what ``import ces.utils as utils`` does.
 """
 import numpy as np
@@ -80,6 +84,155 @@ class lineal(object):
                 b = np.broadcast_to(np.asarray(self.b, dtype=np.float64), (self.n_obs,))
             self._dev_token = engine.forward_set_lineal(np.asarray(self.A), b)      # (another model may have installed its map)
             self._dev_A, self._dev_b, self._dev_fp = self.A, self.b, fp
+
+
+class _map_hook(object):
+    """The device hook of the closed-form maps (build-only): one descriptor (``_map_desc``) installed in the engine's map
+    stage (cesx_map_set), re-installed when a parameter changed or another model installed its own on the same engine."""
+
+    map_kind = None            # 'elliptic' | 'banana' | 'exp' (ces_amd.engine.MAP_KINDS)
+    fused_kind = False         # cesx_mh_run_map has an instantiation for this kind
+
+    def _map_desc(self):
+        raise NotImplementedError
+
+    def _fingerprint(self):
+        return (self.map_kind,) + tuple(float(v) for v in self._map_desc())
+
+    def invalidate_device(self):
+        """Forget the map installed in an engine (build-only): the next ``forward_device`` installs it again."""
+        self._map_fp = None
+        self._map_token = 0
+
+    def ensure_installed(self, engine):
+        """Make THIS model the one installed in the map stage of ``engine`` (build-only; ``invalidate_device()`` forces it)."""
+        fp = self._fingerprint()
+        if (getattr(self, "_map_fp", None) != fp
+                or getattr(engine, "_map_token", None) is not getattr(self, "_map_token", 0)):
+            self._map_token = engine.map_set(self.map_kind, self._map_desc())
+            self._map_fp = fp
+
+    def forward_device(self, engine, U_dev, out=None):
+        if self.flag_noise:
+            raise ValueError("the device hook evaluates the noise-free map only")
+        self.ensure_installed(engine)
+        return engine.map_apply(U_dev, out=out)
+
+
+class lineal_log(lineal):
+    """``A exp(phi) + b`` (ces/utils.py:33-51): ``lineal`` in log-parameters, with the log-Jacobian helpers."""
+
+    engine_lineal = False      # G's moments do NOT follow from U's through A (ShardedUpdate.lineal_fast_ok): A acts on exp(U)
+    map_kind = "exp"
+    fused_kind = False
+
+    def __init__(self, A, flag_noise=False):
+        super().__init__(A, flag_noise=flag_noise)
+        self.model_name = "lineal_log"
+        self.jacobian_adjusted = True
+
+    def __call__(self, phi):
+        return super().__call__(np.exp(phi))
+
+    def grad_logjacobian(self, params):
+        return -np.exp(-params)
+
+    def logjacobian(self, params):
+        if self.jacobian_adjusted:
+            return -params.sum(axis=0)
+        else:
+            return 0.0
+
+    def invalidate_device(self):
+        super().invalidate_device()
+        self._map_token = 0
+
+    def ensure_installed(self, engine):
+        """Both halves (build-only): the exp prologue in the engine's map stage -- ``map_set`` allocates the engine's
+        (p, J) scratch buffer, never an apply -- and A, b as the installed lineal map (``_fingerprint`` is lineal's)."""
+        if getattr(engine, "_map_token", None) is not getattr(self, "_map_token", 0):
+            self._map_token = engine.map_set(self.map_kind, ())
+        super().ensure_installed(engine)
+
+    def forward_device(self, engine, U_dev, out=None):
+        if self.flag_noise:
+            raise ValueError("the device hook evaluates the noise-free map only")
+        self.ensure_installed(engine)
+        return engine.forward_apply(engine.map_apply(U_dev, out=engine.map_scratch), out=out)
+
+
+class elliptic(_map_hook):
+    """The two-point observation of the 1-d elliptic problem (ces/utils.py:53-89): ``p(x) = u2 x + exp(-u1)(-x^2/2 + x/2)``
+    at ``x1 = 1/4`` and ``x2 = 3/4``.  ``__call__`` returns the LIST ``[x, y]`` as the reference does (``dG=True``: the
+    2 x 2 Jacobian); ``theta`` is one particle or a (2, J) block."""
+
+    map_kind = "elliptic"
+    fused_kind = True
+
+    def __init__(self, flag_noise=False):
+        self.x1 = 1. / 4
+        self.x2 = 3. / 4
+        self.flag_noise = flag_noise
+        self.sigma = np.sqrt(0.01)
+        self.model_name = "elliptic"
+        self.type = "map"
+
+    def __repr__(self):
+        return self.model_name
+
+    def __str__(self):
+        return self.model_name
+
+    def __call__(self, theta, dG=False):
+        u1, u2 = theta
+        x = (u2 * self.x1) + (np.exp(-u1) * (-self.x1**2 + self.x1) * 0.5)
+        y = (u2 * self.x2) + (np.exp(-u1) * (-self.x2**2 + self.x2) * 0.5)
+        if self.flag_noise:                               # (:80-82: len(): a block of particles only)
+            x += (self.sigma * np.random.normal(size=len(u1)))
+            y += (self.sigma * np.random.normal(size=len(u2)))
+        if dG:
+            return np.array([[-np.exp(-u1) * (-self.x1**2 + self.x1) * 0.5, self.x1],
+                             [-np.exp(-u1) * (-self.x2**2 + self.x2) * 0.5, self.x2]])
+        return [x, y]
+
+    def _map_desc(self):
+        return (self.x1, self.x2)
+
+
+class banana(_map_hook):
+    """The banana-shaped map ``(a u1, u2 / a - b (u1^2 + a^2))`` (ces/utils.py:91-122) with its correlated ``Gamma``.  One
+    particle per call: the (2,) noise term is added -- times ``flag_noise`` -- whether or not noise is on, so the global
+    RNG advances by two normals per call and a (2, J) block does not broadcast for J other than 2."""
+
+    map_kind = "banana"
+    fused_kind = True
+
+    def __init__(self, a=1.0, b=.5, rho=.9, flag_noise=False):
+        self.flag_noise = flag_noise
+        self.sigma = np.sqrt(0.55)
+        self.model_name = "banana"
+        self.type = "map"
+        self.a = a
+        self.b = b
+        self.Gamma = np.identity(2)
+        self.Gamma[0, 1] = rho
+        self.Gamma[1, 0] = rho
+        self.Gamma = (0.55**2) * self.Gamma
+
+    def __repr__(self):
+        return self.model_name
+
+    def __str__(self):
+        return self.model_name
+
+    def __call__(self, theta, dG=False):
+        u1, u2 = theta
+        x = u1 * self.a
+        y = u2 / self.a - self.b * (u1**2 + self.a**2)
+        return np.array([x, y]) + self.flag_noise * np.linalg.cholesky(self.Gamma).dot(np.random.normal(0, 1, [2, ]))
+
+    def _map_desc(self):
+        return (self.a, self.b)
 
 
 def __getattr__(name):

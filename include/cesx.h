@@ -538,6 +538,45 @@ int cesx_mh_stats(cesx_handle h, unsigned long long* steps, double* rate, unsign
    Synchronises.  CESX_ESTATE before a start (cesx_mh_start / cesx_gp_start). */
 int cesx_mh_phi(cesx_handle h, double* phi_host);
 
+/* ---- Closed-form forward maps over the columns (ces/utils.py:33-122; kernels_maps.hip) --
+   The maps of ces_amd.utils.elliptic, banana and the exp prologue of lineal_log, one column per LANE, evaluated in fp64
+   whatever the engine dtype and rounded on the store:
+       CESX_MAP_ELLIPTIC (prm: x1, x2)  g_i = u2 x_i + exp(-u1) (-x_i^2 + x_i) / 2,  i = 1, 2      (p = n_obs = 2)
+       CESX_MAP_BANANA   (prm: a, b)    g_1 = a u1,  g_2 = u2 / a - b (u1^2 + a^2)                 (p = n_obs = 2)
+       CESX_MAP_EXP      (no prm)       G = exp(U), (p x J_local) in the engine dtype: lineal_log's prologue, followed by
+                                        cesx_forward_apply with the installed lineal map
+   The stage keeps state of its own: the lineal, the Darcy and the Lorenz maps and the problem are untouched. */
+#define CESX_MAP_ELLIPTIC 1
+#define CESX_MAP_BANANA   2
+#define CESX_MAP_EXP      3
+typedef struct {
+    int struct_bytes;            /* sizeof(cesx_map_desc) */
+    int kind;                    /* CESX_MAP_* */
+    double prm[8];               /* the kind's parameters (above); the rest is ignored */
+} cesx_map_desc;
+/* Copies the descriptor; replaces an earlier one.  CESX_EINVAL for an unknown kind, a parameter that is not finite (banana:
+   a == 0) or a handle whose shape the kind does not fit (elliptic and banana need p = n_obs = 2); the installed map is kept
+   then.  Launches nothing. */
+int cesx_map_set(cesx_handle h, const cesx_map_desc* desc);
+/* U_dev (p x J_local, engine dtype) -> G_dev (n_obs x J_local; CESX_MAP_EXP: p x J_local), engine dtype.  G_dev may equal
+   U_dev only for CESX_MAP_EXP.  CESX_ESTATE without an installed map. */
+int cesx_map_apply(cesx_handle h, const void* U_dev, void* G_dev, void* stream);
+/* n_steps Metropolis steps of every chain in ONE launch, one chain per lane, for the installed map of a fused kind
+   (CESX_MAP_ELLIPTIC, CESX_MAP_BANANA): per step k = 0 .. n_steps - 1 the proposal of cesx_mh_propose, the map, phi and the
+   test of cesx_mh_accept, with the noise of step step_index + k -- xi_dev[n_steps][p][J_local] (engine dtype) and
+   logu_dev[n_steps][J_local] (fp64), or NULL for the device draws of those steps: the counter words of cesx_mh_propose /
+   cesx_mh_accept, the normals as an fp64 engine draws them.  Afterwards U_dev, the chains' phi, the accept counters and the
+   step count are as n_steps calls of cesx_mh_propose / cesx_map_apply / cesx_mh_accept would have left them (up to the
+   rounding of a different order of the same products): fused launches and single steps may alternate.
+   trace_dev (NULL: none) receives the states after the steps with (k + 1) % stride == 0, laid out [kept][p][J_local] in the
+   engine dtype, kept = n_steps / stride.
+   All arithmetic inside a launch is fp64 for either engine dtype; an fp32 engine rounds where it stores -- trace_dev, and
+   U_dev at the end of the launch: its state is rounded at launch boundaries only, not after every step.
+   CESX_ESTATE without cesx_set_problem, cesx_mh_set_proposal, cesx_mh_start or an installed map of a fused kind; CESX_EINVAL
+   for n_steps < 1, stride < 1 or a step index >= 2^31.  Neither launches anything. */
+int cesx_mh_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride, void* U_dev, void* trace_dev,
+                    const void* xi_dev, const double* logu_dev, void* stream);
+
 /* ---- Emulate: GP prediction and the GP sampler over the columns (ces/emulate.py, ces/sample.py:17-119) --
    One exact GP per output, trained on the host (ces_amd/emulate.py); the engine holds its own fp64 image of them and
    evaluates them for every column at once.  GP i maps an input x to z = A_i (x - c) (A_i = diag(1/l_i) S^{-1} lower
