@@ -763,6 +763,11 @@ int launch_gp_predict(Engine& e, const void* X, double* mean, double* var, bool 
 // counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double* mean, const double* var, void* U,
                     const double* logu, unsigned step, hipStream_t s);
+// kernels_gpchain.hip: n_steps Metropolis steps of every chain on the emulator in one launch (mode CESX_GP_GAMMA / _VAR /
+// _GAMMA_VAR; include/cesx.h, cesx_gp_run).  gp_run_fits: the tile's LDS need is within the workgroup budget
+bool gp_run_fits(int p, int Jp, int n_gp);
+int launch_gp_run(Engine& e, int mode, uint64_t step_index, int n_steps, int stride, bool nugget, void* U, void* trace,
+                  const void* xi, const double* logu, hipStream_t s);
 // kernels_gpdense.hip: the same for CESX_GP_DENSE -- Sigma_j = Gamma + B diag(var_j) B^T factored per chain; mean and var
 // are (gpd.k x J).  gp_dense_prepare: once per installed descriptor (the kernels' dynamic LDS limit for n and k)
 int gp_dense_prepare(Engine& e, int n, int k);

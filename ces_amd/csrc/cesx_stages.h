@@ -25,6 +25,7 @@ struct MhState {
     DevBuf<double> phi;                // [J] phi of the chains' current states
     DevBuf<unsigned long long> cnt;    // [J] accepted proposals per chain
     DevBuf<double> LSi;                // [p][p] L_Sigma^{-1} of a dense Sigma, fp64: the dense prior's factor as gp_score_kernel reads it
+    DevBuf<double> bS;                 // [p][p] b S, fp64 row-major: the proposal as gp_chain_kernel reads it (cesx_gp_run)
     std::vector<double> h_bS;          // [p][p] b S on the host: cesx_mh_run_map passes it by value
     bool none() const { return kind < 0; }
     void drop() { kind = -1; started = false; }      // every buffer is sized by the engine: kept

@@ -883,6 +883,8 @@ int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) 
     for (double& v : bS) v *= b;
     TRY(mh_upload_tri(e, bS.data(), e.mh.W, e.mh.Wf));
     e.mh.h_bS = bS;
+    TRY_BUF(e.mh.bS.ensure((size_t)p * p * 8));
+    TRY(upload(e, e.mh.bS, bS.data(), (size_t)p * p * 8));
     e.mh.dense_prior = kind == CESX_MH_RW && !e.diag_sigma;
     if (!e.diag_sigma) {                       // gp_score_kernel's fp64 L_Sigma^{-1} (RW and pCN: ces/sample.py:57 / :96)
         TRY_BUF(e.mh.LSi.ensure((size_t)p * p * 8));
@@ -1161,6 +1163,26 @@ int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U, const 
     else if (mode == CESX_GP_PROJ) TRY(launch_gp_score_proj(e, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
     else TRY(launch_gp_score(e, mode, false, P, mean, var, U, logu, mh_step_word(step_index), (hipStream_t)stream));
     ++e.mh.steps;
+    return CESX_OK;
+}
+
+int cesx_gp_run(cesx_handle h, int mode, uint64_t step_index, int n_steps, int stride, int nugget, void* U, void* trace,
+                const void* xi, const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U) { e.err = "cesx_gp_run: null pointer"; return CESX_EINVAL; }
+    if (n_steps < 1 || stride < 1) { e.err = "cesx_gp_run: n_steps and stride must be >= 1"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull || step_index + (uint64_t)n_steps > 0x80000000ull) { e.err = "cesx_gp_run: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    if (mode == CESX_GP_DENSE || mode == CESX_GP_PROJ) { e.err = "cesx_gp_run: CESX_GP_DENSE and CESX_GP_PROJ stay on the step path (cesx_mh_propose / cesx_gp_predict / cesx_gp_accept)"; return CESX_EINVAL; }
+    if (mode != CESX_GP_GAMMA && mode != CESX_GP_VAR && mode != CESX_GP_GAMMA_VAR) { e.err = "cesx_gp_run: unknown likelihood mode"; return CESX_EINVAL; }
+    if (!e.problem_set || e.mh.none() || e.gp.none() || !e.mh.started) { e.err = "cesx_gp_run: needs cesx_set_problem, cesx_mh_set_proposal, cesx_gp_set and a start (cesx_gp_start / cesx_mh_start)"; return CESX_ESTATE; }
+    if (mode != CESX_GP_GAMMA && e.whiten) { e.err = "cesx_gp_run: the variance modes need a diagonal Gamma"; return CESX_EINVAL; }
+    if (e.gp.n != e.n) { e.err = "cesx_gp_run: the emulator's n_gp differs from n_obs"; return CESX_EINVAL; }
+    if (!gp_run_fits(e.p, e.gp.Jp, e.gp.n)) { e.err = "cesx_gp_run: the tile does not fit in LDS (256 (3 p + J_p + 2 n_gp) + 8192 bytes > 160 KiB); take the step path"; return CESX_EUNSUPPORTED; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_gp_run(e, mode, step_index, n_steps, stride, nugget != 0, U, trace, xi, logu, (hipStream_t)stream));
+    e.mh.steps += (unsigned long long)n_steps;
     return CESX_OK;
 }
 

@@ -18,7 +18,7 @@ OK, EINVAL, ENOTPD, EHIP, ESTATE, EUNSUPPORTED, ENOCONV = 0, 1, 2, 3, 4, 5, 6
 F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
-ABI_VERSION = 6
+ABI_VERSION = 7
 MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
@@ -31,7 +31,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_profile_clock", "cesx_calibrate_mfma", "cesx_profile_gap", "cesx_moments_rest_lineal", "cesx_copy_cols_async",
            "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count",
            "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats", "cesx_mh_phi",
-           "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_dense_set", "cesx_gp_proj_set",
+           "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_run", "cesx_gp_dense_set", "cesx_gp_proj_set",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_darcy_set_streamed", "cesx_darcy_workspace_bytes", "cesx_lorenz_set", "cesx_lorenz_apply",
            "cesx_lorenz_three_set", "cesx_lorenz_three_apply", "cesx_map_set", "cesx_map_apply", "cesx_mh_run_map")
@@ -266,7 +266,8 @@ def load_library(path=None):
     lib.cesx_gp_predict.argtypes = [vp, vp, vp, vp, i32, vp]
     lib.cesx_gp_start.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.cesx_gp_accept.argtypes = [vp, i32, u64, vp, vp, vp, vp, vp, vp]
-    lib.cesx_gp_dense_set.argtypes = [vp, C.POINTER(GpDenseDesc)]
+    lib.cesx_gp_run.argtypes = [vp, i32, u64, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.cesx_gp_dense_set.argtypes =[vp, C.POINTER(GpDenseDesc)]
     lib.cesx_gp_proj_set.argtypes = [vp, C.POINTER(GpProjDesc)]
     lib.cesx_mh_phi.argtypes = [vp, dp]
     lib.cesx_gpfit_set.argtypes = [vp, C.POINTER(GpFitDesc)]
@@ -1029,6 +1030,30 @@ class Engine:
                                                 mean.data_ptr(), None if var is None else var.data_ptr(),
                                                 None if logu is None else logu.data_ptr(), self._stream()))
         self._keep_gp_a = (U, P, mean, var, logu)
+
+    def gp_run(self, mode, step_index, n_steps, U, stride=1, trace=None, xi=None, logu=None, nugget=True):
+        """``n_steps`` Metropolis steps of every chain on the installed emulator in one launch (cesx_gp_run), likelihood
+        mode ``mode`` of GP_MODES ('gamma', 'var', 'gamma_var'): ``U`` (p, J) is advanced in place, the engine's phi,
+        counters and step count follow.  ``trace`` (n_steps // stride, p, J) engine dtype, or None; ``xi`` (n_steps, p, J)
+        engine dtype and ``logu`` (n_steps, J) float64, or None for the device draws of steps ``step_index`` ..
+        ``step_index + n_steps - 1``; ``nugget`` as in ``gp_predict``.  An emulator whose tile does not fit in LDS raises
+        ``CesxError`` with code EUNSUPPORTED."""
+        n_steps, stride = int(n_steps), int(stride)
+        for name, t, shape, dt in (("U", U, (self.p, self.J), self.torch_dtype),
+                                   ("trace", trace, (max(n_steps, 0) // max(stride, 1), self.p, self.J), self.torch_dtype),
+                                   ("xi", xi, (n_steps, self.p, self.J), self.torch_dtype),
+                                   ("logu", logu, (n_steps, self.J), torch.float64)):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError("gp_run: %s must be a contiguous %s tensor of shape %s" % (name, dt, shape))
+        with torch.cuda.device(self.device):
+            rc = self.lib.cesx_gp_run(self._h, GP_MODES[mode], int(step_index), n_steps, stride, 1 if nugget else 0,
+                                      U.data_ptr(), None if trace is None or trace.numel() == 0 else trace.data_ptr(),
+                                      None if xi is None else xi.data_ptr(),
+                                      None if logu is None else logu.data_ptr(), self._stream())
+            if rc == EUNSUPPORTED:            # (the LDS limit, not the reference's missing LM_procedure of _check)
+                raise CesxError(rc, self.lib.cesx_last_error(self._h).decode())
+            self._check(rc)
+        self._keep_gp_run = (U, trace, xi, logu)
 
     # -- GP training: the batched likelihood and gradient (include/cesx.h, cesx_gpfit_*; ces_amd/emulate.py drives it) --
     def gpfit_set(self, X, Y, family, ard=True, mean="zero"):

@@ -35,6 +35,14 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          (three launches per step) otherwise; ``False`` forces the step path; ``True`` on a model without a
                          fused kernel raises ``ValueError``.  Both paths draw the same noise and leave the same chains up to
                          the rounding of a different product order.
+                         gp_mh with ``chains=``: ``True`` takes the fused chain kernel of the emulator (``gp_chain_kernel``,
+                         ``cesx_gp_run``: one workgroup per 32 chains, per step the proposal, every GP's mean and variance on
+                         one K* panel in LDS, phi and the test; the likelihoods Gamma, diag(gvars) and diag(Gamma) +
+                         diag(gvars)); ``None`` (default, ``GP_FUSED_DEFAULT``) and ``False`` take the step path.  ``True``
+                         with ``pca_tools`` (the dense and the projected Sigma stay on the step path) or ``separable``
+                         raises ``ValueError``, and so does an emulator whose tile does not fit in LDS.  A launch runs at
+                         most ``GP_FUSED_WORK`` of arithmetic.  ``self.fused_launches`` counts the fused launches of the last
+                         call of either sampler (0: the step path).
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -54,6 +62,22 @@ except Exception:                      # pragma: no cover - tqdm is optional plu
         return it
 
 
+def fused_chunks(n_mcmc, stride, steps_max, buffer_bytes, bytes_per_step, work_max=None, work_per_step=0):
+    """The launches of a fused run of ``n_mcmc`` steps: ``(K_max, [K_0, K_1, ...])``, every launch ``K_max`` steps but the last.
+
+    ``K_max`` is a multiple of ``stride`` -- so that a launch's own count of kept states continues the run's -- and as large
+    as the caps allow: ``steps_max`` steps, ``buffer_bytes // bytes_per_step`` (one launch's noise and trace) and, with
+    ``work_max``, ``work_max // work_per_step`` (the arithmetic of one launch).  A stride longer than every cap still makes
+    one launch: ``K_max = stride``.  Pure: no engine, no device."""
+    n_mcmc, stride = int(n_mcmc), max(1, int(stride))
+    cap = min(int(steps_max), int(buffer_bytes) // max(1, int(bytes_per_step)))
+    if work_max is not None and work_per_step > 0:
+        cap = min(cap, int(work_max) // int(work_per_step))
+    cap = max(1, cap)
+    K_max = max(stride, cap // stride * stride)
+    return K_max, [min(K_max, n_mcmc - k0) for k0 in range(0, n_mcmc, K_max)]
+
+
 class MCMC(object):
     """Metropolis-Hastings samplers of ces/sample.py (:12-202)."""
 
@@ -62,6 +86,14 @@ class MCMC(object):
     FUSED_DEFAULT = True
     FUSED_STEPS_MAX = 4096
     FUSED_BUFFER_BYTES = 64 << 20
+    # build-only, gp_mh(chains=, fused=): what fused=None resolves to (the step path: every call without fused= runs as it
+    # did before the fused kernel existed; the measurement: NOTEBOOK.md, tools/gp_chain_bench.py), and the arithmetic one
+    # launch may hold.  A fused gp step does real work -- per chain and GP the K* panel and its triangular product,
+    # J_p (J_p / 2 + p + 8) multiply-adds -- so a launch is capped by K M n_gp J_p (J_p / 2 + p + 8) <= GP_FUSED_WORK as well.
+    # The constant is 50 steps at shape E1 (65 536 chains, p = 8, 32 GPs, J_t = 512), where NOTEBOOK.md records 19 ms per
+    # step: a launch of about 1 s on a card that others share, not the minute that FUSED_STEPS_MAX steps would take.
+    GP_FUSED_DEFAULT = False
+    GP_FUSED_WORK = 50 * 65536 * 32 * 512 * (512 // 2 + 8 + 8)
 
     def __init__(self):
         self.mute_bar = False
@@ -95,6 +127,8 @@ class MCMC(object):
                               "not installed; ces/sample.py fails when it imports gpflow, :8)")
         if kwargs.get("chains", None) is not None:
             return self._gp_mh_device(enka, n_mcmc, prior, delta, enka_scaling, kwargs)
+        if kwargs.get("fused", None) is not None:
+            raise ValueError("fused=%r chooses between the device paths of chains=M; the host path has one" % (kwargs.get("fused"),))
         if kwargs.get("sigma_form", None) is not None:
             raise ValueError("sigma_form=%r chooses between the device kernels of chains=M; the host path has one form"
                              % (kwargs.get("sigma_form"),))
@@ -251,20 +285,26 @@ class MCMC(object):
             self._mh_key = key
         return self._mh_eng
 
-    def _mh_device(self, enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi, fused=False):
+    def _mh_device(self, enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi, fused=False,
+                   fused_work=0):
         """M = kwargs['chains'] chains on the engine: what ``model_mh(chains=)`` and ``gp_mh(chains=)`` have in common.
 
         Gamma                    the data covariance handed to ``set_problem``
         scales_of(update)        the proposal scales S (p, p), formed once ``prior`` and ``update`` have been checked
         bind(eng, M)             runs after ``mh_set_proposal``; returns ``score_start(U)`` (phi of the states U into the
-                                 engine, counters cleared) and ``score_accept(step, U, P, logu)`` (phi of P, the test, U := P
-                                 where it passes)
+                                 engine, counters cleared), ``score_accept(step, U, P, logu)`` (phi of P, the test, U := P
+                                 where it passes) and ``run_steps(step, K, U, stride, trace, xi, logu)`` (K steps in one
+                                 launch: ``eng.mh_run_map`` for a map, ``eng.gp_run`` for the emulator; None where the
+                                 sampler has no fused kernel)
         resume_keeps_start_phi   the reference's model_mh scores the START point before it looks for ``self.samples`` and
                                  keeps that phi for the resumed states (ces/sample.py:131-163); its gp_mh scores the resumed
                                  states (:31-39).  True: the first, for ``noise='numpy'`` (``noise='device'`` re-scores the
                                  resumed states either way: the exact resume of model_mh's docstring)
-        fused                    the steps run through ``eng.mh_run_map`` (the fused chain kernel of the map ``bind``
-                                 installed, K Metropolis steps per launch) instead of propose / ``score_accept``
+        fused                    the steps run through ``run_steps`` (K Metropolis steps per launch) instead of propose /
+                                 ``score_accept``
+        fused_work               the arithmetic of one fused step of all chains, in the units of ``GP_FUSED_WORK`` (0: a launch
+                                 is capped by ``FUSED_STEPS_MAX`` and ``FUSED_BUFFER_BYTES`` alone)
+        ``self.fused_launches`` is the number of fused launches of the call, 0 on the step path.
         """
         import torch
         M = kwargs["chains"]
@@ -296,8 +336,9 @@ class MCMC(object):
         eng = self._mh_engine(p, n, M)
         eng.set_problem(np.asarray(self.y_obs, dtype=np.float64).reshape(n), Gamma, mu, cov, mu)
         eng.mh_set_proposal(update, scales, kwargs.get("beta", 0.5))
-        score_start, score_accept = bind(eng, M)
+        score_start, score_accept, run_steps = bind(eng, M)
         P = eng.empty(p)
+        self.fused_launches = 0
 
         resume = hasattr(self, "samples")
         prev, base, kept = None, 0, [U0.copy()]
@@ -315,16 +356,17 @@ class MCMC(object):
             base, kept = int(getattr(self, "_mh_next_step", 0)), []
 
         if fused:
-            # launches of at most K_max steps (cesx_mh_run_map): K_max a multiple of the stride -- so that a launch's own count
-            # of kept states continues the run's -- and small enough that one launch's noise and trace stay under the budget.
+            # launches of at most K_max steps (cesx_mh_run_map / cesx_gp_run; fused_chunks): K_max a multiple of the stride --
+            # so that a launch's own count of kept states continues the run's -- and small enough that one launch's noise and
+            # trace stay under the budget and, for the emulator, its arithmetic under GP_FUSED_WORK.
             # The trace buffer is allocated once per run; each launch's trace crosses to the host once.
             esz = eng.np_dtype.itemsize
             per_step = -(-M * p * esz // stride) + (M * (p * esz + 8) if self.noise == "numpy" else 0)     # trace; xi and log u
-            cap = max(1, min(self.FUSED_STEPS_MAX, self.FUSED_BUFFER_BYTES // per_step))
-            K_max = max(stride, cap // stride * stride)
+            K_max, chunks = fused_chunks(n_mcmc, stride, self.FUSED_STEPS_MAX, self.FUSED_BUFFER_BYTES, per_step,
+                                         self.GP_FUSED_WORK if fused_work else None, fused_work)
             trace = torch.empty((min(K_max, n_mcmc) // stride, p, M), dtype=eng.torch_dtype, device=eng.device)
-            for k0 in tqdm(range(0, n_mcmc, K_max), desc="MCMC samples: ", disable=self.mute_bar):
-                K = min(K_max, n_mcmc - k0)
+            for i, K in enumerate(tqdm(chunks, desc="MCMC samples: ", disable=self.mute_bar)):
+                k0 = i * K_max
                 xi_t = logu_t = None
                 if self.noise == "numpy":                 # the step loop's draws in the step loop's order, stacked
                     xi, logu = np.empty((K, p, M)), np.empty((K, M))
@@ -334,7 +376,8 @@ class MCMC(object):
                     xi_t = torch.as_tensor(xi, device=eng.device).to(eng.torch_dtype).contiguous()
                     logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
                 tr = trace[:K // stride]
-                eng.mh_run_map(base + k0, K, U, stride=stride, trace=tr, xi=xi_t, logu=logu_t)
+                run_steps(base + k0, K, U, stride, tr, xi_t, logu_t)
+                self.fused_launches += 1
                 if K // stride:
                     kept.extend(tr.cpu().numpy().astype(np.float64))
             if n_mcmc % stride and n_mcmc > 0:            # the run's last state, where the stride does not land on it
@@ -414,7 +457,7 @@ class MCMC(object):
             def score_accept(step, U, P, logu):       # phi(P) NaN for a failed integration: the test rejects (mh_test)
                 fwd(P, GP)
                 eng.mh_accept(step, U, P, GP, logu=logu)
-            return score_start, score_accept
+            return score_start, score_accept, None
 
         def bind(eng, M):
             takes_out = hook_takes_out(model.forward_device)
@@ -435,7 +478,10 @@ class MCMC(object):
             def score_accept(step, U, P, logu):
                 fwd(P, GP)
                 eng.mh_accept(step, U, P, GP, logu=logu)
-            return score_start, score_accept
+
+            def run_steps(step, K, U, stride, trace, xi, logu):
+                eng.mh_run_map(step, K, U, stride=stride, trace=trace, xi=xi, logu=logu)
+            return score_start, score_accept, run_steps if fused else None
 
         self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_pde if pde else bind, resume_keeps_start_phi=True,
                         fused=fused)
@@ -445,6 +491,16 @@ class MCMC(object):
         from . import emulate
         from . import engine as _engine
         host = "; run gp_mh without chains= (the host path)"
+        # fused: None -- GP_FUSED_DEFAULT, the step path --, False, True (the fused chain kernel, cesx_gp_run)
+        fused = kwargs.get("fused", None)
+        if fused not in (None, False, True):
+            raise ValueError("fused must be None, False or True, got %r" % (fused,))
+        if fused and kwargs.get("separable", False):
+            raise ValueError("fused=True: separable predicts one point at a time and has no device path" + host)
+        if fused and kwargs.get("pca_tools", None) is not None:
+            raise ValueError("fused=True: the dense and the projected Sigma of pca_tools stay on the step path (the fused chain "
+                             "kernel scores Gamma, diag(gvars) and diag(Gamma) + diag(gvars)); pass fused=None or False")
+        fused = self.GP_FUSED_DEFAULT if fused is None else bool(fused)
         if kwargs.get("separable", False):
             raise ValueError("chains=: separable predicts one point at a time" + host)
         p, n = enka.p, enka.n_obs
@@ -524,6 +580,20 @@ class MCMC(object):
             def score_accept(step, U, P, logu):
                 eng.gp_predict(P, nugget=nugget, var=want_var, out=(mean_p, var_p))
                 eng.gp_accept(mode, step, U, P, mean_p, var_p, logu=logu)
-            return score_start, score_accept
 
-        self._mh_device(enka, n_mcmc, prior, kwargs, G, scales_of, bind, resume_keeps_start_phi=False)
+            def run_steps(step, K, U, stride, trace, xi, logu):
+                try:
+                    eng.gp_run(mode, step, K, U, stride=stride, trace=trace, xi=xi, logu=logu, nugget=nugget)
+                except _engine.CesxError as exc:
+                    if exc.code != _engine.EUNSUPPORTED:
+                        raise
+                    raise ValueError("chains=, fused=True: %s -- the fused chain kernel keeps a tile's K* panel, GP rows and "
+                                     "states in LDS, 256 (3 p + J_p + 2 n_gp) + 8192 bytes <= 160 KiB; pass fused=False for the "
+                                     "step path" % exc)
+            return score_start, score_accept, run_steps if fused else None
+
+        # the arithmetic of one fused step of all chains, in the units of GP_FUSED_WORK
+        Jp = (int(img["Jt"]) + 15) // 16 * 16
+        work = int(kwargs["chains"]) * n_gp * Jp * (Jp // 2 + p + 8) if fused else 0
+        self._mh_device(enka, n_mcmc, prior, kwargs, G, scales_of, bind, resume_keeps_start_phi=False, fused=fused,
+                        fused_work=work)

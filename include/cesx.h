@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CESX_ABI_VERSION 6
+#define CESX_ABI_VERSION 7
 
 /* status codes */
 #define CESX_OK            0
@@ -620,6 +620,30 @@ int cesx_gp_predict(cesx_handle h, const void* X_dev, double* mean_dev, double* 
 int cesx_gp_start(cesx_handle h, int mode, const void* U_dev, const double* mean_dev, const double* var_dev, void* stream);
 int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev, const void* P_dev, const double* mean_dev,
                    const double* var_dev, const double* logu_dev, void* stream);
+/* n_steps Metropolis steps of every chain on the installed emulator in ONE launch (kernels_gpchain.hip, gp_chain_kernel: one
+   workgroup per tile of 32 chains), in mode CESX_GP_GAMMA (diagonal or dense Gamma), CESX_GP_VAR or CESX_GP_GAMMA_VAR: per
+   step k = 0 .. n_steps - 1 the proposal of cesx_mh_propose, the prediction of cesx_gp_predict (nugget as there; the
+   variance only where the mode reads it) and the score and test of cesx_gp_accept, with the noise of step step_index + k --
+   xi_dev[n_steps][p][J_local] (engine dtype) and logu_dev[n_steps][J_local] (fp64), or NULL for the device draws of those
+   steps: the counter words of cesx_mh_propose / cesx_gp_accept, the normals as an fp64 engine draws them.  The GP rows of
+   the proposals stay on chip: for the same fp64 proposal they are bit-identical to cesx_gp_predict's.  Afterwards U_dev, the
+   chains' phi, the accept counters and the step count are as n_steps calls of cesx_mh_propose / cesx_gp_predict /
+   cesx_gp_accept would have left them (up to the rounding of a different order of the proposal's products): fused launches
+   and single steps may alternate, cesx_mh_stats and cesx_mh_phi read the same state.  A proposal whose phi is NaN or
+   inf - inf is rejected; a chain whose current phi is NaN stays where it is.
+   trace_dev (NULL: none) receives the states after the steps with (k + 1) % stride == 0, laid out [kept][p][J_local] in the
+   engine dtype, kept = n_steps / stride.
+   All arithmetic inside a launch is fp64 for either engine dtype; an fp32 engine rounds where it stores -- trace_dev, and
+   U_dev at the end of the launch: its state is rounded at launch boundaries only, not after every step.
+   Limit: a tile's K* panel, GP rows, states and partial sums live in LDS,
+       256 (3 p + J_p + 2 n_gp) + 8192 bytes <= 160 KiB,    J_p = J_t rounded up to 16
+   (p = 2, n_gp = 10: J_t <= 576); beyond it CESX_EUNSUPPORTED -- the global-memory panel of cesx_gp_predict is not carried
+   over, take the step path.
+   CESX_ESTATE without cesx_set_problem, cesx_mh_set_proposal, cesx_gp_set or a start (cesx_gp_start / cesx_mh_start);
+   CESX_EINVAL for n_steps < 1, stride < 1, a NULL U_dev, a step index that reaches 2^31, mode CESX_GP_DENSE or CESX_GP_PROJ
+   (these stay on the step path), a variance mode with a dense Gamma, or n_gp != n_obs.  None of these launches anything. */
+int cesx_gp_run(cesx_handle h, int mode, uint64_t step_index, int n_steps, int stride, int nugget, void* U_dev,
+                void* trace_dev, const void* xi_dev, const double* logu_dev, void* stream);
 /* CESX_GP_DENSE: k GPs on PCA-decorrelated outputs (pca_tools of ces/emulate.py:74-77 and ces/sample.py:52-53, :91-92).  The
    data space is rebuilt per chain j from column j of the (k x J_local) rows of cesx_gp_predict (n_gp == k):
        d = B m_j + g0 - y,    Sigma_j = Gamma + B diag(v_j) B^T,    phi = 1/2 d^T Sigma_j^{-1} d [+ 1/2 log det Sigma_j] + prior term
