@@ -1,7 +1,7 @@
 """One engine driven through a sequence of steps: the tables and the stepper, written for a device engine (``ces_amd.engine``) and
-run so far by tests/test_engine_reuse_host.py against a numpy stand-in for the engine.  The device module that drives the same
-stepper has not been seen to pass on an MI355X and is therefore not in the tree (NOTEBOOK.md, "Tests: one engine across rules,
-problems and stages").
+run by tests/test_engine_reuse_host.py against a numpy stand-in for the engine and by tests/test_gpu_engine_reuse.py against the
+engine itself on a device (NOTEBOOK.md, "Tests: one engine across rules, problems and stages" and "Tests: the engine-reuse
+sequences on a device").
 
 Production keeps ONE engine for the life of a ``calibrate.sampling`` object, calls ``set_problem`` before every step and changes
 route whenever the caller changes the rule or the time step.  What a step returns then depends on state that outlives a step in
@@ -75,6 +75,56 @@ for _k in range(6):
         P_STEPS.append(step("eks", prob=_k))
 P_DENSE = [(False, False), (False, True), (True, False), (True, False), (True, False), (False, False)]      # (dense Gamma, dense Sigma)
 
+# T: every other stage of the engine between Calibrate steps that leave the PROBLEM alone: the step behind a block runs on the
+# predicted shift, on warm inverses, possibly with a noise block drawn ahead, and must not notice the block.  R's steps under flow
+# 'cycle', one problem per shape with a dense Gamma (whitening live) and a dense Sigma (the dense prior live).  No block calls
+# set_problem with other values; the stepper sets the same problem again before every step (a no-op in the engine), and a block
+# sets its own proposal and descriptors whenever it runs.
+T_STEPS = R_STEPS
+T_ENGINE = (4, 5, 65, "float64")                  # the smallest shape every stage installs at (tests/test_gpu_engine_state.py)
+# the blocks, in the order they are taken (cycling when they run out).  At step i >= 1 block (i - 1) % len runs in ``between``
+# in front of step i AND in ``before_result`` of step i - 1 (behind the launch of step i - 1, before its result is read).
+T_BLOCKS = ("lineal",          # forward_apply of the installed linear map
+            "darcy",           # Darcy resident, K = 4: darcy_apply
+            "darcy_streamed",  # Darcy streamed, K = 4: a re-install across solvers, then apply
+            "l96",             # homogeneous Lorenz '96 at (5, 3): l96_apply with the carried W
+            "gp",              # gp_set with J_t = 17, gp_predict with variance
+            "mh",              # mh_set_proposal RW on the dense prior, mh_start, 2 x (mh_propose engine noise, mh_accept device
+            #                    uniform), mh_phi, mh_stats
+            "gp_dense",        # gp_dense_set, gp_start('dense'), 2 x gp_accept
+            "gp_proj",         # gp_proj_set, gp_start('proj'), 2 x gp_accept
+            "gp_run",          # fused chains: gp_run of 5 steps in mode 'gamma' (n_gp = n_obs; 256 (3 p + 32 + 2 n) + 8192 B of LDS)
+            "gpfit",           # gpfit_set with J_t = 17, 2 GPs, gpfit_eval
+            "all")             # all of the above, one after another
+# E1 (256, 64, 512) fp32, after include/cesx.h: the Darcy maps need p <= K^2 (K = 4: p <= 16); the Lorenz '96 map needs n_obs = 5
+# or 5 n_slow; cesx_gp_run in mode 'gamma' needs n_gp = n_obs = 64 GPs and 256 (3 * 256 + 32 + 2 * 64) + 8192 = 245 760 B of
+# LDS > 160 KiB (CESX_EUNSUPPORTED).  The others carry no limit that E1 passes: k <= n_obs <= 128 (dense), k <= 128 (proj).
+T_BLOCKS_E1 = ("lineal", "gp", "mh", "gp_dense", "gp_proj", "gpfit", "all")
+# (name, engine shape, blocks, (dense Gamma, dense Sigma)).  E1 with a dense Sigma takes form 1 and never the chained form 2
+# (``pick``: form 2 needs a diagonal Sigma), so E1 runs twice: with the diagonal Sigma (forms 2 and 0) and with the dense one.
+T_RUNS = (("T", T_ENGINE, T_BLOCKS, (True, True)),
+          ("E1 diagonal Sigma", ENGINES["E1"], T_BLOCKS_E1, (True, False)),
+          ("E1 dense Sigma", ENGINES["E1"], T_BLOCKS_E1, (True, True)))
+T_MH_STEP0 = 1000                                 # MH step index of the sequence's first block call; each call takes 16
+
+
+def t_plan(blocks, n_steps=len(R_STEPS)):
+    """(between, before_result): {step: (call number, block name)} of sequence T.  The call number counts the block calls of the
+    sequence in the order they run; a call's MH step indices start at T_MH_STEP0 + 16 * call number."""
+    between, before = {}, {}
+    for i in range(1, n_steps):
+        name = blocks[(i - 1) % len(blocks)]
+        before[i - 1] = (2 * (i - 1), name)
+        between[i] = (2 * (i - 1) + 1, name)
+    return between, before
+
+
+def t_problem(fam, shape, dense):
+    """(A, U0, [problem]) of one run of T"""
+    p, n, J, dtype = shape
+    d = cr.family(fam, p, n, J, dtype, dense_gamma=dense[0], dense_sigma=dense[1])
+    return d["A"], d["U0"], [{k: d[k] for k in ("y", "Gamma", "mu", "sigma", "ustar")}]
+
 
 def flow_of(flow, i):
     """'cycle': the three call flows from step to step, against the noise modes' own cycle of three"""
@@ -110,7 +160,7 @@ def problems(fam, p, n, J, dtype, which="R"):
 
 def expected_form(eng_name, s, prob):
     """The update form ``pick`` names for a step (-1: aldi_constant, whose two launches carry no form)."""
-    p, n, J, dtype = ENGINES[eng_name]
+    p, n, J, dtype = T_ENGINE if eng_name == "T" else ENGINES[eng_name]
     if s["update"] == "aldi_constant":
         return -1
     return ge.pick(p, n, J, dtype, s["update"], s["kw"]["time_step"], dense_sigma=not cr.is_diagonal(prob["sigma"]))[0]
@@ -181,10 +231,13 @@ def bound_ratio(dev, ref, B, c, eps, extra=0.0):
     return float(r.max())
 
 
-def run_sequence(eng_mod, eng, A, U0, probs, steps, flow, rec, label, forms=None, strict=True, between=None, host_noise=False):
+def run_sequence(eng_mod, eng, A, U0, probs, steps, flow, rec, label, forms=None, strict=True, between=None, host_noise=False,
+                 before_result=None):
     """Drive ``eng`` through ``steps`` (tables above) under ``flow`` ('step' | 'split' | 'sharded' | 'cycle') with checks 1-5
     after every step.  forms: the expected update form per step.  between: {i: f(eng)} run in front of step i (another stage on
-    the same engine).  host_noise: the engine-drawn blocks restated by oracle/philox.py instead of read through cesx_draw_noise.
+    the same engine).  before_result: {i: f(eng)} run after step i has been launched and before its result is read, in every
+    flow -- where ``calibrate._run_device`` has the forward map of U_new: the one place a stage call meets a deferred metric
+    finalisation.  host_noise: the engine-drawn blocks restated by oracle/philox.py instead of read through cesx_draw_noise.
     Returns [(form, warm_inverse)] per step."""
     from ces_amd.dist import ShardedUpdate
     p, n, J = eng.p, eng.n_obs, eng.J
@@ -243,6 +296,8 @@ def run_sequence(eng_mod, eng, A, U0, probs, steps, flow, rec, label, forms=None
             rec.add(label, i, "K3 drift", bound_ratio(drift, ref, B, cu, eps), strict, lab)
             rec.add(label, i, "K3 max|drift|", 0.0 if float(absmax.cpu()[0]) == np.max(np.abs(drift)) else np.inf, strict, lab)
             eng.apply_finish(prm, absmax, U, xi_t, out)
+            if before_result and i in before_result:
+                before_result[i](eng)
             res = eng.result()
             got = out.cpu().numpy().astype(np.float64)
             hk_ref = 0.1 / np.max(np.abs(drift))
@@ -263,6 +318,8 @@ def run_sequence(eng_mod, eng, A, U0, probs, steps, flow, rec, label, forms=None
             else:
                 sh.begin(prm, U, G, recenter=s["recenter"], noise_step=idx if ahead else None)
                 sh.finish(prm, U, G, xi=xi_t, out=out)
+            if before_result and i in before_result:
+                before_result[i](eng)
             res = sh.result() if fl == "sharded" else eng.result()
             got = out.cpu().numpy().astype(np.float64)
             form = eng.update_form()

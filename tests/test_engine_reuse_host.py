@@ -351,6 +351,54 @@ def test_dry_run_of_sequence_s(name, fam):
     dry(name, "S", fam, "cycle", between={rc.S_AT: lambda e: e.set_problem(other["y"], other["Gamma"], other["mu"], other["sigma"], other["ustar"])})
 
 
+@pytest.mark.parametrize("fam", cr.FAMILIES)
+@pytest.mark.parametrize("run", rc.T_RUNS, ids=[r[0].replace(" ", "-") for r in rc.T_RUNS])
+def test_dry_run_of_sequence_t(run, fam):
+    """T's Calibrate steps with the reference alone: no-op blocks, still called through both hooks, in the table's order (every
+    block in ``before_result`` of a step and then in ``between`` in front of the next); every check of every step passes."""
+    name, shape, blocks, dense = run
+    p, n, J, dtype = shape
+    A, U0, probs = rc.t_problem(fam, shape, dense)
+    assert (not cr.is_diagonal(probs[0]["Gamma"]), not cr.is_diagonal(probs[0]["sigma"])) == dense
+    between, before = rc.t_plan(blocks)
+    assert sorted(between) == list(range(1, 12)) and sorted(before) == list(range(11))
+    assert all(before[i - 1][1] == between[i][1] == blocks[(i - 1) % len(blocks)] for i in range(1, 12))
+    assert {b for _, b in between.values()} == set(blocks)
+    eng, calls = NumpyEngine(p, n, J, dtype), []
+
+    def hook(where, i, call, block):
+        def f(e):
+            assert e is eng
+            calls.append((call, where, i, block, e.steps_done))
+        return f
+    rec = rc.Record()
+    forms = forms_of(name.split()[0], rc.T_STEPS, probs)
+    rc.run_sequence(MOD, eng, A, U0, probs, rc.T_STEPS, "cycle", rec, "T %s %s" % (name, fam), forms=forms,
+                    between={i: hook("between", i, *v) for i, v in between.items()},
+                    before_result={i: hook("before_result", i, *v) for i, v in before.items()})
+    # 22 calls in the table's order; a ``before_result`` call of step i runs when the stand-in has finished i + 1 steps (the
+    # launch of step i is behind it), the ``between`` call in front of step i when it has finished i
+    assert [c[0] for c in calls] == list(range(22))
+    assert all(done == (i + 1 if where == "before_result" else i) for _, where, i, _, done in calls), calls
+    if name == "T":
+        assert set(forms) == {0, -1}
+    else:
+        assert set(forms) == ({2, 0, -1} if not dense[1] else {1, 0, -1})
+    room(rec, dtype)
+
+
+def test_the_new_hook_leaves_present_callers_alone():
+    """``before_result=None`` (the default) and an empty table record the same ratios as a call without the argument."""
+    p, n, J, dtype = rc.ENGINES["E3"]
+    A, U0, probs = rc.problems("data", p, n, J, dtype)
+    rows = []
+    for kw in ({}, dict(before_result=None), dict(before_result={})):
+        rec = rc.Record()
+        rc.run_sequence(MOD, NumpyEngine(p, n, J, dtype), A, U0, probs, rc.R_STEPS[:4], "cycle", rec, "R", **kw)
+        rows.append(rec.rows)
+    assert rows[0] == rows[1] == rows[2]
+
+
 def room(rec, dtype):
     """on fp32 the K2-from-inputs errors stay under a tenth of their bar: the bar has room before a device is involved"""
     k2 = max(r for _, _, part, r in rec.rows if part.startswith("K2 ") and part != "K2 L")
