@@ -484,6 +484,7 @@ struct Engine {
     L96State l9;                       // Lorenz '96 forward map (cesx_lorenz_*, kernels_l96.hip)
     L63State l6;                       // Lorenz '63 forward map (cesx_lorenz_three_*, kernels_l63.hip)
     MapState mp;                       // closed-form maps and their fused chain kernel (cesx_map_*, cesx_mh_run_map, kernels_maps.hip)
+    ChainSumState cs;                  // streaming summaries of the chains' draws (cesx_chain_summary_*, kernels_chainsum.hip)
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -550,6 +551,8 @@ struct Engine {
 // kernel launchers (defined in the .hip files)
 // ---------------------------------------------------------------------------
 int launch_colsum(Engine& e, const void* U, const void* G, double* sums, hipStream_t s);
+// rowsum_kernel over the `rows` rows of X alone: part[row * nslices + slice], the caller's own buffer
+int launch_rowsum(Engine& e, const void* X, int rows, int nslices, double* part, hipStream_t s);
 int launch_set_shift(Engine& e, const double* sums, hipStream_t s);
 // ---- K1: the moments launches (kernels_gram.hip, kernels_gram2.hip) ----
 // The plans of both launches of this engine (Engine::gram[.].plan), with center_u_wgs and gram_b_short; needs p, n, J, Jg, the
@@ -806,6 +809,12 @@ int launch_l63(Engine& e, const void* U, const double* W_in, void* G, double* W_
 int launch_map_apply(Engine& e, const void* U, void* G, hipStream_t s);
 int launch_mh_run_map(Engine& e, uint64_t step_index, int n_steps, int stride, void* U, void* trace, const void* xi,
                       const double* logu, hipStream_t s);
+
+// kernels_chainsum.hip: the stage behind cesx_chain_summary_* (include/cesx.h); the entry points have checked the state
+int chainsum_begin(Engine& e, long long n_draws);
+int chainsum_add(Engine& e, const void* trace, int kept, hipStream_t s);
+int chainsum_read(Engine& e, double* c, double* s1, double* cc, double* within, double* between, double* half_mean,
+                  double* half_var, hipStream_t s);
 
 // kernels_gpfit.hip: lml, gradient and status of the GPs gf.idx[0 .. n_active) at gf.theta into gf.out
 int launch_gpfit_eval(Engine& e, int n_active, hipStream_t s);

@@ -1,4 +1,4 @@
-// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gpp, gf, dc, l9, l6, mp).  Each owns its
+// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gpp, gf, dc, l9, l6, mp, cs).  Each owns its
 // device memory (DevBuf: freed with the struct), says what "nothing installed" is, and has one drop() that establishes it.
 // drop() releases the buffers whose size comes from the installed descriptor and keeps the ones sized by the engine's
 // shape alone (allocated on first use, reused by every later install).  No hip/ header: tools/devbuf_check.cpp runs these
@@ -127,6 +127,22 @@ struct MapState {
     bool none() const { return desc.kind == 0; }
     bool fused() const { return desc.kind == CESX_MAP_ELLIPTIC || desc.kind == CESX_MAP_BANANA; }   // cesx_mh_run_map has it
     void drop() { desc = cesx_map_desc{}; }
+};
+
+// ---- streaming summaries of the chains' draws (cesx_chain_summary_*, kernels_chainsum.hip); state of its own: cesx_set_problem does not touch it ----
+struct ChainSumState {
+    long long N = 0, added = 0;        // draws of the run in hand (0: no cesx_chain_summary_begin), draws added so far
+    int slabs = 0;                     // column slabs of the pooled launch (kernels_chainsum.hip, cs_slab_cols): the rows of `part`
+    DevBuf<double> shift;              // [p][J] every chain's first draw: the shift of its half sums
+    DevBuf<double> S;                  // [2 halves][2: S1, S2][p][J] sum (x - shift), sum (x - shift)^2
+    DevBuf<double> c;                  // [p] the pooled shift: the row mean of the first draw
+    DevBuf<double> cpart;              // [p][slices] the row sums behind c
+    DevBuf<double> tot;                // [p][p] sum (x - c)(x - c)^T, lower triangle, then [p] sum (x - c): the run's totals
+    DevBuf<double> part;               // [slabs][pairs][64][64] a launch's cross moments per slab, then [slabs][pp] its row sums
+    DevBuf<double> hpart;              // [p][blocks][3] the half-chain reduce's partials, then [p][3] sum (m - c), sum (m - c)^2, sum s^2
+    DevBuf<double> half;               // [2: m, s^2][2 halves][p][J], only while a cesx_chain_summary_read that asks for them runs
+    bool none() const { return N == 0; }
+    void drop() { N = 0; added = 0; half.reset(); }       // every other buffer is sized by the engine: kept
 };
 
 }  // namespace cesx

@@ -1736,4 +1736,38 @@ int cesx_mh_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride,
     return CESX_OK;
 }
 
+// ---- Streaming summaries of the chains' draws (MCMC(..., chains=M, summary=True); kernels_chainsum.hip) ----
+
+int cesx_chain_summary_begin(cesx_handle h, int n_draws, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    (void)stream;                                         // nothing is launched: the first add overwrites the stage's sums
+    if (n_draws < 4) { e.err = "cesx_chain_summary_begin: n_draws must be >= 4 (two half-chains of two draws)"; return CESX_EINVAL; }
+    if (e.J != e.Jg) { e.err = "cesx_chain_summary_begin: sharded chains (J_local != J_global) are not summarised"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    return chainsum_begin(e, n_draws);
+}
+
+int cesx_chain_summary_add(cesx_handle h, const void* trace, int kept, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!trace) { e.err = "cesx_chain_summary_add: null pointer"; return CESX_EINVAL; }
+    if (kept < 1) { e.err = "cesx_chain_summary_add: kept must be >= 1"; return CESX_EINVAL; }
+    if (e.cs.none()) { e.err = "cesx_chain_summary_add: cesx_chain_summary_begin has not been called"; return CESX_ESTATE; }
+    if (e.cs.added + kept > e.cs.N) { e.err = "cesx_chain_summary_add: more draws than cesx_chain_summary_begin announced"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    return chainsum_add(e, trace, kept, (hipStream_t)stream);
+}
+
+int cesx_chain_summary_read(cesx_handle h, double* c, double* s1, double* cc, double* within, double* between, double* half_mean,
+                            double* half_var, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!c || !s1 || !cc || !within || !between) { e.err = "cesx_chain_summary_read: null pointer"; return CESX_EINVAL; }
+    if (e.cs.none()) { e.err = "cesx_chain_summary_read: cesx_chain_summary_begin has not been called"; return CESX_ESTATE; }
+    if (e.cs.added != e.cs.N) { e.err = "cesx_chain_summary_read: fewer draws were added than cesx_chain_summary_begin announced"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    return chainsum_read(e, c, s1, cc, within, between, half_mean, half_var, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -98,6 +98,18 @@ int launch_colsum(Engine& e, const void* U, const void* G, double* sums, hipStre
     return e.cfg.dtype == CESX_F32 ? colsum_t<float>(e, U, G, sums, s) : colsum_t<double>(e, U, G, sums, s);
 }
 
+// part[row * nslices + slice] of the `rows` rows of X alone (rows x J, engine dtype), into the caller's own partials
+int launch_rowsum(Engine& e, const void* X, int rows, int nslices, double* part, hipStream_t s) {
+    if (e.cfg.dtype == CESX_F32)
+        hipLaunchKernelGGL(rowsum_kernel<float>, dim3(nslices, rows), dim3(ST_THREADS), 0, s, (const float*)X, (const float*)X, rows, 0,
+                           (long long)e.J, nslices, part);
+    else
+        hipLaunchKernelGGL(rowsum_kernel<double>, dim3(nslices, rows), dim3(ST_THREADS), 0, s, (const double*)X, (const double*)X, rows, 0,
+                           (long long)e.J, nslices, part);
+    CESX_HIP(hipGetLastError());
+    return CESX_OK;
+}
+
 int launch_set_shift(Engine& e, const double* sums, hipStream_t s) {
     const int P = e.p + e.n;
     if (e.whiten) {

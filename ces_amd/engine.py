@@ -18,7 +18,7 @@ OK, EINVAL, ENOTPD, EHIP, ESTATE, EUNSUPPORTED, ENOCONV = 0, 1, 2, 3, 4, 5, 6
 F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
-ABI_VERSION = 7
+ABI_VERSION = 8
 MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
@@ -34,7 +34,8 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_run", "cesx_gp_dense_set", "cesx_gp_proj_set",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_darcy_set_streamed", "cesx_darcy_workspace_bytes", "cesx_lorenz_set", "cesx_lorenz_apply",
-           "cesx_lorenz_three_set", "cesx_lorenz_three_apply", "cesx_map_set", "cesx_map_apply", "cesx_mh_run_map")
+           "cesx_lorenz_three_set", "cesx_lorenz_three_apply", "cesx_map_set", "cesx_map_apply", "cesx_mh_run_map",
+           "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
               2: "a state or an error norm was not finite",
               3: "max_attempts steps were attempted"}
@@ -286,6 +287,9 @@ def load_library(path=None):
     lib.cesx_map_set.argtypes = [vp, C.POINTER(MapDesc)]
     lib.cesx_map_apply.argtypes = [vp, vp, vp, vp]
     lib.cesx_mh_run_map.argtypes = [vp, u64, i32, i32, vp, vp, vp, vp, vp]
+    lib.cesx_chain_summary_begin.argtypes = [vp, i32, vp]
+    lib.cesx_chain_summary_add.argtypes = [vp, vp, i32, vp]
+    lib.cesx_chain_summary_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if lib.cesx_abi_version() != ABI_VERSION:
         raise ImportError("libcesx.so ABI %d != binding ABI %d" % (lib.cesx_abi_version(), ABI_VERSION))
     if path == LIB_PATH:
@@ -1268,6 +1272,40 @@ class Engine:
                                                  None if xi is None else xi.data_ptr(),
                                                  None if logu is None else logu.data_ptr(), self._stream()))
         self._keep_mh_run = (U, trace, xi, logu)
+
+    # -- streaming summaries of the chains' draws (include/cesx.h, cesx_chain_summary_*) --
+    def chain_summary_begin(self, n_draws):
+        """Clear the stage for a run of ``n_draws`` draws per chain (cesx_chain_summary_begin); ValueError below 4."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_chain_summary_begin(self._h, int(n_draws), self._stream()))
+
+    def chain_summary_add(self, trace):
+        """Add the draws of ``trace``, (kept, p, J) or one state (p, J), engine dtype, in order (cesx_chain_summary_add).
+        Nothing is copied: the kernels read ``trace`` on the current stream."""
+        shape = tuple(trace.shape)
+        if (trace.dtype != self.torch_dtype or not trace.is_cuda or not trace.is_contiguous()
+                or shape[-2:] != (self.p, self.J) or len(shape) not in (2, 3)):
+            raise ValueError("chain_summary_add: trace must be a contiguous %s tensor of shape (kept, %d, %d) or (%d, %d)"
+                             % (self.torch_dtype, self.p, self.J, self.p, self.J))
+        kept = shape[0] if len(shape) == 3 else 1
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_chain_summary_add(self._h, trace.data_ptr(), kept, self._stream()))
+        self._keep_chain_summary = trace
+
+    def chain_summary_read(self, halves=False):
+        """The run's raw sums as host fp64 arrays (cesx_chain_summary_read): ``c`` (p,), ``s1`` (p,), ``cc`` (p, p) lower
+        triangle, ``within`` (p,), ``between`` (p,); with ``halves`` also ``half_mean`` and ``half_var`` (2, p, J)."""
+        p, J = self.p, self.J
+        out = dict(c=np.empty(p), s1=np.empty(p), cc=np.empty((p, p)), within=np.empty(p), between=np.empty(p))
+        if halves:
+            out.update(half_mean=np.empty((2, p, J)), half_var=np.empty((2, p, J)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_chain_summary_read(self._h, out["c"].ctypes.data, out["s1"].ctypes.data, out["cc"].ctypes.data,
+                                                         out["within"].ctypes.data, out["between"].ctypes.data,
+                                                         out["half_mean"].ctypes.data if halves else None,
+                                                         out["half_var"].ctypes.data if halves else None, self._stream()))
+        self._keep_chain_summary = None
+        return out
 
     def profile_enable(self, on=True):
         """on: False / True, 2 = bind only the events cesx_profile_gap needs, 3 / 4 = the update / the moments

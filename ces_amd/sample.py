@@ -43,6 +43,18 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          raises ``ValueError``, and so does an emulator whose tile does not fit in LDS.  A launch runs at
                          most ``GP_FUSED_WORK`` of arithmetic.  ``self.fused_launches`` counts the fused launches of the last
                          call of either sampler (0: the step path).
+  kwarg ``summary``      with ``chains=``: ``True`` sums the kept states on the device instead of copying them to the host
+                         (``cesx_chain_summary_*``, kernels_chainsum.hip).  The draws are the states the trace would hold
+                         but the start state -- after the call's steps s with ``s % trace_stride == 0`` -- that have
+                         ``s > burn`` (kwarg ``burn``, steps, default 0; ``burn=`` without ``summary=True`` and fewer than 4
+                         draws raise ``ValueError``).  ``self.summary`` is a dict of host fp64 values: ``n`` draws per chain
+                         and ``chains``; ``mean`` (p,) and ``cov`` (p, p) pooled over all draws of all chains (ddof = 1);
+                         ``within`` = W and ``between`` = B_m (p,), the mean variance and the variance of the means
+                         (ddof = 1) of the 2 M half-chains (each chain's first and last n // 2 draws); ``rhat`` =
+                         sqrt(((n_h - 1) / n_h W + B_m) / W) and ``ess`` = min(2 M n_h, 2 M var+ / B_m) with n_h = n // 2
+                         (no rank normalisation, no autocorrelations).  The chains run exactly as without it;
+                         ``self.samples`` gains only the start state (a fresh run) and the call's last state, so a resume
+                         works, and a resumed call summarises its own steps.
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -76,6 +88,46 @@ def fused_chunks(n_mcmc, stride, steps_max, buffer_bytes, bytes_per_step, work_m
     cap = max(1, cap)
     K_max = max(stride, cap // stride * stride)
     return K_max, [min(K_max, n_mcmc - k0) for k0 in range(0, n_mcmc, K_max)]
+
+
+def _host_has_no_summary(kwargs):
+    """``summary=`` and ``burn=`` belong to the device paths of ``chains=M``."""
+    for name in ("summary", "burn"):
+        if kwargs.get(name, None) is not None:
+            raise ValueError("%s=%r summarises the chains of chains=M on the device; the host path keeps every state in "
+                             "self.samples" % (name, kwargs.get(name)))
+
+
+def summary_draws(n_mcmc, stride, burn):
+    """How many states of a call of ``n_mcmc`` steps ``summary=True`` summarises: the states after the steps s = 1 .. n_mcmc
+    of the call with ``s % stride == 0`` (the ones the trace would hold; not the start state, not an off-stride last
+    state) and ``s > burn``."""
+    n_mcmc, stride, burn = int(n_mcmc), max(1, int(stride)), int(burn)
+    return max(0, n_mcmc // stride - min(burn, n_mcmc) // stride)
+
+
+def finalise_summary(raw, n_draws, chains):
+    """The ``MCMC.summary`` dict from the raw sums of ``Engine.chain_summary_read`` (host numpy on p-sized arrays).
+
+    ``raw``: ``c`` (p,) the pooled shift, ``s1`` (p,) = sum (x - c) and ``cc`` (p, p) = the lower triangle of
+    sum (x - c)(x - c)^T over all N M draws, ``within`` = W and ``between`` = B_m of the 2 M half-chains of n = N // 2 draws.
+    mean and cov pool all draws (ddof = 1); var+ = (n - 1) / n W + B_m, rhat = sqrt(var+ / W) and
+    ess = min(2 M n, 2 M var+ / B_m): the split statistics without rank normalisation, and an effective sample size from
+    the between-half-chain variance, not from autocorrelations."""
+    N, M = int(n_draws), int(chains)
+    c = np.asarray(raw["c"], dtype=np.float64)
+    s1 = np.asarray(raw["s1"], dtype=np.float64)
+    cc = np.tril(np.asarray(raw["cc"], dtype=np.float64))
+    cc = cc + np.tril(cc, -1).T
+    W = np.asarray(raw["within"], dtype=np.float64)
+    B = np.asarray(raw["between"], dtype=np.float64)
+    T, n = N * M, N // 2
+    d = s1 / T
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var_plus = (n - 1) / n * W + B
+        rhat = np.sqrt(var_plus / W)
+        ess = np.minimum(2.0 * M * n, 2.0 * M * var_plus / B)
+    return dict(n=N, chains=M, mean=c + d, cov=(cc - T * np.outer(d, d)) / (T - 1), rhat=rhat, ess=ess, within=W, between=B)
 
 
 class MCMC(object):
@@ -132,6 +184,7 @@ class MCMC(object):
         if kwargs.get("sigma_form", None) is not None:
             raise ValueError("sigma_form=%r chooses between the device kernels of chains=M; the host path has one form"
                              % (kwargs.get("sigma_form"),))
+        _host_has_no_summary(kwargs)
         from . import emulate
         if enka_scaling:
             scales = delta * np.linalg.cholesky(np.cov(enka.Ustar))
@@ -211,6 +264,7 @@ class MCMC(object):
             return self._model_mh_device(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, kwargs)
         if kwargs.get("fused", None) is not None:
             raise ValueError("fused=%r chooses between the device paths of chains=M; the host path has one" % (kwargs.get("fused"),))
+        _host_has_no_summary(kwargs)
         # RW needs the proposal distribution (:122-126)
         if enka_scaling:
             scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(enka.p, enka.p))
@@ -305,6 +359,9 @@ class MCMC(object):
         fused_work               the arithmetic of one fused step of all chains, in the units of ``GP_FUSED_WORK`` (0: a launch
                                  is capped by ``FUSED_STEPS_MAX`` and ``FUSED_BUFFER_BYTES`` alone)
         ``self.fused_launches`` is the number of fused launches of the call, 0 on the step path.
+        ``kwargs['summary'] = True`` (with ``kwargs['burn']`` steps left out) keeps the kept states on the device and sums
+        them there (``eng.chain_summary_*``): ``self.summary`` (``finalise_summary``) instead of a trace in ``self.samples``,
+        which gains the start state of a fresh run and the call's last state only.  The chains run as without it.
         """
         import torch
         M = kwargs["chains"]
@@ -318,6 +375,23 @@ class MCMC(object):
             raise ValueError("chains=: unknown update %r (None or 'pCN')" % (update,))
         if self.noise not in ("numpy", "device"):
             raise ValueError("noise must be 'numpy' or 'device', got %r" % (self.noise,))
+        stride = max(1, int(self.trace_stride))
+        summary, burn = kwargs.get("summary", None), kwargs.get("burn", None)
+        if summary not in (None, False, True):
+            raise ValueError("summary must be None, False or True, got %r" % (summary,))
+        summary = bool(summary)
+        if burn is not None and not summary:
+            raise ValueError("burn=%r counts the steps summary=True leaves out; without summary=True every kept state is in "
+                             "self.samples" % (burn,))
+        if summary:
+            burn = 0 if burn is None else burn
+            if isinstance(burn, bool) or not isinstance(burn, (int, np.integer)) or burn < 0:
+                raise ValueError("burn must be an integer >= 0 (steps), got %r" % (burn,))
+            burn = int(burn)
+            n_draws = summary_draws(n_mcmc, stride, burn)
+            if n_draws < 4:
+                raise ValueError("summary=True: %d steps at trace_stride %d with burn=%d leave %d draws per chain; the split "
+                                 "statistics need 4 (two half-chains of two)" % (n_mcmc, stride, burn, n_draws))
         p, n = enka.p, enka.n_obs
         scales = scales_of(update)
         start = kwargs.get("start", "mean")
@@ -329,7 +403,6 @@ class MCMC(object):
             U0 = np.array(enka.Ustar[:, :M], dtype=np.float64)
         else:
             raise ValueError("start must be 'mean' or 'ensemble', got %r" % (start,))
-        stride = max(1, int(self.trace_stride))
         mu = np.asarray(prior.mean, dtype=np.float64).reshape(p)
         cov = np.asarray(prior.cov, dtype=np.float64).reshape(p, p)
 
@@ -354,6 +427,8 @@ class MCMC(object):
             if not resume_keeps_start_phi or self.noise == "device":
                 score_start(U)
             base, kept = int(getattr(self, "_mh_next_step", 0)), []
+        if summary:                                       # the draws stay on the device: cesx_chain_summary_*
+            eng.chain_summary_begin(n_draws)
 
         if fused:
             # launches of at most K_max steps (cesx_mh_run_map / cesx_gp_run; fused_chunks): K_max a multiple of the stride --
@@ -378,9 +453,13 @@ class MCMC(object):
                 tr = trace[:K // stride]
                 run_steps(base + k0, K, U, stride, tr, xi_t, logu_t)
                 self.fused_launches += 1
-                if K // stride:
+                if summary:                               # the launch's states after the steps s = k0 + stride (t + 1) > burn
+                    t0 = max(0, burn // stride - k0 // stride)
+                    if t0 < K // stride:
+                        eng.chain_summary_add(tr[t0:])
+                elif K // stride:
                     kept.extend(tr.cpu().numpy().astype(np.float64))
-            if n_mcmc % stride and n_mcmc > 0:            # the run's last state, where the stride does not land on it
+            if (summary or n_mcmc % stride) and n_mcmc > 0:   # the run's last state, where the trace does not hold it
                 kept.append(eng.to_host(U))
         else:
             for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
@@ -393,8 +472,15 @@ class MCMC(object):
                     logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
                 eng.mh_propose(step, U, xi=xi_t, out=P)
                 score_accept(step, U, P, logu_t)
-                if (k + 1) % stride == 0 or k + 1 == n_mcmc:
+                if summary:
+                    if (k + 1) % stride == 0 and k + 1 > burn:
+                        eng.chain_summary_add(U)
+                    if k + 1 == n_mcmc:
+                        kept.append(eng.to_host(U))
+                elif (k + 1) % stride == 0 or k + 1 == n_mcmc:
                     kept.append(eng.to_host(U))
+        if summary:
+            self.summary = finalise_summary(eng.chain_summary_read(), n_draws, M)
         steps, rate, per = eng.mh_stats(per_chain=True)
 
         new = np.stack(kept, axis=1) if kept else np.zeros((p, 0, M))      # (p, n_new, M)

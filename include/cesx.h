@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CESX_ABI_VERSION 7
+#define CESX_ABI_VERSION 8
 
 /* status codes */
 #define CESX_OK            0
@@ -576,6 +576,35 @@ int cesx_map_apply(cesx_handle h, const void* U_dev, void* G_dev, void* stream);
    for n_steps < 1, stride < 1 or a step index >= 2^31.  Neither launches anything. */
 int cesx_mh_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride, void* U_dev, void* trace_dev,
                     const void* xi_dev, const double* logu_dev, void* stream);
+
+/* ---- Streaming summaries of the chains' draws (MCMC(..., chains=M, summary=True); kernels_chainsum.hip) --
+   The sums behind the pooled mean and covariance, the split R-hat and an effective sample size of a run of
+   M = J_local chains, taken from the draws while they are in device memory: no draw crosses to the host.  A run
+   announces its N draws, adds them in order in any chunking, and reads the sums once.  With n = N / 2 (rounded down),
+   a chain's two half-chains are its first n and its last n draws (the middle draw of an odd N belongs to neither):
+       per (row, chain, half)   S1 = sum (x - shift), S2 = sum (x - shift)^2, shift = the chain's first draw;
+                                m = shift + S1 / n, s^2 = (S2 - S1^2 / n) / (n - 1)
+       per row                  W = mean(s^2) and B_m = var(m, ddof = 1) over the 2 M half-chains
+       pooled                   c = the row means of the first draw, sum (x - c) and sum (x - c)(x - c)^T over all N M draws
+   All sums are fp64 (an fp32 draw converts exactly), run in a fixed order and use no atomics: a run is bit-reproducible,
+   and the per-chain sums do not depend on the chunking.
+   The stage keeps state of its own, sized by the engine's shape alone, allocated by the first begin and kept until
+   cesx_destroy; cesx_set_problem does not touch it.  Its size: the half sums 2 halves x (S1, S2) x p x J_local x 8 bytes
+   and the per-chain shift p x J_local x 8 bytes -- 537 MB and 134 MB at p = 256, J_local = 65 536 --, and the pooled
+   launch's slab partials, 32 KiB per workgroup of a launch of about 1 024 (34 MB there). */
+/* Clears the stage and fixes N = n_draws, and with it the half boundaries.  CESX_EINVAL for n_draws < 4 or a sharded
+   handle (J_local != J_global).  Launches nothing. */
+int cesx_chain_summary_begin(cesx_handle h, int n_draws, void* stream);
+/* Adds `kept` draws laid out [kept][p][J_local] in the engine dtype: a launch's trace_dev (cesx_mh_run_map, cesx_gp_run), or
+   U_dev itself with kept = 1.  Reads the draws and writes only the stage's own memory.  CESX_ESTATE without a begin or
+   past N draws, CESX_EINVAL for a null pointer or kept < 1; neither launches anything. */
+int cesx_chain_summary_add(cesx_handle h, const void* trace_dev, int kept, void* stream);
+/* HOST outputs; synchronises `stream`.  c (p), s1 = sum (x - c) (p), cc = sum (x - c)(x - c)^T (p x p row-major, the lower
+   triangle; zero above), within = W (p), between = B_m (p); optional (NULL allowed) half_mean and half_var
+   ([2 halves][p][J_local] each): m and s^2 of every half-chain.  CESX_ESTATE unless exactly N draws were added (nothing
+   is launched then); the stage stays readable until the next begin. */
+int cesx_chain_summary_read(cesx_handle h, double* c, double* s1, double* cc, double* within, double* between,
+                            double* half_mean, double* half_var, void* stream);
 
 /* ---- Emulate: GP prediction and the GP sampler over the columns (ces/emulate.py, ces/sample.py:17-119) --
    One exact GP per output, trained on the host (ces_amd/emulate.py); the engine holds its own fp64 image of them and
