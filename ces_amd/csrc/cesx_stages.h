@@ -1,4 +1,4 @@
-// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gpp, gf, dc, l9, l6, mp, cs).  Each owns its
+// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gpp, gf, dc, l9, l6, mp, cs, ch).  Each owns its
 // device memory (DevBuf: freed with the struct), says what "nothing installed" is, and has one drop() that establishes it.
 // drop() releases the buffers whose size comes from the installed descriptor and keeps the ones sized by the engine's
 // shape alone (allocated on first use, reused by every later install).  No hip/ header: tools/devbuf_check.cpp runs these
@@ -143,6 +143,20 @@ struct ChainSumState {
     DevBuf<double> half;               // [2: m, s^2][2 halves][p][J], only while a cesx_chain_summary_read that asks for them runs
     bool none() const { return N == 0; }
     void drop() { N = 0; added = 0; half.reset(); }       // every other buffer is sized by the engine: kept
+};
+
+// ---- streaming 1-D and 2-D marginals of the chains' draws (cesx_chain_hist_*, kernels_chainhist.hip); state of its own: cesx_set_problem does not touch it ----
+struct ChainHistState {
+    int bins = 0, bins2 = 0, n_pairs = 0;      // of the run in hand (bins 0: no cesx_chain_hist_begin)
+    long long added = 0;                       // draws added so far
+    // every buffer is sized by the engine's p and the caps of include/cesx.h (CESX_CHAIN_HIST_*_MAX): allocated by the first begin
+    DevBuf<double> edges1;                     // [p][bins + 1]
+    DevBuf<double> edges2;                     // [n_pairs][2][bins2 + 1] the edges of each pair's first and second row
+    DevBuf<int> pairs;                         // [n_pairs][2]
+    DevBuf<unsigned long long> tot1;           // [p][bins + 2] the run's counts: the bins, below, above
+    DevBuf<unsigned long long> tot2;           // [n_pairs][bins2][bins2], then [n_pairs] outside
+    bool none() const { return bins == 0; }
+    void drop() { bins = 0; bins2 = 0; n_pairs = 0; added = 0; }      // every buffer is sized by the engine: kept
 };
 
 }  // namespace cesx

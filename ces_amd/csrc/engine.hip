@@ -1770,4 +1770,64 @@ int cesx_chain_summary_read(cesx_handle h, double* c, double* s1, double* cc, do
     return chainsum_read(e, c, s1, cc, within, between, half_mean, half_var, (hipStream_t)stream);
 }
 
+// ---- Streaming marginals of the chains' draws (MCMC(..., chains=M, summary=True, marginals=...); kernels_chainhist.hip) ----
+
+// finite and strictly increasing
+static bool hist_edges_ok(const double* e, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(e[i]) || (i > 0 && !(e[i] > e[i - 1]))) return false;
+    return true;
+}
+
+// Failure rule: a refused begin touches nothing; the run in hand goes on.
+int cesx_chain_hist_begin(cesx_handle h, const cesx_chain_hist_desc* d, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!d || d->struct_bytes != (uint32_t)sizeof(cesx_chain_hist_desc)) { e.err = "cesx_chain_hist_begin: bad cesx_chain_hist_desc"; return CESX_EINVAL; }
+    if (e.J != e.Jg) { e.err = "cesx_chain_hist_begin: sharded chains (J_local != J_global) are not counted"; return CESX_EINVAL; }
+    if (d->bins < 2 || d->bins > CESX_CHAIN_HIST_BINS_MAX) { e.err = "cesx_chain_hist_begin: bins must be in [2, 256]"; return CESX_EINVAL; }
+    if (d->bins2d < 2 || d->bins2d > CESX_CHAIN_HIST_BINS2D_MAX) { e.err = "cesx_chain_hist_begin: bins2d must be in [2, 64]"; return CESX_EINVAL; }
+    if (d->n_pairs < 0 || d->n_pairs > CESX_CHAIN_HIST_PAIRS_MAX) { e.err = "cesx_chain_hist_begin: n_pairs must be in [0, 64]"; return CESX_EINVAL; }
+    if (!d->edges1 || (d->n_pairs > 0 && (!d->edges2 || !d->pairs))) { e.err = "cesx_chain_hist_begin: null pointer"; return CESX_EINVAL; }
+    for (int r = 0; r < e.p; ++r)
+        if (!hist_edges_ok(d->edges1 + (size_t)r * (d->bins + 1), d->bins + 1)) {
+            e.err = "cesx_chain_hist_begin: edges1 of row " + std::to_string(r) + " are not finite and strictly increasing";
+            return CESX_EINVAL;
+        }
+    for (int k = 0; k < d->n_pairs; ++k) {
+        const int i = d->pairs[2 * k], j = d->pairs[2 * k + 1];
+        if (i < 0 || i >= e.p || j < 0 || j >= e.p || i == j) {
+            e.err = "cesx_chain_hist_begin: pair " + std::to_string(k) + " must name two different rows in [0, p)";
+            return CESX_EINVAL;
+        }
+        for (const int r : {i, j})
+            if (!hist_edges_ok(d->edges2 + (size_t)r * (d->bins2d + 1), d->bins2d + 1)) {
+                e.err = "cesx_chain_hist_begin: edges2 of row " + std::to_string(r) + " are not finite and strictly increasing";
+                return CESX_EINVAL;
+            }
+    }
+    SET_DEVICE(e);
+    return chainhist_begin(e, d, (hipStream_t)stream);
+}
+
+int cesx_chain_hist_add(cesx_handle h, const void* trace, int kept, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!trace) { e.err = "cesx_chain_hist_add: null pointer"; return CESX_EINVAL; }
+    if (kept < 1) { e.err = "cesx_chain_hist_add: kept must be >= 1"; return CESX_EINVAL; }
+    if (e.ch.none()) { e.err = "cesx_chain_hist_add: cesx_chain_hist_begin has not been called"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    return chainhist_add(e, trace, kept, (hipStream_t)stream);
+}
+
+int cesx_chain_hist_read(cesx_handle h, unsigned long long* hist1, unsigned long long* out1, unsigned long long* hist2,
+                         unsigned long long* out2, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (e.ch.none()) { e.err = "cesx_chain_hist_read: cesx_chain_hist_begin has not been called"; return CESX_ESTATE; }
+    if (!hist1 || !out1 || (e.ch.n_pairs > 0 && (!hist2 || !out2))) { e.err = "cesx_chain_hist_read: null pointer"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    return chainhist_read(e, hist1, out1, hist2, out2, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -18,7 +18,7 @@ OK, EINVAL, ENOTPD, EHIP, ESTATE, EUNSUPPORTED, ENOCONV = 0, 1, 2, 3, 4, 5, 6
 F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
-ABI_VERSION = 8
+ABI_VERSION = 9
 MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
@@ -35,7 +35,8 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_darcy_set_streamed", "cesx_darcy_workspace_bytes", "cesx_lorenz_set", "cesx_lorenz_apply",
            "cesx_lorenz_three_set", "cesx_lorenz_three_apply", "cesx_map_set", "cesx_map_apply", "cesx_mh_run_map",
-           "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read")
+           "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read",
+           "cesx_chain_hist_begin", "cesx_chain_hist_add", "cesx_chain_hist_read")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
               2: "a state or an error norm was not finite",
               3: "max_attempts steps were attempted"}
@@ -147,6 +148,11 @@ def l63_desc_struct(desc):
 
 class MapDesc(C.Structure):
     _fields_ = [("struct_bytes", C.c_int), ("kind", C.c_int), ("prm", C.c_double * 8)]
+
+
+class ChainHistDesc(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("bins", C.c_int32), ("bins2d", C.c_int32), ("n_pairs", C.c_int32),
+                ("edges1", C.c_void_p), ("edges2", C.c_void_p), ("pairs", C.c_void_p)]
 
 
 class CesxError(RuntimeError):
@@ -290,6 +296,9 @@ def load_library(path=None):
     lib.cesx_chain_summary_begin.argtypes = [vp, i32, vp]
     lib.cesx_chain_summary_add.argtypes = [vp, vp, i32, vp]
     lib.cesx_chain_summary_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cesx_chain_hist_begin.argtypes = [vp, vp, vp]
+    lib.cesx_chain_hist_add.argtypes = [vp, vp, i32, vp]
+    lib.cesx_chain_hist_read.argtypes = [vp, vp, vp, vp, vp, vp]
     if lib.cesx_abi_version() != ABI_VERSION:
         raise ImportError("libcesx.so ABI %d != binding ABI %d" % (lib.cesx_abi_version(), ABI_VERSION))
     if path == LIB_PATH:
@@ -350,6 +359,8 @@ class Engine:
         if rc != OK:
             raise CesxError(rc, self.lib.cesx_last_error(None).decode())
         self._problem = None
+        self._chain_hist_shape = None      # (bins, bins2d, pairs) of the run of histograms in hand
+        self._keep_chain_hist = None
 
     def close(self):
         """Destroy the handle and free its device memory now (what garbage collection would do later)."""
@@ -1306,6 +1317,66 @@ class Engine:
                                                          out["half_var"].ctypes.data if halves else None, self._stream()))
         self._keep_chain_summary = None
         return out
+
+    # -- streaming marginals of the chains' draws (include/cesx.h, cesx_chain_hist_*) --
+    def chain_hist_begin(self, edges1, edges2=None, pairs=None):
+        """Start a run of histograms (cesx_chain_hist_begin): ``edges1`` (p, bins + 1) the 1-D edges of every row,
+        ``edges2`` (p, bins2d + 1) the 2-D edges (only the rows named in ``pairs`` are read) and ``pairs`` (P, 2) rows
+        (i, j), host fp64 / int.  ValueError for a limit of include/cesx.h; the run in hand then goes on."""
+        e1 = np.ascontiguousarray(np.asarray(edges1, dtype=np.float64))
+        if e1.ndim != 2 or e1.shape[0] != self.p:
+            raise ValueError("chain_hist_begin: edges1 must have shape (%d, bins + 1), got %s" % (self.p, e1.shape))
+        pr = np.zeros((0, 2), dtype=np.int32) if pairs is None else np.asarray(pairs)
+        if pr.size == 0:
+            pr = pr.reshape(0, 2)
+        if pr.ndim != 2 or pr.shape[1] != 2 or (pr.size and not np.issubdtype(pr.dtype, np.integer)):
+            raise ValueError("chain_hist_begin: pairs must be (P, 2) integers, got %s %s" % (pr.dtype, pr.shape))
+        pr = np.ascontiguousarray(pr, dtype=np.int32)
+        if edges2 is None:
+            if len(pr):
+                raise ValueError("chain_hist_begin: pairs need edges2")
+            e2 = np.zeros((self.p, 3))
+            e2[:, 1:] = (1.0, 2.0)
+        else:
+            e2 = np.ascontiguousarray(np.asarray(edges2, dtype=np.float64))
+        if e2.ndim != 2 or e2.shape[0] != self.p:
+            raise ValueError("chain_hist_begin: edges2 must have shape (%d, bins2d + 1), got %s" % (self.p, e2.shape))
+        d = ChainHistDesc()
+        d.struct_bytes = C.sizeof(ChainHistDesc)
+        d.bins, d.bins2d, d.n_pairs = e1.shape[1] - 1, e2.shape[1] - 1, len(pr)
+        d.edges1, d.edges2, d.pairs = e1.ctypes.data, e2.ctypes.data, pr.ctypes.data if len(pr) else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_chain_hist_begin(self._h, C.byref(d), self._stream()))
+        self._chain_hist_shape = (d.bins, d.bins2d, len(pr))
+
+    def chain_hist_add(self, trace):
+        """Count the draws of ``trace``, (kept, p, J) or one state (p, J), engine dtype (cesx_chain_hist_add): the argument
+        of ``chain_summary_add``.  Nothing is copied: the kernels read ``trace`` on the current stream."""
+        shape = tuple(trace.shape)
+        if (trace.dtype != self.torch_dtype or not trace.is_cuda or not trace.is_contiguous()
+                or shape[-2:] != (self.p, self.J) or len(shape) not in (2, 3)):
+            raise ValueError("chain_hist_add: trace must be a contiguous %s tensor of shape (kept, %d, %d) or (%d, %d)"
+                             % (self.torch_dtype, self.p, self.J, self.p, self.J))
+        kept = shape[0] if len(shape) == 3 else 1
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_chain_hist_add(self._h, trace.data_ptr(), kept, self._stream()))
+        self._keep_chain_hist = trace
+
+    def chain_hist_read(self):
+        """The run's counts so far as host int64 arrays (cesx_chain_hist_read): ``hist1d`` (p, bins), ``below`` and ``above``
+        (p,), ``hist2d`` (P, bins2d, bins2d) -- row the bin of a pair's first parameter, column that of its second -- and
+        ``outside2d`` (P,).  Synchronises; the run goes on."""
+        if self._chain_hist_shape is None:
+            raise CesxError(ESTATE, "chain_hist_read: chain_hist_begin has not been called")
+        B, B2, P = self._chain_hist_shape
+        h1, o1 = np.zeros((self.p, B), dtype=np.uint64), np.zeros((self.p, 2), dtype=np.uint64)
+        h2, o2 = np.zeros((P, B2, B2), dtype=np.uint64), np.zeros(P, dtype=np.uint64)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_chain_hist_read(self._h, h1.ctypes.data, o1.ctypes.data, h2.ctypes.data if P else None,
+                                                      o2.ctypes.data if P else None, self._stream()))
+        self._keep_chain_hist = None
+        return dict(hist1d=h1.astype(np.int64), below=o1[:, 0].astype(np.int64), above=o1[:, 1].astype(np.int64),
+                    hist2d=h2.astype(np.int64), outside2d=o2.astype(np.int64))
 
     def profile_enable(self, on=True):
         """on: False / True, 2 = bind only the events cesx_profile_gap needs, 3 / 4 = the update / the moments

@@ -55,6 +55,21 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          (no rank normalisation, no autocorrelations).  The chains run exactly as without it;
                          ``self.samples`` gains only the start state (a fresh run) and the call's last state, so a resume
                          works, and a resumed call summarises its own steps.
+  kwarg ``marginals``    with ``chains=`` and ``summary=True`` (``ValueError`` without): histograms of every parameter and of
+                         chosen parameter pairs over exactly the draws the summary sums, counted on the device
+                         (``cesx_chain_hist_*``, kernels_chainhist.hip).  ``None`` / ``False``: off; ``True``: the defaults; or a
+                         dict with ``bins`` (64, 2 .. 256), ``bins2d`` (20 -- ``plots.find_levels``'s --, 2 .. 64), ``pairs``
+                         (``None``, a list of (i, j), or 'all': every i < j, at most 64), ``range`` ((p, 2) rows [lo, hi]) and
+                         ``width`` (6.0: without ``range``, row r spans mean_r -+ width std_r of ``enka.Ustar``, ddof = 1; a
+                         zero spread raises ``ValueError``; with ``range``, ``width`` is not read); an unknown key raises ``ValueError``.  Edges are
+                         ``np.linspace(lo, hi, bins + 1)``; the bin rule is ``numpy.histogram``'s, in fp64, and the counts
+                         equal numpy's on the same draws bit for bit.  ``self.marginals`` is a dict of host arrays: ``n``,
+                         ``chains``, ``edges`` (p, bins + 1), ``hist1d`` (p, bins) int64, ``below`` and ``above`` (p,) (draws
+                         left of the range; right of it, and NaN), ``pairs`` (P, 2), ``edges2d`` (p, bins2d + 1), ``hist2d``
+                         (P, bins2d, bins2d) int64 (row: the bin of the pair's first parameter) and ``outside2d`` (P,).
+                         ``marginal_density`` and ``marginal_quantiles`` read it; ``plots.find_levels(H=hist2d[k])`` gives
+                         the contour levels.  The chains, ``self.summary`` and ``self.samples`` are as without it.  A call
+                         without ``marginals=`` removes ``self.marginals``: the attribute is always the last call's.
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -91,9 +106,9 @@ def fused_chunks(n_mcmc, stride, steps_max, buffer_bytes, bytes_per_step, work_m
 
 
 def _host_has_no_summary(kwargs):
-    """``summary=`` and ``burn=`` belong to the device paths of ``chains=M``."""
-    for name in ("summary", "burn"):
-        if kwargs.get(name, None) is not None:
+    """``summary=``, ``burn=`` and ``marginals=`` belong to the device paths of ``chains=M``."""
+    for name in ("summary", "burn", "marginals"):
+        if kwargs.get(name, None) is not None and not (name == "marginals" and kwargs[name] is False):
             raise ValueError("%s=%r summarises the chains of chains=M on the device; the host path keeps every state in "
                              "self.samples" % (name, kwargs.get(name)))
 
@@ -128,6 +143,122 @@ def finalise_summary(raw, n_draws, chains):
         rhat = np.sqrt(var_plus / W)
         ess = np.minimum(2.0 * M * n, 2.0 * M * var_plus / B)
     return dict(n=N, chains=M, mean=c + d, cov=(cc - T * np.outer(d, d)) / (T - 1), rhat=rhat, ess=ess, within=W, between=B)
+
+
+MARGINALS_KEYS = ("bins", "bins2d", "pairs", "range", "width")
+MARGINALS_BINS_MAX, MARGINALS_BINS2D_MAX, MARGINALS_PAIRS_MAX = 256, 64, 64      # CESX_CHAIN_HIST_*_MAX
+
+
+def marginals_spec(marginals, Ustar):
+    """What ``marginals=`` asks for, as the arrays ``Engine.chain_hist_begin`` takes: ``None`` (off: ``None`` / ``False``) or a
+    dict ``bins``, ``bins2d``, ``pairs`` (P, 2) int32, ``edges`` (p, bins + 1) and ``edges2d`` (p, bins2d + 1), fp64.
+
+    ``True`` is ``{}``.  Keys: ``bins`` (64), ``bins2d`` (20, what ``plots.find_levels`` uses), ``pairs`` (None, a list of
+    (i, j) with i != j, or 'all': every i < j), ``range`` ((p, 2) rows [lo, hi]; default row r of ``Ustar`` (p, J):
+    mean_r -+ width std_r, ddof = 1) and ``width`` (6.0; not read with ``range``).  Row r's edges are ``np.linspace(lo_r, hi_r, bins + 1)``, computed
+    here once: the device counts against these very bits.  Pure: no engine, no device; every refusal is a ValueError."""
+    if marginals is None or marginals is False:
+        return None
+    if marginals is True:
+        marginals = {}
+    if not isinstance(marginals, dict):
+        raise ValueError("marginals must be None, False, True or a dict with keys from %s, got %r" % (MARGINALS_KEYS, marginals))
+    unknown = [k for k in marginals if k not in MARGINALS_KEYS]
+    if unknown:
+        raise ValueError("marginals: unknown key(s) %s (known: %s)" % (sorted(map(str, unknown)), ", ".join(MARGINALS_KEYS)))
+    Ustar = np.asarray(Ustar, dtype=np.float64)
+    p = Ustar.shape[0]
+    sizes = {}
+    for name, default, most in (("bins", 64, MARGINALS_BINS_MAX), ("bins2d", 20, MARGINALS_BINS2D_MAX)):
+        v = marginals.get(name, default)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 2 <= v <= most:
+            raise ValueError("marginals: %s must be an integer in [2, %d], got %r" % (name, most, v))
+        sizes[name] = int(v)
+    pairs = marginals.get("pairs", None)
+    if pairs is None:
+        pairs = np.zeros((0, 2), dtype=np.int32)
+    elif isinstance(pairs, str):
+        if pairs != "all":
+            raise ValueError("marginals: pairs must be None, a list of (i, j) or 'all', got %r" % (pairs,))
+        if p * (p - 1) // 2 > MARGINALS_PAIRS_MAX:
+            raise ValueError("marginals: pairs='all' is %d pairs at p = %d; at most %d are counted -- name the pairs"
+                             % (p * (p - 1) // 2, p, MARGINALS_PAIRS_MAX))
+        pairs = np.array([(i, j) for i in range(p) for j in range(i + 1, p)], dtype=np.int32).reshape(-1, 2)
+    else:
+        try:
+            arr = np.asarray(pairs)
+        except ValueError:                                # a ragged list
+            arr = np.zeros(1)
+        if arr.size == 0:
+            arr = np.zeros((0, 2), dtype=np.int32)
+        if arr.ndim != 2 or arr.shape[1] != 2 or not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError("marginals: pairs must be None, a list of (i, j) or 'all', got %r" % (pairs,))
+        if len(arr) > MARGINALS_PAIRS_MAX:
+            raise ValueError("marginals: %d pairs; at most %d are counted" % (len(arr), MARGINALS_PAIRS_MAX))
+        if arr.size and (arr.min() < 0 or arr.max() >= p or np.any(arr[:, 0] == arr[:, 1])):
+            raise ValueError("marginals: every pair (i, j) needs i != j and both in [0, %d), got %r" % (p, pairs))
+        pairs = np.ascontiguousarray(arr, dtype=np.int32)
+    rng = marginals.get("range", None)
+    if rng is None:
+        width = marginals.get("width", 6.0)
+        if isinstance(width, bool) or not isinstance(width, (int, float, np.integer, np.floating)) or not (np.isfinite(width) and width > 0):
+            raise ValueError("marginals: width must be a finite number > 0, got %r" % (width,))
+        mean = Ustar.mean(axis=1)
+        std = Ustar.std(axis=1, ddof=1) if Ustar.shape[1] > 1 else np.zeros(p)
+        if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(std)) and np.all(std > 0)):
+            raise ValueError("marginals: the spread of enka.Ustar is zero or not finite in row(s) %s, so the default range "
+                             "mean -+ width std is empty; pass range= (p, 2)"
+                             % np.nonzero(~(np.isfinite(mean) & np.isfinite(std) & (std > 0)))[0].tolist())
+        rng = np.stack([mean - float(width) * std, mean + float(width) * std], axis=1)
+    else:
+        rng = np.asarray(rng, dtype=np.float64)
+        if rng.shape != (p, 2):
+            raise ValueError("marginals: range must have shape (%d, 2), rows [lo, hi]; got %s" % (p, rng.shape))
+    if not (np.all(np.isfinite(rng)) and np.all(rng[:, 0] < rng[:, 1])):
+        raise ValueError("marginals: every row of the range needs finite lo < hi, got %r" % (rng.tolist(),))
+    edges = np.stack([np.linspace(lo, hi, sizes["bins"] + 1) for lo, hi in rng])
+    edges2d = np.stack([np.linspace(lo, hi, sizes["bins2d"] + 1) for lo, hi in rng])
+    for e in (edges, edges2d):
+        if not np.all(np.diff(e, axis=1) > 0):
+            raise ValueError("marginals: a range is too narrow for its bins: the edges are not strictly increasing")
+    return dict(bins=sizes["bins"], bins2d=sizes["bins2d"], pairs=pairs, edges=edges, edges2d=edges2d)
+
+
+def marginal_density(marginals, row):
+    """``(centres, density)`` of row ``row`` of ``MCMC.marginals``: the bin centres and count / (all draws x bin width).  The
+    density integrates to the fraction of the draws inside the range (1 when ``below`` and ``above`` are 0)."""
+    e = np.asarray(marginals["edges"][row], dtype=np.float64)
+    h = np.asarray(marginals["hist1d"][row], dtype=np.float64)
+    total = h.sum() + float(marginals["below"][row]) + float(marginals["above"][row])
+    return 0.5 * (e[:-1] + e[1:]), h / (total * np.diff(e))
+
+
+def marginal_quantiles(marginals, q):
+    """The quantiles ``q`` (in [0, 1]) of every row from ``MCMC.marginals``: (p, len(q)).  The cumulative mass starts at
+    ``below`` and ends short of 1 by ``above``; inside a bin it is linear (the draws taken as uniform over the bin), so the
+    value is within one bin width of the sample quantile.  NaN where the quantile falls outside the range."""
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if np.any(~((q >= 0) & (q <= 1))):
+        raise ValueError("marginal_quantiles: q must lie in [0, 1]")
+    edges = np.asarray(marginals["edges"], dtype=np.float64)
+    out = np.full((edges.shape[0], q.size), np.nan)
+    for r in range(edges.shape[0]):
+        h = np.asarray(marginals["hist1d"][r], dtype=np.float64)
+        below, above = float(marginals["below"][r]), float(marginals["above"][r])
+        total = h.sum() + below + above
+        if total == 0:
+            continue
+        cum = below + np.concatenate([[0.0], np.cumsum(h)])        # the mass left of every edge
+        nz = np.nonzero(h)[0]
+        for i, t in enumerate(q * total):
+            if t < cum[0] or t > cum[-1] or nz.size == 0:          # in the mass below or above the range
+                continue
+            k = int(np.searchsorted(cum, t, side="left"))          # the first edge with cum >= t: cum[k - 1] < t <= cum[k]
+            if k == 0:                                             # t == below exactly: where the inside mass begins
+                out[r, i] = edges[r, nz[0]]
+            else:
+                out[r, i] = edges[r, k - 1] + (t - cum[k - 1]) / (cum[k] - cum[k - 1]) * (edges[r, k] - edges[r, k - 1])
+    return out
 
 
 class MCMC(object):
@@ -362,6 +493,8 @@ class MCMC(object):
         ``kwargs['summary'] = True`` (with ``kwargs['burn']`` steps left out) keeps the kept states on the device and sums
         them there (``eng.chain_summary_*``): ``self.summary`` (``finalise_summary``) instead of a trace in ``self.samples``,
         which gains the start state of a fresh run and the call's last state only.  The chains run as without it.
+        ``kwargs['marginals']`` (``marginals_spec``; needs ``summary=True``) counts the same draws into histograms on the device
+        (``eng.chain_hist_*``): ``self.marginals``.  The chains and ``self.summary`` are as without it.
         """
         import torch
         M = kwargs["chains"]
@@ -392,6 +525,11 @@ class MCMC(object):
             if n_draws < 4:
                 raise ValueError("summary=True: %d steps at trace_stride %d with burn=%d leave %d draws per chain; the split "
                                  "statistics need 4 (two half-chains of two)" % (n_mcmc, stride, burn, n_draws))
+        marg = kwargs.get("marginals", None)
+        if marg is not None and marg is not False and not summary:
+            raise ValueError("marginals=%r counts the draws summary=True sums; without summary=True every kept state is in "
+                             "self.samples and numpy.histogram counts them" % (marg,))
+        marg = marginals_spec(marg, enka.Ustar)
         p, n = enka.p, enka.n_obs
         scales = scales_of(update)
         start = kwargs.get("start", "mean")
@@ -429,6 +567,8 @@ class MCMC(object):
             base, kept = int(getattr(self, "_mh_next_step", 0)), []
         if summary:                                       # the draws stay on the device: cesx_chain_summary_*
             eng.chain_summary_begin(n_draws)
+        if marg:                                          # and are counted there: cesx_chain_hist_*, the same slices
+            eng.chain_hist_begin(marg["edges"], marg["edges2d"], marg["pairs"])
 
         if fused:
             # launches of at most K_max steps (cesx_mh_run_map / cesx_gp_run; fused_chunks): K_max a multiple of the stride --
@@ -457,6 +597,8 @@ class MCMC(object):
                     t0 = max(0, burn // stride - k0 // stride)
                     if t0 < K // stride:
                         eng.chain_summary_add(tr[t0:])
+                        if marg:
+                            eng.chain_hist_add(tr[t0:])
                 elif K // stride:
                     kept.extend(tr.cpu().numpy().astype(np.float64))
             if (summary or n_mcmc % stride) and n_mcmc > 0:   # the run's last state, where the trace does not hold it
@@ -475,12 +617,20 @@ class MCMC(object):
                 if summary:
                     if (k + 1) % stride == 0 and k + 1 > burn:
                         eng.chain_summary_add(U)
+                        if marg:
+                            eng.chain_hist_add(U)
                     if k + 1 == n_mcmc:
                         kept.append(eng.to_host(U))
                 elif (k + 1) % stride == 0 or k + 1 == n_mcmc:
                     kept.append(eng.to_host(U))
         if summary:
             self.summary = finalise_summary(eng.chain_summary_read(), n_draws, M)
+        self.__dict__.pop("marginals", None)             # a call without marginals= leaves no earlier call's counts behind
+        if marg:
+            counts = eng.chain_hist_read()
+            self.marginals = dict(n=n_draws, chains=M, edges=marg["edges"], hist1d=counts["hist1d"], below=counts["below"],
+                                  above=counts["above"], pairs=marg["pairs"], edges2d=marg["edges2d"], hist2d=counts["hist2d"],
+                                  outside2d=counts["outside2d"])
         steps, rate, per = eng.mh_stats(per_chain=True)
 
         new = np.stack(kept, axis=1) if kept else np.zeros((p, 0, M))      # (p, n_new, M)

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CESX_ABI_VERSION 8
+#define CESX_ABI_VERSION 9
 
 /* status codes */
 #define CESX_OK            0
@@ -605,6 +605,49 @@ int cesx_chain_summary_add(cesx_handle h, const void* trace_dev, int kept, void*
    is launched then); the stage stays readable until the next begin. */
 int cesx_chain_summary_read(cesx_handle h, double* c, double* s1, double* cc, double* within, double* between,
                             double* half_mean, double* half_var, void* stream);
+
+/* ---- Streaming marginals of the chains' draws (MCMC(..., chains=M, summary=True, marginals=...); kernels_chainhist.hip) --
+   Histograms of every parameter (row) and of chosen pairs of parameters over all draws of all M = J_local chains, counted
+   from the draws while they are in device memory: the input of cesx_chain_summary_add, the other half of its summary.
+   The bin rule is fp64 throughout (an fp32 draw converts exactly).  For a row with strictly increasing edges e[0 .. B] a
+   draw x lands in bin k where e[k] <= x < e[k + 1], and x == e[B] lands in bin B - 1: what numpy.histogram(x, bins=e)
+   counts.  x < e[0] (and -inf) counts as `below`; everything else not inside (x > e[B], +inf, NaN) as `above`; a 2-D draw
+   with either coordinate outside goes to the pair's one `outside` counter.  The edges need not be uniform: a guessed bin
+   is kept only where the edge array confirms it.
+   Counts are integers: a workgroup counts in LDS (32 bits; a launch is cut so that they cannot overflow) and adds what
+   it counted to the run's 64-bit totals with integer atomics, so the totals depend neither on the order of the
+   workgroups nor on how the run is cut into adds: they are exact, and equal numpy's bit for bit.
+   The stage keeps state of its own, sized by p and the caps below alone (not by J_local), allocated by the first begin
+   and kept until cesx_destroy; cesx_set_problem does not touch it.  Its size at p = 256 (any J_local, 65 536 included):
+   the 1-D totals p x (256 + 2) x 8 bytes = 528 KB and edges p x 257 x 8 bytes = 526 KB, the 2-D totals
+   64 pairs x (64 x 64 + 1 outside counter) x 8 bytes = 2.1 MB and edges 64 x 2 x 65 x 8 bytes = 67 KB. */
+#define CESX_CHAIN_HIST_BINS_MAX    256
+#define CESX_CHAIN_HIST_BINS2D_MAX  64
+#define CESX_CHAIN_HIST_PAIRS_MAX   64
+typedef struct {
+    uint32_t struct_bytes;    /* sizeof(cesx_chain_hist_desc) */
+    int32_t bins;             /* B of the 1-D histograms, 2 .. CESX_CHAIN_HIST_BINS_MAX */
+    int32_t bins2d;           /* B2 of the 2-D histograms, 2 .. CESX_CHAIN_HIST_BINS2D_MAX */
+    int32_t n_pairs;          /* 0 .. CESX_CHAIN_HIST_PAIRS_MAX */
+    const double* edges1;     /* HOST [p][bins + 1], every row finite and strictly increasing */
+    const double* edges2;     /* HOST [p][bins2d + 1]; only the rows named in `pairs` are read (NULL allowed for n_pairs 0) */
+    const int32_t* pairs;     /* HOST [n_pairs][2] rows (i, j), i != j, both in [0, p) (NULL allowed for n_pairs 0) */
+} cesx_chain_hist_desc;
+/* Starts a run: copies the descriptor and clears the totals (synchronises `stream` first: an earlier run's adds are
+   done).  CESX_EINVAL (text in cesx_last_error) for a bad descriptor, a limit above, a pair with i == j or an index outside
+   [0, p), edges that are not finite and strictly increasing, or a sharded handle (J_local != J_global); the run in hand,
+   if any, goes on unharmed. */
+int cesx_chain_hist_begin(cesx_handle h, const cesx_chain_hist_desc* desc, void* stream);
+/* Counts `kept` draws laid out [kept][p][J_local] in the engine dtype: the arguments of cesx_chain_summary_add.  Reads
+   the draws and writes only the stage's own memory.  CESX_ESTATE without a begin, CESX_EINVAL for a null pointer or
+   kept < 1; neither launches anything. */
+int cesx_chain_hist_add(cesx_handle h, const void* trace_dev, int kept, void* stream);
+/* HOST outputs, all unsigned long long; synchronises `stream`.  hist1 [p][bins]; out1 [p][2] (below, above);
+   hist2 [n_pairs][bins2d][bins2d], the row index the bin of the pair's first parameter, the column that of its second;
+   out2 [n_pairs] (hist2 and out2 may be NULL for n_pairs 0).  May be called more than once; an add after a read
+   continues the run.  CESX_ESTATE without a begin. */
+int cesx_chain_hist_read(cesx_handle h, unsigned long long* hist1, unsigned long long* out1, unsigned long long* hist2,
+                         unsigned long long* out2, void* stream);
 
 /* ---- Emulate: GP prediction and the GP sampler over the columns (ces/emulate.py, ces/sample.py:17-119) --
    One exact GP per output, trained on the host (ces_amd/emulate.py); the engine holds its own fp64 image of them and
