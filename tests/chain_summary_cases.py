@@ -31,12 +31,28 @@ import numpy as np
 
 EPS = 2.0 ** -52
 SLAB, WGS, TC, CH = 2048, 1024, 32, 1024    # kernels_chainsum.hip: CS_SLAB, CS_WGS, CS_TC, CS_CH
+SLICES, RL = 64, 32                         # CS_SLICES, CS_RL
 
 # engine level (the issue's table): every p x J x N below runs in both dtypes, both families and the three chunkings
 P_SET = (1, 3, 16, 17, 33)
 J_SET = (1, 2, 63, 64, 65, 130)
 N_SET = (4, 5, 9)
 FAMILIES = ("centred", "offset")
+
+# The launch plan's other regimes (``plan_of``): at every shape of the table above there is one 64 x 64 super tile, one staged
+# tile per slab, at most five slabs, one slice of the row sums and one workgroup of the half reduce.  (p, J, N), the smallest
+# shapes that reach each regime; tests/test_chain_summary_host.py asserts from ``plan_of`` that they do.
+#   (64, 65, 5)      a full single super tile: all four waves of chain_pool_kernel, wave w with w + 1 blocks
+#   (65, 130, 4)     3 pairs: one row in super tile 1, the off-diagonal tile (1, 0) with one staged row of A and all 8 of B
+#   (129, 65, 5)     6 pairs: si = 2, the tiles (2, 0) and (2, 1)
+#   (2, 1025, 5)     33 slabs (a second pass of the 32 reduce lanes), 2 slices, 2 workgroups of the half reduce
+#   (3, 32801, 4)    slabs of 64 chains (two tiles a draw), 513 slabs, the last of 33 chains (its second tile holds one),
+#                    33 slices and workgroups
+#   (1, 65601, 4)    slabs of 96 chains (three tiles), 684 slabs, 64 slices -- the cap, where ceil(J / 1024) = 65 --, 65 workgroups
+#   (129, 5505, 4)   off-diagonal tiles and two tiles a draw together (6 pairs, 87 slabs, the last of one chain)
+# Not covered: the clamp of a slab at CS_SLAB chains (``lo > want`` in cs_slab_cols) needs J > 2^21 at p <= 64, or close to a
+# gigabyte of trace at a larger p.
+PLAN_SHAPES = ((64, 65, 5), (65, 130, 4), (129, 65, 5), (2, 1025, 5), (3, 32801, 4), (1, 65601, 4), (129, 5505, 4))
 
 
 def chunkings(N):
@@ -67,6 +83,17 @@ def slab_plan(p, J):
     per = -(-J // want)
     cols = -(-per // TC) * TC
     return cols, -(-J // cols)
+
+
+def plan_of(p, J):
+    """The launch plan of the stage at an engine of p rows and J chains, from the kernel file's constants as ``slab_plan`` is:
+    ``pairs`` (super tiles of the lower triangle: cs_pairs), ``cols`` and ``slabs`` (``slab_plan``), ``ntile`` (staged tiles a
+    draw of the widest slab), ``last`` (chains of the last slab), ``slices`` (of the row sums behind c: cs_slices) and
+    ``blocks`` (workgroups a row of chain_half_reduce_kernel: cs_blocks)."""
+    t = -(-p // 64)
+    cols, slabs = slab_plan(p, J)
+    return dict(pairs=t * (t + 1) // 2, cols=cols, slabs=slabs, ntile=-(-min(J, cols) // TC), last=J - (slabs - 1) * cols,
+                slices=max(1, min(SLICES, -(-J // 1024))), blocks=-(-J // CH))
 
 
 def c_pool(N, J, p):
@@ -104,6 +131,11 @@ def ref_raw(trace, c=None, mutant=None):
         lo, hi = x[:n + 1], x[N - n + 1:]
     if mutant == "chain_left_out":                          # (J > 1)
         pooled = x[:, :, :-1]
+    cols, _ = slab_plan(p, J)
+    if mutant == "tile_dropped":                            # (cols > TC) the second staged tile of every slab never summed
+        pooled = x[:, :, (np.arange(J) % cols) // TC != 1]
+    if mutant == "chain_twice":                             # (slabs > 1) slab 0's ragged tile not zeroed past its j1
+        pooled = np.concatenate([x, x[:, :, cols:cols + 1]], axis=2)
     S1 = np.stack([(h - shift).sum(axis=0) for h in (lo, hi)])
     S2 = np.stack([((h - shift) ** 2).sum(axis=0) for h in (lo, hi)])
     A1 = np.stack([np.abs(h - shift).sum(axis=0) for h in (lo, hi)])
@@ -120,6 +152,8 @@ def ref_raw(trace, c=None, mutant=None):
     d = pooled - c[None, :, None]
     s1 = d.sum(axis=(0, 2))
     cc = np.einsum("npj,nqj->pq", d, d)
+    if mutant == "off_tile_uncentred":                      # (p > 64) the B panel of an off-diagonal super tile staged with c = 0
+        cc[64:, :64] = np.einsum("npj,nqj->pq", d[:, 64:], pooled[:, :64])
     B_s1 = np.abs(d).sum(axis=(0, 2))
     B_cc = np.einsum("npj,nqj->pq", np.abs(d), np.abs(d))
     mm, vv = (m[:, :, :-1], v[:, :, :-1]) if mutant == "chain_left_out" else (m, v)
@@ -134,7 +168,16 @@ def ref_raw(trace, c=None, mutant=None):
                 a0_abs=f(np.abs(dm).sum(axis=(0, 2))), a1=f(a1), dm_abs=f(np.abs(dm)), v_abs=f(np.abs(vv)))
 
 
-MUTANTS = ("draw_dropped", "half_boundary_off_by_one", "shift_not_added_back", "chain_left_out", "sums_about_zero")
+MUTANTS = ("draw_dropped", "half_boundary_off_by_one", "shift_not_added_back", "chain_left_out", "sums_about_zero",
+           "tile_dropped", "chain_twice", "off_tile_uncentred")
+
+
+def mutant_applies(name, p, J):
+    """Whether the mutant ``name`` changes anything at an engine of p rows and J chains: the last three model a regime of the
+    launch plan and are the reference itself where the plan does not reach it."""
+    plan = plan_of(p, J)
+    return {"chain_left_out": J > 1, "tile_dropped": plan["ntile"] > 1, "chain_twice": plan["slabs"] > 1,
+            "off_tile_uncentred": plan["pairs"] > 1}.get(name, True)
 
 
 def wb_bounds(ref):

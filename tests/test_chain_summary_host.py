@@ -6,7 +6,10 @@
 2. Two fixed-seed sanity cases: iid chains give rhat near 1 and ess near the draw count; half the chains shifted by three
    standard deviations give a clearly larger rhat.
 3. The reference made wrong on purpose -- a draw dropped, the half boundary off by one, the shift not added back, a chain left
-   out, sums about zero instead of about the chain's first draw -- leaves the bounds the GPU test applies by a clear factor.
+   out, sums about zero instead of about the chain's first draw -- leaves the bounds the GPU test applies by a clear factor,
+   at the shapes of the launch plan's other regimes too (``PLAN_SHAPES``: the table is held to the regimes it names from
+   ``plan_of``), where three more mutants model what those regimes can get wrong: the second staged tile of every slab
+   dropped, a chain of the next slab counted in a slab's ragged tile, an off-diagonal super tile formed without centring.
 4. The ABI: the three entry points, the version, the new translation unit, the stage struct on the host compiler alone.
 5. The argument errors that need no device."""
 import ctypes
@@ -105,10 +108,58 @@ def test_shifted_chains_have_a_large_rhat():
 
 # ---- 3. the bounds see the mutants ----------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("shape", HOST_SHAPES, ids=str)
+PLAN_HOST_SHAPES = [s for s in cs.PLAN_SHAPES if s != (129, 5505, 4)]      # (left out for time: its reference takes seconds)
+
+
+def test_plan_shapes_reach_the_regimes_they_name():
+    """``PLAN_SHAPES`` against ``plan_of``: every regime the table's comment names is reached by the shape it names, and the
+    older table reaches none of them."""
+    assert cs.PLAN_SHAPES == ((64, 65, 5), (65, 130, 4), (129, 65, 5), (2, 1025, 5), (3, 32801, 4), (1, 65601, 4), (129, 5505, 4))
+    assert (cs.SLAB, cs.WGS, cs.TC, cs.CH, cs.SLICES, cs.RL) == (2048, 1024, 32, 1024, 64, 32)
+    src = open(os.path.join(ROOT, "ces_amd", "csrc", "kernels_chainsum.hip")).read()
+    for name, v in (("CS_SLAB", cs.SLAB), ("CS_WGS", cs.WGS), ("CS_TC", cs.TC), ("CS_CH", cs.CH), ("CS_SLICES", cs.SLICES)):
+        assert "constexpr int %s = %d;" % (name, v) in src, name
+    assert "CS_RL = %d;" % cs.RL in src
+    plan = {s: cs.plan_of(s[0], s[1]) for s in cs.PLAN_SHAPES}
+    for s, pl in plan.items():
+        assert (pl["cols"], pl["slabs"]) == cs.slab_plan(s[0], s[1]) and pl["cols"] % cs.TC == 0 and pl["cols"] <= cs.SLAB
+        assert (pl["slabs"] - 1) * pl["cols"] < s[1] <= pl["slabs"] * pl["cols"] and 1 <= pl["last"] <= pl["cols"]
+    for p in cs.P_SET:                                       # the older table: one super tile, one tile, one pass, one slice
+        for J in cs.J_SET:
+            pl = cs.plan_of(p, J)
+            assert (pl["pairs"], pl["cols"], pl["ntile"], pl["slices"], pl["blocks"]) == (1, 32, 1, 1, 1) and pl["slabs"] <= 5
+    # a full single super tile: the largest p with one pair (wave 3's block row is whole); one row more makes 3 pairs, two
+    # super tiles more rows 6 (si = 2: the off-diagonal tiles (2, 0) and (2, 1))
+    assert plan[(64, 65, 5)]["pairs"] == 1 and plan[(65, 130, 4)]["pairs"] == 3 and cs.plan_of(128, 130)["pairs"] == 3
+    assert plan[(129, 65, 5)]["pairs"] == 6
+    assert all(plan[s]["ntile"] == 1 and plan[s]["slabs"] <= 5 for s in cs.PLAN_SHAPES[:3])
+    # a second pass of the reduce lanes, two slices, two workgroups of the half reduce
+    pl = plan[(2, 1025, 5)]
+    assert pl["slabs"] == 33 > cs.RL and (pl["slices"], pl["blocks"], pl["ntile"]) == (2, 2, 1)
+    # two tiles a draw, a ragged last slab whose second tile holds one chain
+    pl = plan[(3, 32801, 4)]
+    assert (pl["cols"], pl["ntile"], pl["slabs"], pl["last"], pl["slices"], pl["blocks"]) == (64, 2, 513, 33, 33, 33)
+    assert pl["last"] - cs.TC == 1
+    # three tiles a draw, the slices at their cap below the workgroups of the half reduce
+    pl = plan[(1, 65601, 4)]
+    assert (pl["cols"], pl["ntile"], pl["slabs"], pl["slices"], pl["blocks"]) == (96, 3, 684, 64, 65)
+    assert -(-65601 // 1024) == 65 > cs.SLICES
+    # off-diagonal tiles and two tiles a draw together
+    pl = plan[(129, 5505, 4)]
+    assert (pl["pairs"], pl["cols"], pl["ntile"], pl["slabs"], pl["last"]) == (6, 64, 2, 87, 1)
+    # each of the regimes' mutants changes something at one shape of the host's part of the table at least
+    for name in ("tile_dropped", "chain_twice", "off_tile_uncentred"):
+        assert any(cs.mutant_applies(name, s[0], s[1]) for s in PLAN_HOST_SHAPES), name
+    assert not any(cs.mutant_applies("tile_dropped", p, J) or cs.mutant_applies("off_tile_uncentred", p, J)
+                   for p in cs.P_SET for J in cs.J_SET)
+
+
+@pytest.mark.parametrize("shape", HOST_SHAPES + PLAN_HOST_SHAPES, ids=str)
 def test_the_bounds_hold_fp64_numpy_and_no_mutant(shape):
     """(a) the same sums in plain fp64 numpy stay inside the bounds; (b) every mutant leaves them by more than 100x in one
-    output at least, in one of the two families at least (sums about zero: in the offset family)."""
+    output at least, in one of the two families at least (sums about zero: in the offset family).  A mutant of a plan regime
+    is asked for at the shapes whose plan reaches that regime (``mutant_applies``: elsewhere it is the reference itself);
+    test_plan_shapes_reach_the_regimes_they_name holds each to one such shape at least."""
     p, J, N = shape
     seen = {}
     for fam in cs.FAMILIES:
@@ -133,7 +184,7 @@ def test_the_bounds_hold_fp64_numpy_and_no_mutant(shape):
             assert np.all(np.abs(np.tril(np.einsum("npj,nqj->pq", dd, dd)) - ref["cc"]) <= bounds["cc"])
             # (b)
             for name in cs.MUTANTS:
-                if name == "chain_left_out" and J == 1:
+                if not cs.mutant_applies(name, p, J):
                     continue
                 mut = cs.ref_raw(x, c=ref["c"], mutant=name)
                 worst = 0.0
@@ -145,7 +196,7 @@ def test_the_bounds_hold_fp64_numpy_and_no_mutant(shape):
                 seen[name] = max(seen.get(name, 0.0), worst)
     print("%s: mutants / bound %s" % (shape, {k: "%.3g" % v for k, v in seen.items()}))
     assert all(v > 100.0 for v in seen.values()), (shape, "mutants the bounds cannot see (ratio to the bound)", seen)
-    assert len(seen) == len(cs.MUTANTS) - (J == 1)
+    assert set(seen) == {m for m in cs.MUTANTS if cs.mutant_applies(m, p, J)} and len(seen) >= 5 - (J == 1)
 
 
 # ---- 4. the ABI -----------------------------------------------------------------------------------------------------------

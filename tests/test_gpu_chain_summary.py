@@ -4,7 +4,9 @@ Engine level: synthetic traces are uploaded and summed in three chunkings; every
 elementwise to  c 2^-52 B  against the fp64 reference computed from the same, already rounded, trace
 (tests/chain_summary_cases.py: the reference, the tables, the derivation of every c; tests/test_chain_summary_host.py shows
 that the bounds see the reference made wrong).  Two identical runs are the same bits; the per-chain outputs are the same bits
-across the chunkings, the pooled sums stay inside the bound in each.
+across the chunkings, the pooled sums stay inside the bound in each.  A second table (``cs.PLAN_SHAPES``) holds the same
+conditions at the launch plan's other regimes: several super tiles, several staged tiles a draw, more slabs than reduce
+lanes, several slices and workgroups of the two row reduces.
 Sampler level: every run twice with the same seed, with and without ``summary=True``: the chains are the same bits, and
 ``summary`` is the reference applied to the twin's kept states.
 
@@ -87,6 +89,64 @@ def test_raw_sums_against_fp64(p, dtype):
                     assert np.all(np.abs(fin[k] - want[k])[ok] <= b[ok]), (tag, k)
         eng.close()
     print("\n[chainsum] p = %d %s: worst |dev - ref| / bound %s" % (p, dtype, {k: "%.3g" % v for k, v in worst.items()}))
+
+
+def _plan_cases():
+    """(shape, dtype, families) over ``cs.PLAN_SHAPES``: both dtypes and both families, but (129, 5505, 4) -- whose extended
+    precision reference takes seconds -- once per dtype with one family each."""
+    out = []
+    for shape in cs.PLAN_SHAPES:
+        for k, dtype in enumerate(("float64", "float32")):
+            out.append((shape, dtype, (cs.FAMILIES[k],) if shape == (129, 5505, 4) else cs.FAMILIES))
+    return out
+
+
+SINGLES_MAX = 1 << 16                                         # draw-by-draw adds too where N J p is at most this
+
+
+@pytest.mark.parametrize("shape,dtype,families", _plan_cases(), ids=["p%d-J%d-N%d-%s" % (s + (d,)) for s, d, _ in _plan_cases()])
+def test_raw_sums_at_the_plans_other_regimes(shape, dtype, families):
+    """test_raw_sums_against_fp64 at the shapes that reach the launch plan's other regimes (``cs.PLAN_SHAPES``: several super
+    tiles and the off-diagonal branch, two and three staged tiles a draw with a ragged last one, a second pass of the reduce
+    lanes, several slices of the row sums -- their cap -- and several workgroups of the half reduce), under the same bounds:
+    ``cs.raw_bounds``, ``cs.c_shift`` and ``cs.summary_bounds`` take their depths from the plan."""
+    import torch
+    from ces_amd import engine, sample
+    p, J, N = shape
+    worst = {k: 0.0 for k in RAW + ("c",)}
+    eng = engine.Engine(p, 2, J, dtype=dtype)
+    for fam in families:
+        x = cs.make_trace(p, J, N, fam, dtype)
+        t = torch.as_tensor(x, device=eng.device).to(eng.torch_dtype).contiguous()
+        assert np.array_equal(t.double().cpu().numpy(), x)              # the upload is exact: the trace was rounded first
+        chunkings = cs.chunkings(N)
+        if N * J * p > SINGLES_MAX:
+            del chunkings["singles"]
+        outs = {name: _summed(eng, t, ch) for name, ch in chunkings.items()}
+        again = _summed(eng, t, [N])
+        ref = cs.ref_raw(x, c=outs["one"]["c"])
+        bounds = cs.raw_bounds(ref)
+        tag = (shape, fam, dtype)
+        # the pooled shift against the row mean of the first draw, then everything else about the device's own c
+        mean0 = np.asarray(x[0].astype(np.longdouble).sum(axis=1) / J, dtype=np.float64)
+        worst["c"] = max(worst["c"], _ratio(outs["one"]["c"], mean0, cs.c_shift(J) * cs.EPS * ref["B_c"]))
+        for name, out in outs.items():
+            assert np.array_equal(out["c"], outs["one"]["c"]), tag
+            assert np.all(np.triu(out["cc"], 1) == 0), tag
+            for k in RAW:
+                worst[k] = max(worst[k], _ratio(out[k], ref[k], bounds[k]))
+            for k in PER_CHAIN:                                      # a chain's sums do not depend on the chunking
+                assert np.array_equal(out[k], outs["one"][k]), (tag, name, k)
+        for k in RAW + ("c",):                                       # two identical runs: the same bits
+            assert np.array_equal(again[k], outs["one"][k]), (tag, k)
+        print("\n[chainsum plan] %s %s %s %s: worst |dev - ref| / bound so far %s"
+              % (shape, cs.plan_of(p, J), fam, dtype, {k: "%.3g" % v for k, v in worst.items()}))
+        assert all(v <= 1.0 for v in worst.values()), (tag, worst)
+        fin, want, fb = sample.finalise_summary(outs["one"], N, J), cs.finalise_ref(ref), cs.summary_bounds(ref)
+        for k, b in fb.items():
+            ok = np.isfinite(want[k]) & np.isfinite(b)
+            assert np.all(np.abs(fin[k] - want[k])[ok] <= b[ok]), (tag, k)
+    eng.close()
 
 
 def test_error_returns_leave_the_stage_alone():
