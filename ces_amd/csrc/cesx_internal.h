@@ -763,6 +763,15 @@ inline MhChains mh_chains(const Engine& e, bool start, const double* logu, unsig
 int launch_mh_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s);
 // kernels_gp.hip: the GP means (and variances, var_out != nullptr) of the states X (p x J, engine dtype) into fp64 (gp.n x J)
 int launch_gp_predict(Engine& e, const void* X, double* mean, double* var, bool nugget, hipStream_t s);
+// kernels_gpgrad.hip: launch_gp_predict with the gradients of the rows with respect to x, fp64 (gp.n x p x J); var and dvar
+// nullptr: the mean-only mode
+int launch_gp_predict_grad(Engine& e, const void* X, double* mean, double* var, double* dmean, double* dvar, bool nugget,
+                           hipStream_t s);
+// kernels_gpgrad.hip: the Langevin step on the GP rows and gradients.  what 0: phi and g = S^T grad phi of the states X into
+// mh.phi / mh.lv_g, counters cleared; 1: P = U + S (xi - g / 2) with the block in mh.xi; 2: the proposal X with its rows, the
+// test with the Langevin correction, U := X, phi and g on the accepted columns
+int launch_gp_langevin(Engine& e, int what, int mode, const void* X, const double* mean, const double* var, const double* dmean,
+                       const double* dvar, void* U, void* P, const double* logu, unsigned step, hipStream_t s);
 // kernels_gp.hip: phi of the states X from the GP rows (mode CESX_GP_GAMMA / _VAR / _GAMMA_VAR); start: into mh.phi,
 // counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double* mean, const double* var, void* U,

@@ -12,29 +12,33 @@ namespace cesx {
 
 // ---- Metropolis-Hastings over the columns (cesx_mh_*, kernels_mh.hip); the chains of cesx_gp_* are these too ----
 struct MhState {
-    int kind = -1;                     // CESX_MH_RW / CESX_MH_PCN after cesx_mh_set_proposal, -1: none (cesx_set_problem drops it)
+    int kind = -1;                     // CESX_MH_RW / CESX_MH_PCN / CESX_MH_LANGEVIN after cesx_mh_set_proposal, -1: none (cesx_set_problem drops it)
     double a = 1.0;                    // P = a U + (b S) xi
     bool dense_prior = false;          // RW with a dense Sigma: the prior term is scored through w = L_Sigma^{-1} (u - mu)
     bool started = false;
+    bool lv_proposed = false;          // Langevin: a cesx_gp_langevin_propose since the start or the last accept (its block is in xi)
     unsigned long long steps = 0;      // cesx_mh_accept calls since cesx_mh_start
     DevBuf<void> W, Wf;                // b S zero padded [rpad][kp], row-major and in the LDS-DMA kernels' order
     DevBuf<void> Li, Li_f;             // dense prior: L_Sigma^{-1} in the same two layouts
     DevBuf<void> lb;                   // dense prior: -L_Sigma^{-1} mu [rpad] (the bias of the w launch)
     DevBuf<void> w;                    // dense prior: [p][J] w of the states being scored
-    DevBuf<void> xi;                   // fp64: [p][J] the step's noise block (update3_kernel reads segments from memory)
+    DevBuf<void> xi;                   // fp64: [p][J] the step's noise block (update3_kernel reads segments from memory); Langevin: either dtype, kept from propose to accept
     DevBuf<double> phi;                // [J] phi of the chains' current states
     DevBuf<unsigned long long> cnt;    // [J] accepted proposals per chain
     DevBuf<double> LSi;                // [p][p] L_Sigma^{-1} of a dense Sigma, fp64: the dense prior's factor as gp_score_kernel reads it
     DevBuf<double> bS;                 // [p][p] b S, fp64 row-major: the proposal as gp_chain_kernel reads it (cesx_gp_run)
     std::vector<double> h_bS;          // [p][p] b S on the host: cesx_mh_run_map passes it by value
+    DevBuf<double> lv_g, lv_gp;        // Langevin: [p][J] g = S^T grad phi of the chains' states and of the proposals (kernels_gpgrad.hip)
+    DevBuf<double> lv_a, lv_b, lv_gphi; // Langevin: [n][J], [n][J], [p][J] what lv_score keeps per chain: a_i, b_i, grad phi
     bool none() const { return kind < 0; }
-    void drop() { kind = -1; started = false; }      // every buffer is sized by the engine: kept
+    void drop() { kind = -1; started = false; lv_proposed = false; }      // every buffer is sized by the engine: kept
 };
 
 // ---- GP emulator over the columns (cesx_gp_*, kernels_gp.hip) ----
 struct GpState {
     int n = 0, Jt = 0, Jp = 0;         // GPs, training points, training points rounded up to 16 (n 0: no emulator)
     size_t li_len = 0;                 // doubles of one GP's packed L^{-1} (Jp/16 (Jp/16 + 1)/2 blocks of 256)
+    bool matern12 = false;             // a GP of family 1: no gradient (cesx_gp_predict_grad refuses)
     DevBuf<double> A;                  // [n][p][p] the input maps A_i (lower triangular)
     DevBuf<double> c;                  // [p] the input shift c
     DevBuf<double> Z;                  // [n][Jt][p] the mapped training points

@@ -867,7 +867,7 @@ int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) 
     if (!h) return CESX_EINVAL;
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!S) { e.err = "cesx_mh_set_proposal: null pointer"; return CESX_EINVAL; }
-    if (kind != CESX_MH_RW && kind != CESX_MH_PCN) { e.err = "cesx_mh_set_proposal: unknown proposal kind"; return CESX_EINVAL; }
+    if (kind != CESX_MH_RW && kind != CESX_MH_PCN && kind != CESX_MH_LANGEVIN) { e.err = "cesx_mh_set_proposal: unknown proposal kind"; return CESX_EINVAL; }
     if (kind == CESX_MH_PCN && !(beta > 0.0 && beta <= 1.0)) { e.err = "cesx_mh_set_proposal: pCN needs 0 < beta <= 1"; return CESX_EINVAL; }
     if (!e.problem_set) { e.err = "cesx_set_problem has not been called"; return CESX_ESTATE; }
     const int p = e.p;
@@ -902,7 +902,12 @@ int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) 
         TRY(upload_T(e, e.mh.lb, lb.data(), e.rpad));
         TRY_BUF(e.mh.w.ensure((size_t)p * (size_t)e.J * e.esz));
     }
-    if (e.cfg.dtype == CESX_F64) TRY_BUF(e.mh.xi.ensure((size_t)p * (size_t)e.J * 8));
+    if (e.cfg.dtype == CESX_F64 || kind == CESX_MH_LANGEVIN) TRY_BUF(e.mh.xi.ensure((size_t)p * (size_t)e.J * e.esz));
+    if (kind == CESX_MH_LANGEVIN) {            // what the lv_* kernels keep per chain (kernels_gpgrad.hip)
+        TRY_BUF(e.mh.lv_g.ensure((size_t)p * (size_t)e.J * 8)); TRY_BUF(e.mh.lv_gp.ensure((size_t)p * (size_t)e.J * 8));
+        TRY_BUF(e.mh.lv_gphi.ensure((size_t)p * (size_t)e.J * 8));
+        TRY_BUF(e.mh.lv_a.ensure((size_t)e.n * (size_t)e.J * 8)); TRY_BUF(e.mh.lv_b.ensure((size_t)e.n * (size_t)e.J * 8));
+    }
     TRY_BUF(e.mh.phi.ensure((size_t)e.J * 8)); TRY_BUF(e.mh.cnt.ensure((size_t)e.J * 8));
     e.mh.a = kind == CESX_MH_PCN ? std::sqrt(1.0 - beta * beta) : 1.0;
     e.mh.kind = kind;
@@ -914,6 +919,7 @@ int cesx_mh_start(cesx_handle h, const void* U, const void* G, void* stream) {
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U || !G) { e.err = "cesx_mh_start: null pointer"; return CESX_EINVAL; }
     if (e.mh.none() || !e.problem_set) { e.err = "cesx_mh_start: no proposal (cesx_mh_set_proposal after cesx_set_problem)"; return CESX_ESTATE; }
+    if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_mh_start: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }
     SET_DEVICE(e);
     FLUSH(e);
     TRY(mh_score(e, true, U, G, nullptr, nullptr, 0u, (hipStream_t)stream));
@@ -929,6 +935,7 @@ int cesx_mh_propose(cesx_handle h, uint64_t step_index, const void* U, const voi
     if (U == P) { e.err = "cesx_mh_propose: P must not alias U"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull) { e.err = "cesx_mh_propose: MH step indices are limited to 2^31"; return CESX_EINVAL; }
     if (e.mh.none()) { e.err = "cesx_mh_propose: cesx_mh_set_proposal has not been called"; return CESX_ESTATE; }
+    if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_mh_propose: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }
     SET_DEVICE(e);
     FLUSH(e);
     hipStream_t s = (hipStream_t)stream;
@@ -949,6 +956,7 @@ int cesx_mh_accept(cesx_handle h, uint64_t step_index, void* U, const void* P, c
     if (!U || !P || !GP) { e.err = "cesx_mh_accept: null pointer"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull) { e.err = "cesx_mh_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
     if (e.mh.none() || !e.mh.started) { e.err = "cesx_mh_accept: cesx_mh_start has not been called"; return CESX_ESTATE; }
+    if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_mh_accept: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }
     SET_DEVICE(e);
     FLUSH(e);
     TRY(mh_score(e, false, P, GP, U, logu, mh_step_word(step_index), (hipStream_t)stream));
@@ -1014,6 +1022,8 @@ int cesx_gp_set(cesx_handle h, const cesx_gp_desc* d) {
     TRY_BUF(e.gp.alpha.alloc(alpha.size() * 8)); TRY(upload(e, e.gp.alpha, alpha.data(), alpha.size() * 8));
     TRY_BUF(e.gp.Li.alloc(Li.size() * 8)); TRY(upload(e, e.gp.Li, Li.data(), Li.size() * 8));
     e.gp.Jt = Jt; e.gp.Jp = Jp; e.gp.li_len = li_len;
+    e.gp.matern12 = false;
+    for (int i = 0; i < n; ++i) e.gp.matern12 = e.gp.matern12 || d->family[i] == 1;
     e.gp.n = n;
     return CESX_OK;
 }
@@ -1138,6 +1148,7 @@ int cesx_gp_start(cesx_handle h, int mode, const void* U, const double* mean, co
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U) { e.err = "cesx_gp_start: null pointer"; return CESX_EINVAL; }
     if (e.mh.none() || !e.problem_set) { e.err = "cesx_gp_start: no proposal (cesx_mh_set_proposal after cesx_set_problem)"; return CESX_ESTATE; }
+    if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_gp_start: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }
     TRY(gp_check_mode(e, mode, mean, var));
     SET_DEVICE(e);
     FLUSH(e);
@@ -1156,6 +1167,7 @@ int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U, const 
     if (!U || !P) { e.err = "cesx_gp_accept: null pointer"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull) { e.err = "cesx_gp_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
     if (e.mh.none() || !e.mh.started) { e.err = "cesx_gp_accept: cesx_gp_start has not been called"; return CESX_ESTATE; }
+    if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_gp_accept: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }
     TRY(gp_check_mode(e, mode, mean, var));
     SET_DEVICE(e);
     FLUSH(e);
@@ -1175,6 +1187,7 @@ int cesx_gp_run(cesx_handle h, int mode, uint64_t step_index, int n_steps, int s
     if (step_index >= 0x80000000ull || step_index + (uint64_t)n_steps > 0x80000000ull) { e.err = "cesx_gp_run: MH step indices are limited to 2^31"; return CESX_EINVAL; }
     if (mode == CESX_GP_DENSE || mode == CESX_GP_PROJ) { e.err = "cesx_gp_run: CESX_GP_DENSE and CESX_GP_PROJ stay on the step path (cesx_mh_propose / cesx_gp_predict / cesx_gp_accept)"; return CESX_EINVAL; }
     if (mode != CESX_GP_GAMMA && mode != CESX_GP_VAR && mode != CESX_GP_GAMMA_VAR) { e.err = "cesx_gp_run: unknown likelihood mode"; return CESX_EINVAL; }
+    if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_gp_run: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }
     if (!e.problem_set || e.mh.none() || e.gp.none() || !e.mh.started) { e.err = "cesx_gp_run: needs cesx_set_problem, cesx_mh_set_proposal, cesx_gp_set and a start (cesx_gp_start / cesx_mh_start)"; return CESX_ESTATE; }
     if (mode != CESX_GP_GAMMA && e.whiten) { e.err = "cesx_gp_run: the variance modes need a diagonal Gamma"; return CESX_EINVAL; }
     if (e.gp.n != e.n) { e.err = "cesx_gp_run: the emulator's n_gp differs from n_obs"; return CESX_EINVAL; }
@@ -1183,6 +1196,89 @@ int cesx_gp_run(cesx_handle h, int mode, uint64_t step_index, int n_steps, int s
     FLUSH(e);
     TRY(launch_gp_run(e, mode, step_index, n_steps, stride, nugget != 0, U, trace, xi, logu, (hipStream_t)stream));
     e.mh.steps += (unsigned long long)n_steps;
+    return CESX_OK;
+}
+
+int cesx_gp_predict_grad(cesx_handle h, const void* X, double* mean, double* var, double* dmean, double* dvar, int nugget,
+                         void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!X || !mean || !dmean || (var == nullptr) != (dvar == nullptr)) { e.err = "cesx_gp_predict_grad: null pointer (var_dev and dvar_dev go together)"; return CESX_EINVAL; }
+    if (e.gp.none()) { e.err = "cesx_gp_predict_grad: cesx_gp_set has not been called"; return CESX_ESTATE; }
+    if (e.gp.matern12) { e.err = "cesx_gp_predict_grad: a Matern12 kernel is not differentiable at its training points"; return CESX_EUNSUPPORTED; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    return launch_gp_predict_grad(e, X, mean, var, dmean, dvar, nugget != 0, (hipStream_t)stream);
+}
+
+// ---- the Langevin step of gp_mh(chains=, update='langevin') (kernels_gpgrad.hip) ----
+
+// what every cesx_gp_langevin_* call needs before it looks at its own arguments; `started`: a cesx_gp_langevin_start too
+static int langevin_check_state(Engine& e, bool started) {
+    if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_gp_langevin: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
+    if (e.gp.none()) { e.err = "cesx_gp_langevin: cesx_gp_set has not been called"; return CESX_ESTATE; }
+    if (started && !e.mh.started) { e.err = "cesx_gp_langevin: cesx_gp_langevin_start has not been called"; return CESX_ESTATE; }
+    return CESX_OK;
+}
+
+static int langevin_check_mode(Engine& e, int mode, const double* mean, const double* var, const double* dmean, const double* dvar) {
+    if (mode == CESX_GP_DENSE || mode == CESX_GP_PROJ) { e.err = "cesx_gp_langevin: CESX_GP_DENSE and CESX_GP_PROJ have no gradient on the device"; return CESX_EINVAL; }
+    if (mode != CESX_GP_GAMMA && mode != CESX_GP_VAR && mode != CESX_GP_GAMMA_VAR) { e.err = "cesx_gp_langevin: unknown likelihood mode"; return CESX_EINVAL; }
+    if (!mean || !dmean || (mode != CESX_GP_GAMMA && (!var || !dvar))) { e.err = "cesx_gp_langevin: null pointer"; return CESX_EINVAL; }
+    if (mode != CESX_GP_GAMMA && e.whiten) { e.err = "cesx_gp_langevin: the variance modes need a diagonal Gamma"; return CESX_EINVAL; }
+    if (e.gp.n != e.n) { e.err = "cesx_gp_langevin: the emulator's n_gp differs from n_obs"; return CESX_EINVAL; }
+    return CESX_OK;
+}
+
+int cesx_gp_langevin_start(cesx_handle h, int mode, const void* U, const double* mean, const double* var, const double* dmean,
+                           const double* dvar, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(langevin_check_state(e, false));
+    if (!U) { e.err = "cesx_gp_langevin_start: null pointer"; return CESX_EINVAL; }
+    TRY(langevin_check_mode(e, mode, mean, var, dmean, dvar));
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_gp_langevin(e, 0, mode, U, mean, var, dmean, dvar, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream));
+    e.mh.started = true;
+    e.mh.lv_proposed = false;
+    e.mh.steps = 0;
+    return CESX_OK;
+}
+
+int cesx_gp_langevin_propose(cesx_handle h, uint64_t step_index, const void* U, const void* xi, void* P, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(langevin_check_state(e, true));
+    if (!U || !P) { e.err = "cesx_gp_langevin_propose: null pointer"; return CESX_EINVAL; }
+    if (U == P) { e.err = "cesx_gp_langevin_propose: P must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_gp_langevin_propose: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    hipStream_t s = (hipStream_t)stream;
+    // the block stays in engine memory: the accept step needs it again
+    if (xi) CESX_HIP(hipMemcpyAsync(e.mh.xi, xi, (size_t)e.p * (size_t)e.J * e.esz, hipMemcpyDeviceToDevice, s));
+    else TRY(launch_noise(e, mh_step_word(step_index), e.mh.xi, s));
+    TRY(launch_gp_langevin(e, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, const_cast<void*>(U), P, nullptr, 0u, s));
+    e.mh.lv_proposed = true;
+    return CESX_OK;
+}
+
+int cesx_gp_langevin_accept(cesx_handle h, int mode, uint64_t step_index, void* U, const void* P, const double* mean,
+                            const double* var, const double* dmean, const double* dvar, const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(langevin_check_state(e, true));
+    if (!e.mh.lv_proposed) { e.err = "cesx_gp_langevin_accept: no cesx_gp_langevin_propose since the start or the last accept"; return CESX_ESTATE; }
+    if (!U || !P) { e.err = "cesx_gp_langevin_accept: null pointer"; return CESX_EINVAL; }
+    if (U == P) { e.err = "cesx_gp_langevin_accept: P must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_gp_langevin_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    TRY(langevin_check_mode(e, mode, mean, var, dmean, dvar));
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_gp_langevin(e, 2, mode, P, mean, var, dmean, dvar, U, nullptr, logu, mh_step_word(step_index), (hipStream_t)stream));
+    e.mh.lv_proposed = false;
+    ++e.mh.steps;
     return CESX_OK;
 }
 
@@ -1727,6 +1823,7 @@ int cesx_mh_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride,
     if (!U) { e.err = "cesx_mh_run_map: null pointer"; return CESX_EINVAL; }
     if (n_steps < 1 || stride < 1) { e.err = "cesx_mh_run_map: n_steps and stride must be >= 1"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull || step_index + (uint64_t)n_steps > 0x80000000ull) { e.err = "cesx_mh_run_map: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_mh_run_map: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }
     if (!e.problem_set || e.mh.none() || !e.mh.started) { e.err = "cesx_mh_run_map: cesx_mh_start has not been called (after cesx_set_problem and cesx_mh_set_proposal)"; return CESX_ESTATE; }
     if (!e.mp.fused()) { e.err = "cesx_mh_run_map: no map of a fused kind is installed (cesx_map_set: CESX_MAP_ELLIPTIC or CESX_MAP_BANANA)"; return CESX_ESTATE; }
     SET_DEVICE(e);

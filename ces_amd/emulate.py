@@ -243,6 +243,37 @@ class GPR(object):
         mean, var = self.predict_f(Xnew)
         return mean, var + self.likelihood.variance
 
+    def predict_f_grad(self, Xnew):
+        """``predict_f`` and the gradients of its mean and variance with respect to ``Xnew``: ``(mean (N, 1), var (N, 1),
+        dmean (N, d), dvar (N, d))`` (build-only; include/cesx.h, cesx_gp_predict_grad, restated).  With h(r) = f'(r) / r
+        (``dfr_over_r``) and beta = L^{-T} L^{-1} k*:
+            dk_t / dx = variance h(r_t) (x - X_t) / l^2,  dmean = sum_t alpha_t dk_t / dx + dm / dx,  dvar = -2 sum_t beta_t dk_t / dx.
+        A Matern12 kernel is not differentiable at the training points: ``ValueError``."""
+        if isinstance(self.kern, Matern12):
+            raise ValueError("predict_f_grad: a Matern12 kernel is not differentiable at its training points; train the "
+                             "emulator with RBF, Matern32 or Matern52")
+        mf = self.mean_function
+        if not isinstance(mf, (Zero, Constant, Linear)):
+            raise ValueError("predict_f_grad takes the Zero, Constant and Linear mean functions")
+        Xnew = np.array(Xnew, dtype=np.float64, ndmin=2)
+        mean, var = self.predict_f(Xnew)
+        L, alpha = self._factor()
+        d = self.kern._scaled_diff(self.X, Xnew)                        # (J_t, N, d): (X_t - x) / l
+        r = np.sqrt((d * d).sum(axis=2))
+        W = np.linalg.solve(L, self.kern.variance * self.kern.f(r))
+        beta = np.linalg.solve(L.T, W)                                  # (J_t, N)
+        dk = (self.kern.variance * self.kern.dfr_over_r(r))[:, :, None] * (-d) / self.kern._ls()
+        dmean = np.einsum("t,tnq->nq", alpha[:, 0], dk)
+        if isinstance(mf, Linear):
+            dmean = dmean + np.asarray(mf.A, dtype=np.float64).reshape(1, -1)
+        dvar = -2.0 * np.einsum("tn,tnq->nq", beta, dk)
+        return mean, var, dmean, dvar
+
+    def predict_y_grad(self, Xnew):
+        """``predict_y`` with the gradients of ``predict_f_grad``: the nugget adds nothing to a gradient."""
+        mean, var, dmean, dvar = self.predict_f_grad(Xnew)
+        return mean, var + self.likelihood.variance, dmean, dvar
+
     def compute_log_likelihood(self):
         return self.log_marginal_likelihood()
 
@@ -536,7 +567,10 @@ def scale_ensemble(enka, factor=2.):
 
 
 def predict_gps(enka, X, mute_bar=True, **kwargs):
-    """ces/emulate.py:19-80.  X: (n_points, d).  Build-only ``device=True``: the GPs on the GPU (module docstring)."""
+    """ces/emulate.py:19-80.  X: (n_points, d).  Build-only ``device=True``: the GPs on the GPU (module docstring).
+    Build-only ``grad=True`` (host and ``device=True``): ``[gpmeans, gpvars, dmeans, dvars]``, the gradients
+    (n_gp, n_points, d) with respect to the unscaled X, through ``enka.scale``; the models need ``predict_f_grad`` /
+    ``predict_y_grad`` (this package's GPR); with ``pca_tools`` or ``separable`` it raises ``ValueError``."""
     try:
         getattr(enka, 'gpmodels')
     except AttributeError:
@@ -548,8 +582,16 @@ def predict_gps(enka, X, mute_bar=True, **kwargs):
     else:
         gpmodels = kwargs.get('gpmodels', None)
 
+    if kwargs.get('grad', False):
+        for name in ('pca_tools', 'separable'):
+            if kwargs.get(name, None) not in (None, False):
+                raise ValueError("predict_gps(grad=True): %s has no gradient path (the gradients are those of the GP rows)" % name)
+
     if kwargs.get('device', False):
         return _predict_gps_device(enka, X, gpmodels, kwargs)
+
+    if kwargs.get('grad', False):
+        return _predict_gps_grad(enka, X, gpmodels, kwargs)
 
     if kwargs.get('separable', False):
         gpmeans = np.empty(shape=(kwargs.get('model').n_obs, 1))
@@ -585,6 +627,26 @@ def predict_gps(enka, X, mute_bar=True, **kwargs):
             gpvars = pca_tools['VD_k'].dot(np.diag(gpvars.flatten())).dot(pca_tools['VD_k'].T)
 
     return [gpmeans, gpvars]
+
+
+def _predict_gps_grad(enka, X, gpmodels, kwargs):
+    """The host path of ``predict_gps(grad=True)``: the chain rule through ``enka.scale`` is d/dX = S^{-T} d/dXs."""
+    X = np.asarray(X, dtype=np.float64)
+    name = 'predict_y_grad' if kwargs.get('nugget', True) else 'predict_f_grad'
+    if not all(hasattr(m, name) for m in gpmodels):
+        raise ValueError("predict_gps(grad=True) needs models with %s (ces_amd.emulate.GPR)" % name)
+    if hasattr(enka, 'scaled'):
+        Si = np.linalg.solve(enka.scale['cov'], np.eye(X.shape[1]))
+        Xs = np.linalg.solve(enka.scale['cov'], X.T - enka.scale['mean']).T
+    else:
+        Si, Xs = None, X
+    gpmeans, gpvars = np.empty((len(gpmodels), len(X))), np.empty((len(gpmodels), len(X)))
+    dmeans, dvars = np.empty((len(gpmodels),) + X.shape), np.empty((len(gpmodels),) + X.shape)
+    for ii, model in enumerate(gpmodels):
+        mean, var, dm, dv = getattr(model, name)(Xs)
+        gpmeans[ii], gpvars[ii] = mean.flatten(), var.flatten()
+        dmeans[ii], dvars[ii] = (dm, dv) if Si is None else (dm @ Si, dv @ Si)
+    return [gpmeans, gpvars, dmeans, dvars]
 
 
 def scale_gppreds(gpmeans, gpvars, Gmean, Gstd):
@@ -707,6 +769,15 @@ def _predict_gps_device(enka, X, gpmodels, kwargs):
                          device=kwargs.get('device_index', 0))
     eng.gp_set(img)
     Xd = eng.to_device(np.ascontiguousarray(X.T), p, "gp_X")
+    if kwargs.get('grad', False):
+        try:
+            mean, var, dm, dv = eng.gp_predict_grad(Xd, nugget=kwargs.get('nugget', True), var=True)
+        except _engine.CesxError as exc:
+            if exc.code != _engine.EUNSUPPORTED:
+                raise
+            raise ValueError("predict_gps(grad=True): %s" % exc)
+        return [mean.cpu().numpy(), var.cpu().numpy(), np.ascontiguousarray(dm.cpu().numpy().transpose(0, 2, 1)),
+                np.ascontiguousarray(dv.cpu().numpy().transpose(0, 2, 1))]
     mean, var = eng.gp_predict(Xd, nugget=kwargs.get('nugget', True), var=True)
     gpmeans, gpvars = mean.cpu().numpy(), var.cpu().numpy()
     if kwargs.get('pca_tools', None) is not None:          # the back-projection of the host path (ces/emulate.py:74-77)

@@ -18,8 +18,8 @@ OK, EINVAL, ENOTPD, EHIP, ESTATE, EUNSUPPORTED, ENOCONV = 0, 1, 2, 3, 4, 5, 6
 F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
-ABI_VERSION = 9
-MH_KINDS = {None: 0, "pCN": 1}         # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN
+ABI_VERSION = 10
+MH_KINDS = {None: 0, "pCN": 1, "langevin": 2}     # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN; build-only: CESX_MH_LANGEVIN
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
            "cesx_step", "cesx_result", "cesx_moments_len", "cesx_colsum", "cesx_set_shift",
@@ -32,6 +32,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_debug_warm_inverse", "cesx_debug_update_form", "cesx_comm_count",
            "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats", "cesx_mh_phi",
            "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_run", "cesx_gp_dense_set", "cesx_gp_proj_set",
+           "cesx_gp_predict_grad", "cesx_gp_langevin_start", "cesx_gp_langevin_propose", "cesx_gp_langevin_accept",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_darcy_set_streamed", "cesx_darcy_workspace_bytes", "cesx_lorenz_set", "cesx_lorenz_apply",
            "cesx_lorenz_three_set", "cesx_lorenz_three_apply", "cesx_map_set", "cesx_map_apply", "cesx_mh_run_map",
@@ -277,6 +278,10 @@ def load_library(path=None):
     lib.cesx_gp_dense_set.argtypes =[vp, C.POINTER(GpDenseDesc)]
     lib.cesx_gp_proj_set.argtypes = [vp, C.POINTER(GpProjDesc)]
     lib.cesx_mh_phi.argtypes = [vp, dp]
+    lib.cesx_gp_predict_grad.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.cesx_gp_langevin_start.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gp_langevin_propose.argtypes = [vp, u64, vp, vp, vp, vp]
+    lib.cesx_gp_langevin_accept.argtypes = [vp, i32, u64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cesx_gpfit_set.argtypes = [vp, C.POINTER(GpFitDesc)]
     lib.cesx_gpfit_ntheta.argtypes = [vp]
     lib.cesx_gpfit_eval.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
@@ -1069,6 +1074,58 @@ class Engine:
                 raise CesxError(rc, self.lib.cesx_last_error(self._h).decode())
             self._check(rc)
         self._keep_gp_run = (U, trace, xi, logu)
+
+    def gp_predict_grad(self, X, nugget=True, var=True, out=None):
+        """(mean, var, dmean, dvar): ``gp_predict`` with the gradients of every GP row with respect to x, float64 device
+        tensors (n_gp, p, J) (cesx_gp_predict_grad); mean and var are ``gp_predict``'s bit for bit.  var=False: the
+        mean-only mode, var and dvar are None.  ``out``: a (mean, var, dmean, dvar) tuple to write into.  An emulator with
+        a Matern12 GP raises ``CesxError`` with code EUNSUPPORTED."""
+        mean, v, dm, dv = out if out is not None else (None, None, None, None)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)      # noqa: E731
+        mean = new(self.gp_n, self.J) if mean is None else mean
+        dm = new(self.gp_n, self.p, self.J) if dm is None else dm
+        if var:
+            v = new(self.gp_n, self.J) if v is None else v
+            dv = new(self.gp_n, self.p, self.J) if dv is None else dv
+        with torch.cuda.device(self.device):
+            rc = self.lib.cesx_gp_predict_grad(self._h, X.data_ptr(), mean.data_ptr(), v.data_ptr() if var else None,
+                                               dm.data_ptr(), dv.data_ptr() if var else None, 1 if nugget else 0,
+                                               self._stream())
+            if rc == EUNSUPPORTED:            # (Matern12, not the reference's missing LM_procedure of _check)
+                raise CesxError(rc, self.lib.cesx_last_error(self._h).decode())
+            self._check(rc)
+        self._keep_gp_g = (X, mean, v, dm, dv)
+        return mean, (v if var else None), dm, (dv if var else None)
+
+    def gp_langevin_start(self, mode, U, mean, var, dmean, dvar):
+        """phi and g = S^T grad phi of the current states U from their GP rows and gradients (``gp_predict_grad`` at U) in
+        likelihood mode ``mode`` ('gamma', 'var', 'gamma_var'); counters cleared (cesx_gp_langevin_start)."""
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_langevin_start(self._h, GP_MODES[mode], U.data_ptr(), ptr(mean), ptr(var), ptr(dmean),
+                                                        ptr(dvar), self._stream()))
+        self._keep_lv_s = (U, mean, var, dmean, dvar)
+
+    def gp_langevin_propose(self, step_index, U, xi=None, out=None):
+        """P = U + S (xi - g(U) / 2) (cesx_gp_langevin_propose); xi None: drawn on device in the MH counter domain of
+        step_index.  The engine keeps the block for ``gp_langevin_accept``."""
+        out = self.empty(self.p) if out is None else out
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_langevin_propose(self._h, int(step_index), U.data_ptr(),
+                                                          None if xi is None else xi.data_ptr(), out.data_ptr(), self._stream()))
+        self._keep_lv_p = (U, xi, out)
+        return out
+
+    def gp_langevin_accept(self, mode, step_index, U, P, mean, var, dmean, dvar, logu=None):
+        """phi(P) and g(P) from the rows and gradients at P, the test with the Langevin correction, U := P on the accepted
+        columns (cesx_gp_langevin_accept); logu as in ``gp_accept``."""
+        if logu is not None:
+            assert logu.dtype == torch.float64 and logu.numel() == self.J and logu.is_contiguous()
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_langevin_accept(self._h, GP_MODES[mode], int(step_index), U.data_ptr(), P.data_ptr(),
+                                                         ptr(mean), ptr(var), ptr(dmean), ptr(dvar), ptr(logu), self._stream()))
+        self._keep_lv_a = (U, P, mean, var, dmean, dvar, logu)
 
     # -- GP training: the batched likelihood and gradient (include/cesx.h, cesx_gpfit_*; ces_amd/emulate.py drives it) --
     def gpfit_set(self, X, Y, family, ard=True, mean="zero"):

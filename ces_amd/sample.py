@@ -70,6 +70,16 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          ``marginal_density`` and ``marginal_quantiles`` read it; ``plots.find_levels(H=hist2d[k])`` gives
                          the contour levels.  The chains, ``self.summary`` and ``self.samples`` are as without it.  A call
                          without ``marginals=`` removes ``self.marginals``: the attribute is always the last call's.
+  kwarg ``update='langevin'``  gp_mh only, on the host (one chain) and with ``chains=M``: a preconditioned Metropolis-adjusted
+                         Langevin proposal from the closed-form gradients of the GPs (``emulate.GPR.predict_f_grad``; on the
+                         device ``cesx_gp_predict_grad`` and ``cesx_gp_langevin_*``, kernels_gpgrad.hip).  With S the scales of
+                         the random walk -- so ``delta`` is the Langevin step --, g(u) = S^T grad phi(u) and xi ~ N(0, I):
+                         P = U + S (xi - g(U) / 2), accepted when
+                         log u < phi(U) - phi(P) + |xi|^2 / 2 - |xi - (g(U) + g(P)) / 2|^2 / 2.  The draws per step are the random
+                         walk's (xi, then u).  Likelihoods: Gamma (dense or diagonal), diag(gvars) and diag(Gamma) +
+                         diag(gvars).  ``fused=True``, ``pca_tools``, ``separable``, emulators without gradients and Matern12
+                         kernels raise ``ValueError``; so does ``model_mh``: no device map has a Jacobian yet.  ``summary=``,
+                         ``burn=``, ``marginals=``, ``start=``, ``noise=``, resume and ``trace_stride`` work as for the random walk.
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -317,6 +327,8 @@ class MCMC(object):
                              % (kwargs.get("sigma_form"),))
         _host_has_no_summary(kwargs)
         from . import emulate
+        if kwargs.get("update", None) == "langevin":      # build-only
+            return self._gp_mh_langevin_host(enka, n_mcmc, prior, delta, enka_scaling, kwargs)
         if enka_scaling:
             scales = delta * np.linalg.cholesky(np.cov(enka.Ustar))
         else:
@@ -370,6 +382,87 @@ class MCMC(object):
                 accept += 1.
             samples.append(current)
 
+        self.samples = np.array(samples).T
+        self.accept = accept / n_mcmc
+
+    @staticmethod
+    def _langevin_refusals(kwargs, prior):
+        """What ``gp_mh(update='langevin')`` cannot do, host and device alike: every refusal is a ValueError with the reason."""
+        if kwargs.get("pca_tools", None) is not None:
+            raise ValueError("update='langevin': pca_tools has no gradient path (the dense and the projected Sigma are not "
+                             "differentiated); run the random walk (update=None) with pca_tools")
+        if kwargs.get("separable", False):
+            raise ValueError("update='langevin': separable predicts one point at a time and has no gradient path")
+        if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
+            raise ValueError("update='langevin': the prior must expose .mean and .cov (its gradient is cov^{-1} (u - mean))")
+        Gamma = kwargs.get("Gamma", None)
+        if Gamma is not None and kwargs.get("noise_compounded", False):
+            G = np.asarray(Gamma, dtype=np.float64)
+            if np.any(G != np.diag(np.diag(G))):
+                raise ValueError("update='langevin': noise_compounded with a dense Gamma has no gradient path (Gamma + "
+                                 "diag(gvars) would be factored per state); pass a diagonal Gamma")
+
+    @staticmethod
+    def langevin_phi_grad(mean, var, dmean, dvar, u, y, Gamma, compounded, prior_mean, prior_cov):
+        """phi (up to the prior's constant) and grad phi at the states ``u`` (N, p) from the GP rows ``mean``, ``var`` (n, N)
+        and their gradients ``dmean``, ``dvar`` (n, N, p): the formulas of include/cesx.h (cesx_gp_langevin_*) in numpy,
+        vectorised over the states.  ``Gamma`` None: Sigma = diag(var); ``compounded``: diag(Gamma) + diag(var); else Gamma."""
+        d = mean - np.asarray(y, dtype=np.float64).reshape(-1, 1)                   # (n, N)
+        if Gamma is not None and not compounded:
+            a = np.linalg.solve(np.asarray(Gamma, dtype=np.float64), d)
+            phi = 0.5 * (d * a).sum(axis=0)
+            grad = np.einsum("in,inq->nq", a, dmean)
+        else:
+            v = var if Gamma is None else var + np.diag(np.asarray(Gamma, dtype=np.float64)).reshape(-1, 1)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                phi = 0.5 * (d * d / v + np.log(v)).sum(axis=0)
+                a, b = d / v, 0.5 * (1.0 / v - d * d / (v * v))
+            grad = np.einsum("in,inq->nq", a, dmean) + np.einsum("in,inq->nq", b, dvar)
+        w = np.linalg.solve(np.asarray(prior_cov, dtype=np.float64), (u - np.asarray(prior_mean, dtype=np.float64).reshape(1, -1)).T)
+        phi = phi + 0.5 * ((u - np.asarray(prior_mean, dtype=np.float64).reshape(1, -1)).T * w).sum(axis=0)
+        return phi, grad + w.T
+
+    @staticmethod
+    def langevin_correction(xi, g_current, g_proposal):
+        """log q(U | P) - log q(P | U) of the proposal P = U + S (xi - g(U) / 2), the short way: no S^{-1}, because
+        S^{-1} (P - U + S g(U) / 2) = xi by construction.  The last axis is the parameter axis."""
+        back = xi - 0.5 * (g_current + g_proposal)
+        return 0.5 * (xi * xi).sum(axis=-1) - 0.5 * (back * back).sum(axis=-1)
+
+    def _gp_mh_langevin_host(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
+        """``gp_mh(update='langevin')`` on the host, one chain (module docstring): the restatement the device is held to.
+        The scales, the start, the resume (phi and g of the resumed state) and the draws per step are the random walk's."""
+        from . import emulate
+        self._langevin_refusals(kwargs, prior)
+        p = enka.p
+        scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(p, p)) if enka_scaling else delta * np.eye(p)
+        Gamma, compounded = kwargs.get("Gamma", None), bool(kwargs.get("noise_compounded", False))
+
+        def score(u):
+            try:
+                rows = emulate.predict_gps(enka, u.reshape(1, -1), gpmodels=kwargs.get("gpmodels", None),
+                                           nugget=kwargs.get("nugget", True), grad=True)
+            except ValueError as exc:
+                raise ValueError("update='langevin': %s" % exc)
+            phi, grad = self.langevin_phi_grad(*rows, u.reshape(1, -1), self.y_obs, Gamma, compounded, prior.mean, prior.cov)
+            return phi[0], scales.T @ grad[0]
+
+        current = enka.Ustar.mean(axis=1)
+        if hasattr(self, "samples"):                      # resume: before phi, as gp_mh's random walk
+            samples = list(self.samples.T)
+            current = samples[-1]
+        else:
+            samples = [current.flatten()]
+        accept = 0.
+        phi_current, g_current = score(current)
+        for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
+            xi = np.random.normal(0, 1, p)
+            proposal = current + np.matmul(scales, xi - 0.5 * g_current)
+            phi_proposal, g_proposal = score(proposal)
+            if np.log(np.random.uniform()) < phi_current - phi_proposal + self.langevin_correction(xi, g_current, g_proposal):
+                current, phi_current, g_current = np.copy(proposal), phi_proposal, g_proposal
+                accept += 1.
+            samples.append(current)
         self.samples = np.array(samples).T
         self.accept = accept / n_mcmc
 
@@ -471,7 +564,7 @@ class MCMC(object):
         return self._mh_eng
 
     def _mh_device(self, enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi, fused=False,
-                   fused_work=0):
+                   fused_work=0, langevin=False):
         """M = kwargs['chains'] chains on the engine: what ``model_mh(chains=)`` and ``gp_mh(chains=)`` have in common.
 
         Gamma                    the data covariance handed to ``set_problem``
@@ -480,7 +573,9 @@ class MCMC(object):
                                  engine, counters cleared), ``score_accept(step, U, P, logu)`` (phi of P, the test, U := P
                                  where it passes) and ``run_steps(step, K, U, stride, trace, xi, logu)`` (K steps in one
                                  launch: ``eng.mh_run_map`` for a map, ``eng.gp_run`` for the emulator; None where the
-                                 sampler has no fused kernel)
+                                 sampler has no fused kernel) and, optionally, a fourth hook ``propose(step, U, xi, P)`` that
+                                 stands in for ``eng.mh_propose`` on the step path (the Langevin proposal reads the chains' g)
+        langevin                 the sampler takes ``update='langevin'`` (gp_mh; model_mh has no Jacobian on the device)
         resume_keeps_start_phi   the reference's model_mh scores the START point before it looks for ``self.samples`` and
                                  keeps that phi for the resumed states (ces/sample.py:131-163); its gp_mh scores the resumed
                                  states (:31-39).  True: the first, for ``noise='numpy'`` (``noise='device'`` re-scores the
@@ -504,7 +599,10 @@ class MCMC(object):
         if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
             raise ValueError("chains=: the prior must expose .mean and .cov (a frozen scipy.stats.multivariate_normal does)")
         update = kwargs.get("update", None)
-        if update not in (None, "pCN"):
+        if update == "langevin" and not langevin:
+            raise ValueError("chains=: update='langevin' needs the gradient of phi, and no device map has a Jacobian yet; "
+                             "gp_mh(chains=, update='langevin') differentiates the emulator")
+        if update not in (None, "pCN", "langevin"):
             raise ValueError("chains=: unknown update %r (None or 'pCN')" % (update,))
         if self.noise not in ("numpy", "device"):
             raise ValueError("noise must be 'numpy' or 'device', got %r" % (self.noise,))
@@ -547,7 +645,7 @@ class MCMC(object):
         eng = self._mh_engine(p, n, M)
         eng.set_problem(np.asarray(self.y_obs, dtype=np.float64).reshape(n), Gamma, mu, cov, mu)
         eng.mh_set_proposal(update, scales, kwargs.get("beta", 0.5))
-        score_start, score_accept, run_steps = bind(eng, M)
+        score_start, score_accept, run_steps, propose = (tuple(bind(eng, M)) + (None,))[:4]
         P = eng.empty(p)
         self.fused_launches = 0
 
@@ -612,7 +710,10 @@ class MCMC(object):
                     logu = np.log(np.random.uniform(size=M))  # :188 / :98
                     xi_t = eng.to_device(xi, p, "mh_xi")
                     logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
-                eng.mh_propose(step, U, xi=xi_t, out=P)
+                if propose is None:
+                    eng.mh_propose(step, U, xi=xi_t, out=P)
+                else:
+                    propose(step, U, xi_t, P)
                 score_accept(step, U, P, logu_t)
                 if summary:
                     if (k + 1) % stride == 0 and k + 1 > burn:
@@ -736,6 +837,12 @@ class MCMC(object):
         if fused and kwargs.get("pca_tools", None) is not None:
             raise ValueError("fused=True: the dense and the projected Sigma of pca_tools stay on the step path (the fused chain "
                              "kernel scores Gamma, diag(gvars) and diag(Gamma) + diag(gvars)); pass fused=None or False")
+        langevin = kwargs.get("update", None) == "langevin"
+        if langevin:
+            if fused:
+                raise ValueError("fused=True: update='langevin' runs on the step path (the fused chain kernel has no gradient "
+                                 "phase); pass fused=None or False")
+            self._langevin_refusals(kwargs, prior)
         fused = self.GP_FUSED_DEFAULT if fused is None else bool(fused)
         if kwargs.get("separable", False):
             raise ValueError("chains=: separable predicts one point at a time" + host)
@@ -794,6 +901,10 @@ class MCMC(object):
             img = emulate.device_image(enka, gpmodels)
         except ValueError as exc:
             raise ValueError("chains=: %s" % exc)
+        if langevin and np.any(np.asarray(img["family"]) == 1):
+            raise ValueError("chains=, update='langevin': GP %d has a Matern12 kernel, which is not differentiable at its "
+                             "training points; train the emulator with RBF, Matern32 or Matern52"
+                             % int(np.nonzero(np.asarray(img["family"]) == 1)[0][0]))
 
         def scales_of(update):                            # (:23-26; pCN takes the same scales)
             return delta * np.linalg.cholesky(np.cov(enka.Ustar)) if enka_scaling else delta * np.eye(p)
@@ -808,6 +919,21 @@ class MCMC(object):
             rows = lambda: torch.empty((n_gp, M), dtype=torch.float64, device=eng.device)    # noqa: E731
             mean_u, mean_p = rows(), rows()
             var_u, var_p = (rows(), rows()) if want_var else (None, None)
+            if langevin:                                  # the rows and their gradients of one state at a time: the chains' own g stays in the engine
+                grads = lambda: torch.empty((n_gp, p, M), dtype=torch.float64, device=eng.device)    # noqa: E731
+                out = (mean_p, var_p, grads(), grads() if want_var else None)
+
+                def lv_start(U):
+                    eng.gp_predict_grad(U, nugget=nugget, var=want_var, out=out)
+                    eng.gp_langevin_start(mode, U, *out)
+
+                def lv_propose(step, U, xi, P):
+                    eng.gp_langevin_propose(step, U, xi=xi, out=P)
+
+                def lv_accept(step, U, P, logu):
+                    eng.gp_predict_grad(P, nugget=nugget, var=want_var, out=out)
+                    eng.gp_langevin_accept(mode, step, U, P, *out, logu=logu)
+                return lv_start, lv_accept, None, lv_propose
 
             def score_start(U):
                 eng.gp_predict(U, nugget=nugget, var=want_var, out=(mean_u, var_u))
@@ -832,4 +958,4 @@ class MCMC(object):
         Jp = (int(img["Jt"]) + 15) // 16 * 16
         work = int(kwargs["chains"]) * n_gp * Jp * (Jp // 2 + p + 8) if fused else 0
         self._mh_device(enka, n_mcmc, prior, kwargs, G, scales_of, bind, resume_keeps_start_phi=False, fused=fused,
-                        fused_work=work)
+                        fused_work=work, langevin=True)

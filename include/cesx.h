@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CESX_ABI_VERSION 9
+#define CESX_ABI_VERSION 10
 
 /* status codes */
 #define CESX_OK            0
@@ -515,7 +515,10 @@ int cesx_lorenz_three_apply(cesx_handle h, const void* U_dev, const double* W_in
    (cesx_mh_set_proposal again, then cesx_mh_start). */
 #define CESX_MH_RW   0
 #define CESX_MH_PCN  1
-/* The proposal: kind CESX_MH_RW | CESX_MH_PCN, S_host the p x p LOWER-triangular scale matrix (row-major fp64, computed by the
+#define CESX_MH_LANGEVIN 2   /* the preconditioned Langevin proposal of cesx_gp_langevin_* (below); S as for RW, beta ignored.  With
+                                this kind cesx_mh_start / _propose / _accept, cesx_gp_start / _accept, cesx_gp_run and
+                                cesx_mh_run_map return CESX_EINVAL and launch nothing: no map has a Jacobian on the device. */
+/* The proposal: kind CESX_MH_RW | CESX_MH_PCN | CESX_MH_LANGEVIN, S_host the p x p LOWER-triangular scale matrix (row-major fp64, computed by the
    caller exactly as ces/sample.py:122-129 does; CESX_EINVAL when an entry above the diagonal is nonzero), beta the pCN
    parameter (0 < beta <= 1; ignored for RW).  Needs the problem (cesx_set_problem). */
 int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S_host, double beta);
@@ -716,6 +719,53 @@ int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev, co
    (these stay on the step path), a variance mode with a dense Gamma, or n_gp != n_obs.  None of these launches anything. */
 int cesx_gp_run(cesx_handle h, int mode, uint64_t step_index, int n_steps, int stride, int nugget, void* U_dev,
                 void* trace_dev, const void* xi_dev, const double* logu_dev, void* stream);
+/* cesx_gp_predict with the gradients of every GP row with respect to the input x (kernels_gpgrad.hip, gp_grad_kernel: the
+   tile of cesx_gp_predict -- one workgroup per (GP, 32 chains), W = L^{-1} k* on v_mfma_f64_16x16x4_f64 -- then a second
+   product beta = L^{-T} W from the same packed L^{-1} image read transposed; K^{-1} is never formed).  With h(r) = f'(r) / r
+   (RBF -exp(-r^2/2), Matern32 -3 exp(-sqrt(3) r), Matern52 -(5/3)(1 + sqrt(5) r) exp(-sqrt(5) r): finite at r = 0):
+       dk_t / dz  = sigma_i^2 h(r_t) (z - Z_it)
+       grad_z mean_i = sum_t alpha_it dk_t / dz + w_i,   grad_z var_i = -2 sum_t beta_t dk_t / dz,   grad_x = A_i^T grad_z
+   (the nugget adds nothing to a gradient).  mean_dev and var_dev as cesx_gp_predict writes them, BIT FOR BIT; dmean_dev and
+   dvar_dev fp64 [n_gp][p][J_local].  var_dev and dvar_dev both NULL is the mean-only mode: no triangular product; one of them
+   NULL alone is CESX_EINVAL.  The sums run on the vector ALU in a fixed order, no atomics: runs are bit-reproducible.
+   A tile keeps z, both z-gradients and two J_p x 32 panels (K* then beta, W): (2 J_p + 3 p) 256 bytes next to the 8 KiB of
+   partial sums (J_p + 3 p in the mean-only mode).  Up to 2 J_p + 3 p <= 608 that is LDS; beyond it the tiles live in the
+   global workspace of cesx_gp_predict, one slot per workgroup, and the (GP, tile) pairs go in as many launches of `stream`
+   as the slots need: every J_t that cesx_gp_predict takes works.
+   CESX_ESTATE without cesx_gp_set; CESX_EUNSUPPORTED for an emulator with a Matern12 GP (no gradient at a training point).
+   Neither launches anything. */
+int cesx_gp_predict_grad(cesx_handle h, const void* X_dev, double* mean_dev, double* var_dev, double* dmean_dev,
+                         double* dvar_dev, int nugget, void* stream);
+/* MCMC.gp_mh(chains=M, update='langevin'): a preconditioned Metropolis-adjusted Langevin step on the emulated posterior, every
+   column a chain, on the step path.  Proposal kind CESX_MH_LANGEVIN (cesx_mh_set_proposal): S the lower-triangular scale of
+   the random walk, so the caller's delta is the Langevin step.  With phi as for cesx_gp_start in mode CESX_GP_GAMMA, _VAR or
+   _GAMMA_VAR, d = mean - y and
+       grad phi(u) = sum_i (a_i grad mean_i + b_i grad var_i) + Sigma_prior^{-1} (u - mu)
+       CESX_GP_GAMMA, diagonal Gamma      a_i = d_i / Gamma_ii,  b = 0
+       CESX_GP_GAMMA, dense Gamma         a = L_Gamma^{-T} (L_Gamma^{-1} mean - y~),  b = 0
+       CESX_GP_VAR, CESX_GP_GAMMA_VAR     a_i = d_i / v_i,  b_i = 1/2 (1 / v_i - d_i^2 / v_i^2),  v_i = var_i (+ Gamma_ii)
+   g(u) = S^T grad phi(u) and xi ~ N(0, I):
+       cesx_gp_langevin_start     phi(U) and g(U) from the rows and gradients of cesx_gp_predict_grad at U; counters cleared
+       cesx_gp_langevin_propose   P = U + S (xi - g(U) / 2)       (xi_dev the injected block, engine dtype, or NULL: the device
+                                  draw of cesx_mh_propose for step_index; either way the block is kept in engine memory)
+       cesx_gp_langevin_accept    phi(P), g(P) from the rows and gradients at P, then the test
+                                      log u < phi(U) - phi(P) + 1/2 |xi|^2 - 1/2 |xi - (g(U) + g(P)) / 2|^2
+                                  with the block the last propose kept (no S^{-1}: S^{-1} (P - U + S S^T grad phi(U) / 2) = xi by
+                                  construction) and cesx_gp_accept's log u; accepted columns: U := P, phi := phi(P), g := g(P),
+                                  counter + 1.  The caller passes the same step_index to propose and accept.
+   A NaN or inf - inf in phi(P), g(P) or the correction rejects; a chain whose own phi or g is NaN stays where it is.  One
+   thread per chain (kernels_gpgrad.hip, lv_*), fp64, fixed orders: bit-reproducible.  The counters, cesx_mh_stats and
+   cesx_mh_phi are those of cesx_gp_start / cesx_gp_accept.  var_dev and dvar_dev may be NULL in mode CESX_GP_GAMMA.
+   CESX_ESTATE without cesx_set_problem, a proposal of kind CESX_MH_LANGEVIN, cesx_gp_set or (propose, accept) a
+   cesx_gp_langevin_start; accept also without a propose since the start or the last accept.  CESX_EINVAL for mode
+   CESX_GP_DENSE or CESX_GP_PROJ, an unknown mode, a variance mode with a dense Gamma, n_gp != n_obs, a null pointer, P_dev
+   aliasing U_dev or a step index >= 2^31.  None of these launches anything or touches U_dev or the chains' phi. */
+int cesx_gp_langevin_start(cesx_handle h, int mode, const void* U_dev, const double* mean_dev, const double* var_dev,
+                           const double* dmean_dev, const double* dvar_dev, void* stream);
+int cesx_gp_langevin_propose(cesx_handle h, uint64_t step_index, const void* U_dev, const void* xi_dev, void* P_dev, void* stream);
+int cesx_gp_langevin_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev, const void* P_dev, const double* mean_dev,
+                            const double* var_dev, const double* dmean_dev, const double* dvar_dev, const double* logu_dev,
+                            void* stream);
 /* CESX_GP_DENSE: k GPs on PCA-decorrelated outputs (pca_tools of ces/emulate.py:74-77 and ces/sample.py:52-53, :91-92).  The
    data space is rebuilt per chain j from column j of the (k x J_local) rows of cesx_gp_predict (n_gp == k):
        d = B m_j + g0 - y,    Sigma_j = Gamma + B diag(v_j) B^T,    phi = 1/2 d^T Sigma_j^{-1} d [+ 1/2 log det Sigma_j] + prior term
