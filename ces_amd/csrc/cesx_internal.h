@@ -475,6 +475,7 @@ struct Engine {
     std::vector<double> h_LSi, h_mu;   // L_Sigma^{-1} and mu of the problem (cesx_set_problem): the dense prior's image
     std::vector<double> h_y_raw, h_Gamma_raw;       // y and Gamma as cesx_set_problem got them (UNWHITENED; Gamma symmetric from its lower triangle)
     std::vector<double> h_yw, h_gw;                 // host copies of d_y (whitened for a dense Gamma) and d_gw: cesx_mh_run_map passes the problem by value
+    std::vector<double> h_sw;                       // host copy of d_sw (1 / Sigma_rr): cesx_mh_langevin_run_map passes lv_score's numbers by value
     MhState mh;                        // Metropolis-Hastings over the columns (cesx_mh_*, kernels_mh.hip)
     GpState gp;                        // GP emulator over the columns (cesx_gp_*, kernels_gp.hip)
     GpDenseState gpd;                  // the dense per-chain Sigma of CESX_GP_DENSE (cesx_gp_dense_set, kernels_gpdense.hip)
@@ -819,6 +820,11 @@ int launch_l63(Engine& e, const void* U, const double* W_in, void* G, double* W_
 int launch_map_apply(Engine& e, const void* U, void* G, hipStream_t s);
 int launch_mh_run_map(Engine& e, uint64_t step_index, int n_steps, int stride, void* U, void* trace, const void* xi,
                       const double* logu, hipStream_t s);
+// kernels_maps.hip: G [n][J] and the Jacobian DG [n][p][J] of the installed map, fp64 whatever the engine dtype; and
+// launch_mh_run_map under a Langevin proposal (the chains' g in mh.lv_g is read and written back)
+int launch_map_jac(Engine& e, const void* U, double* G, double* DG, hipStream_t s);
+int launch_mh_langevin_run_map(Engine& e, uint64_t step_index, int n_steps, int stride, void* U, void* trace, const void* xi,
+                               const double* logu, hipStream_t s);
 
 // kernels_chainsum.hip: the stage behind cesx_chain_summary_* (include/cesx.h); the entry points have checked the state
 int chainsum_begin(Engine& e, long long n_draws);

@@ -435,7 +435,7 @@ int cesx_set_problem(cesx_handle h, const double* y, const double* Gamma, const 
     TRY(upload(e, e.d_mu, mu, p * 8)); TRY(upload(e, e.d_ustar, ustar, p * 8));
     TRY(upload(e, e.d_Sigma, Sigma, (size_t)p * p * 8)); TRY(upload(e, e.d_Sinv, inv.data(), (size_t)p * p * 8));
     TRY(upload(e, e.d_sw, sw.data(), p * 8));
-    e.h_yw = yi; e.h_gw = gw;
+    e.h_yw = yi; e.h_gw = gw; e.h_sw = sw;
     {
         // K3 through the Cholesky factor where the problem and the shape allow (cesx_internal.h, Engine::chain).  The two layouts
         // of d_Wq share no writer's footprint: a change of layout starts from a zeroed image, with nothing of the engine in flight
@@ -1829,6 +1829,92 @@ int cesx_mh_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride,
     SET_DEVICE(e);
     FLUSH(e);
     TRY(launch_mh_run_map(e, step_index, n_steps, stride, U, trace, xi, logu, (hipStream_t)stream));
+    e.mh.steps += (unsigned long long)n_steps;
+    return CESX_OK;
+}
+
+// ---- The Langevin step of model_mh(chains=, update='langevin'): launch_gp_langevin on a map's G and Jacobian (kernels_gpgrad.hip,
+// lv_* in mode CESX_GP_GAMMA: mean := G, dmean := DG, no variances), and its fused kernel (kernels_maps.hip) ----
+
+int cesx_map_jac(cesx_handle h, const void* U, double* G, double* DG, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U || !G || !DG) { e.err = "cesx_map_jac: null pointer"; return CESX_EINVAL; }
+    if (e.mp.none()) { e.err = "cesx_map_jac: cesx_map_set has not been called"; return CESX_ESTATE; }
+    if (e.mp.desc.kind == CESX_MAP_EXP) { e.err = "cesx_map_jac: CESX_MAP_EXP has no Jacobian launch (lineal_log's gradient is an A^T product)"; return CESX_EUNSUPPORTED; }
+    SET_DEVICE(e);
+    return launch_map_jac(e, U, G, DG, (hipStream_t)stream);
+}
+
+// what every cesx_mh_langevin_* call needs before it looks at its own arguments; `started`: a cesx_mh_langevin_start too
+static int mh_langevin_check_state(Engine& e, bool started) {
+    if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_mh_langevin: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
+    if (started && !e.mh.started) { e.err = "cesx_mh_langevin: cesx_mh_langevin_start has not been called"; return CESX_ESTATE; }
+    return CESX_OK;
+}
+
+int cesx_mh_langevin_start(cesx_handle h, const void* U, const double* G, const double* DG, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(mh_langevin_check_state(e, false));
+    if (!U || !G || !DG) { e.err = "cesx_mh_langevin_start: null pointer"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_gp_langevin(e, 0, CESX_GP_GAMMA, U, G, nullptr, DG, nullptr, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream));
+    e.mh.started = true;
+    e.mh.lv_proposed = false;
+    e.mh.steps = 0;
+    return CESX_OK;
+}
+
+int cesx_mh_langevin_propose(cesx_handle h, uint64_t step_index, const void* U, const void* xi, void* P, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(mh_langevin_check_state(e, true));
+    if (!U || !P) { e.err = "cesx_mh_langevin_propose: null pointer"; return CESX_EINVAL; }
+    if (U == P) { e.err = "cesx_mh_langevin_propose: P must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_langevin_propose: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    hipStream_t s = (hipStream_t)stream;
+    // the block stays in engine memory: the accept step needs it again
+    if (xi) CESX_HIP(hipMemcpyAsync(e.mh.xi, xi, (size_t)e.p * (size_t)e.J * e.esz, hipMemcpyDeviceToDevice, s));
+    else TRY(launch_noise(e, mh_step_word(step_index), e.mh.xi, s));
+    TRY(launch_gp_langevin(e, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, const_cast<void*>(U), P, nullptr, 0u, s));
+    e.mh.lv_proposed = true;
+    return CESX_OK;
+}
+
+int cesx_mh_langevin_accept(cesx_handle h, uint64_t step_index, void* U, const void* P, const double* G, const double* DG,
+                            const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(mh_langevin_check_state(e, true));
+    if (!e.mh.lv_proposed) { e.err = "cesx_mh_langevin_accept: no cesx_mh_langevin_propose since the start or the last accept"; return CESX_ESTATE; }
+    if (!U || !P || !G || !DG) { e.err = "cesx_mh_langevin_accept: null pointer"; return CESX_EINVAL; }
+    if (U == P) { e.err = "cesx_mh_langevin_accept: P must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_langevin_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_gp_langevin(e, 2, CESX_GP_GAMMA, P, G, nullptr, DG, nullptr, U, nullptr, logu, mh_step_word(step_index), (hipStream_t)stream));
+    e.mh.lv_proposed = false;
+    ++e.mh.steps;
+    return CESX_OK;
+}
+
+int cesx_mh_langevin_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride, void* U, void* trace, const void* xi,
+                             const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U) { e.err = "cesx_mh_langevin_run_map: null pointer"; return CESX_EINVAL; }
+    if (n_steps < 1 || stride < 1) { e.err = "cesx_mh_langevin_run_map: n_steps and stride must be >= 1"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull || step_index + (uint64_t)n_steps > 0x80000000ull) { e.err = "cesx_mh_langevin_run_map: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    TRY(mh_langevin_check_state(e, true));
+    if (!e.mp.fused()) { e.err = "cesx_mh_langevin_run_map: no map of a fused kind is installed (cesx_map_set: CESX_MAP_ELLIPTIC or CESX_MAP_BANANA)"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_mh_langevin_run_map(e, step_index, n_steps, stride, U, trace, xi, logu, (hipStream_t)stream));
+    e.mh.lv_proposed = false;              // (a block proposed before the launch belongs to a state the chains have left)
     e.mh.steps += (unsigned long long)n_steps;
     return CESX_OK;
 }

@@ -19,7 +19,7 @@ F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
 ABI_VERSION = 10
-MH_KINDS = {None: 0, "pCN": 1, "langevin": 2}     # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN; build-only: CESX_MH_LANGEVIN
+MH_KINDS = {None: 0, "pCN": 1, "langevin": 2}     # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN; build-only: CESX_MH_LANGEVIN (gp_mh and model_mh)
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
            "cesx_step", "cesx_result", "cesx_moments_len", "cesx_colsum", "cesx_set_shift",
@@ -36,6 +36,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_darcy_set_streamed", "cesx_darcy_workspace_bytes", "cesx_lorenz_set", "cesx_lorenz_apply",
            "cesx_lorenz_three_set", "cesx_lorenz_three_apply", "cesx_map_set", "cesx_map_apply", "cesx_mh_run_map",
+           "cesx_map_jac", "cesx_mh_langevin_start", "cesx_mh_langevin_propose", "cesx_mh_langevin_accept", "cesx_mh_langevin_run_map",
            "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read",
            "cesx_chain_hist_begin", "cesx_chain_hist_add", "cesx_chain_hist_read")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
@@ -298,6 +299,11 @@ def load_library(path=None):
     lib.cesx_map_set.argtypes = [vp, C.POINTER(MapDesc)]
     lib.cesx_map_apply.argtypes = [vp, vp, vp, vp]
     lib.cesx_mh_run_map.argtypes = [vp, u64, i32, i32, vp, vp, vp, vp, vp]
+    lib.cesx_map_jac.argtypes = [vp, vp, vp, vp, vp]
+    lib.cesx_mh_langevin_start.argtypes = [vp, vp, vp, vp, vp]
+    lib.cesx_mh_langevin_propose.argtypes = [vp, u64, vp, vp, vp, vp]
+    lib.cesx_mh_langevin_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
+    lib.cesx_mh_langevin_run_map.argtypes = [vp, u64, i32, i32, vp, vp, vp, vp, vp]
     lib.cesx_chain_summary_begin.argtypes = [vp, i32, vp]
     lib.cesx_chain_summary_add.argtypes = [vp, vp, i32, vp]
     lib.cesx_chain_summary_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1339,6 +1345,73 @@ class Engine:
                                                  None if trace is None or trace.numel() == 0 else trace.data_ptr(),
                                                  None if xi is None else xi.data_ptr(),
                                                  None if logu is None else logu.data_ptr(), self._stream()))
+        self._keep_mh_run = (U, trace, xi, logu)
+
+    # -- the Langevin step on a closed-form map and its Jacobian (include/cesx.h, cesx_map_jac, cesx_mh_langevin_*) --
+    def map_jac(self, U, out=None):
+        """(G, DG): the installed map of the columns of ``U`` and its Jacobian ``DG[i][q] = dG_i / du_q``, float64 device
+        tensors (n_obs, J) and (n_obs, p, J) whatever the engine dtype (cesx_map_jac).  ``out``: a (G, DG) tuple to write
+        into.  The 'exp' map of ``lineal_log`` raises ``CesxError`` with code EUNSUPPORTED."""
+        if self.__dict__.get("_map_token") is None:
+            raise CesxError(ESTATE, "map_jac: map_set has not been called")
+        G, DG = out if out is not None else (None, None)
+        G = torch.empty((self.n_obs, self.J), dtype=torch.float64, device=self.device) if G is None else G
+        DG = torch.empty((self.n_obs, self.p, self.J), dtype=torch.float64, device=self.device) if DG is None else DG
+        for name, t, shape, dt in (("U", U, (self.p, self.J), self.torch_dtype), ("G", G, (self.n_obs, self.J), torch.float64),
+                                   ("DG", DG, (self.n_obs, self.p, self.J), torch.float64)):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("map_jac: %s must be a contiguous %s tensor of shape %s" % (name, dt, shape))
+        with torch.cuda.device(self.device):
+            rc = self.lib.cesx_map_jac(self._h, U.data_ptr(), G.data_ptr(), DG.data_ptr(), self._stream())
+            if rc == EUNSUPPORTED:            # (the 'exp' map, not the reference's missing LM_procedure of _check)
+                raise CesxError(rc, self.lib.cesx_last_error(self._h).decode())
+            self._check(rc)
+        self._keep_map_jac = (U, G, DG)
+        return G, DG
+
+    def mh_langevin_start(self, U, G, DG):
+        """phi (with the prior term) and g = S^T grad phi of the current states U from their forward map ``G`` (n_obs, J)
+        and its Jacobian ``DG`` (n_obs, p, J), float64 (``map_jac`` at U); counters cleared (cesx_mh_langevin_start)."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_langevin_start(self._h, U.data_ptr(), G.data_ptr(), DG.data_ptr(), self._stream()))
+        self._keep_lv_s = (U, G, DG)
+
+    def mh_langevin_propose(self, step_index, U, xi=None, out=None):
+        """P = U + S (xi - g(U) / 2) (cesx_mh_langevin_propose); xi None: drawn on device in the MH counter domain of
+        step_index.  The engine keeps the block for ``mh_langevin_accept``."""
+        out = self.empty(self.p) if out is None else out
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_langevin_propose(self._h, int(step_index), U.data_ptr(),
+                                                          None if xi is None else xi.data_ptr(), out.data_ptr(), self._stream()))
+        self._keep_lv_p = (U, xi, out)
+        return out
+
+    def mh_langevin_accept(self, step_index, U, P, G, DG, logu=None):
+        """phi(P) and g(P) from the map ``G`` and the Jacobian ``DG`` at P, the test with the Langevin correction, U := P on
+        the accepted columns (cesx_mh_langevin_accept); logu as in ``mh_accept``."""
+        if logu is not None:
+            assert logu.dtype == torch.float64 and logu.numel() == self.J and logu.is_contiguous()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_langevin_accept(self._h, int(step_index), U.data_ptr(), P.data_ptr(), G.data_ptr(),
+                                                         DG.data_ptr(), None if logu is None else logu.data_ptr(), self._stream()))
+        self._keep_lv_a = (U, P, G, DG, logu)
+
+    def mh_langevin_run_map(self, step_index, n_steps, U, stride=1, trace=None, xi=None, logu=None):
+        """``n_steps`` Langevin steps of every chain in one launch with the installed map of a fused kind
+        (cesx_mh_langevin_run_map): ``mh_run_map`` under a Langevin proposal, after ``mh_langevin_start``; the engine's phi,
+        g, counters and step count follow.  The arguments are ``mh_run_map``'s."""
+        n_steps, stride = int(n_steps), int(stride)
+        for name, t, shape, dt in (("U", U, (self.p, self.J), self.torch_dtype),
+                                   ("trace", trace, (max(n_steps, 0) // max(stride, 1), self.p, self.J), self.torch_dtype),
+                                   ("xi", xi, (n_steps, self.p, self.J), self.torch_dtype),
+                                   ("logu", logu, (n_steps, self.J), torch.float64)):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError("mh_langevin_run_map: %s must be a contiguous %s tensor of shape %s" % (name, dt, shape))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_langevin_run_map(self._h, int(step_index), n_steps, stride, U.data_ptr(),
+                                                          None if trace is None or trace.numel() == 0 else trace.data_ptr(),
+                                                          None if xi is None else xi.data_ptr(),
+                                                          None if logu is None else logu.data_ptr(), self._stream()))
         self._keep_mh_run = (U, trace, xi, logu)
 
     # -- streaming summaries of the chains' draws (include/cesx.h, cesx_chain_summary_*) --

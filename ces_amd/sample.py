@@ -70,7 +70,7 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          ``marginal_density`` and ``marginal_quantiles`` read it; ``plots.find_levels(H=hist2d[k])`` gives
                          the contour levels.  The chains, ``self.summary`` and ``self.samples`` are as without it.  A call
                          without ``marginals=`` removes ``self.marginals``: the attribute is always the last call's.
-  kwarg ``update='langevin'``  gp_mh only, on the host (one chain) and with ``chains=M``: a preconditioned Metropolis-adjusted
+  kwarg ``update='langevin'``  gp_mh, on the host (one chain) and with ``chains=M``: a preconditioned Metropolis-adjusted
                          Langevin proposal from the closed-form gradients of the GPs (``emulate.GPR.predict_f_grad``; on the
                          device ``cesx_gp_predict_grad`` and ``cesx_gp_langevin_*``, kernels_gpgrad.hip).  With S the scales of
                          the random walk -- so ``delta`` is the Langevin step --, g(u) = S^T grad phi(u) and xi ~ N(0, I):
@@ -78,8 +78,17 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          log u < phi(U) - phi(P) + |xi|^2 / 2 - |xi - (g(U) + g(P)) / 2|^2 / 2.  The draws per step are the random
                          walk's (xi, then u).  Likelihoods: Gamma (dense or diagonal), diag(gvars) and diag(Gamma) +
                          diag(gvars).  ``fused=True``, ``pca_tools``, ``separable``, emulators without gradients and Matern12
-                         kernels raise ``ValueError``; so does ``model_mh``: no device map has a Jacobian yet.  ``summary=``,
+                         kernels raise ``ValueError``.  ``summary=``,
                          ``burn=``, ``marginals=``, ``start=``, ``noise=``, resume and ``trace_stride`` work as for the random walk.
+                         model_mh takes it for a model with a Jacobian (``ces_amd.utils.elliptic`` and ``banana``:
+                         ``model.jacobian`` on the host, ``model.jacobian_device`` -- ``cesx_map_jac`` -- with ``chains=M``): the
+                         same step on the true posterior, phi with the prior term, grad phi = DG^T Gamma^{-1} (G - y) +
+                         cov^{-1} (u - mean), the same scales, seed and draws, so its chains compare with the emulator's.
+                         On the device the step path is ``cesx_mh_langevin_*`` (the emulator's lv_* kernels on G and DG) and
+                         ``fused=True`` the fused kernel ``mh_langevin_map_kernel`` (``cesx_mh_langevin_run_map``: the chain and its
+                         g in one lane's registers); ``fused=None`` is ``LANGEVIN_FUSED_DEFAULT``.  A resume always scores the
+                         resumed states (phi and g).  A model without a Jacobian (``lineal``, ``lineal_log``, Darcy, every
+                         'pde' model) and ``flag_noise=True`` raise ``ValueError`` before an engine is created.
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -279,6 +288,11 @@ class MCMC(object):
     FUSED_DEFAULT = True
     FUSED_STEPS_MAX = 4096
     FUSED_BUFFER_BYTES = 64 << 20
+    # build-only, model_mh(chains=, update='langevin', fused=): what fused=None resolves to for elliptic and banana -- the path
+    # that tools/map_langevin_bench.py measures faster at BOTH 1 024 and 65 536 chains on the elliptic problem (the step path
+    # if the two sizes disagree).  Measured (NOTEBOOK.md): fused 5.3 us against 33.0 us per step at 1 024 chains, 13.5 us
+    # against 43.8 us at 65 536, fp64 -- and on an fp64 engine both paths leave the same chains bit for bit.
+    LANGEVIN_FUSED_DEFAULT = True
     # build-only, gp_mh(chains=, fused=): what fused=None resolves to (the step path: every call without fused= runs as it
     # did before the fused kernel existed; the measurement: NOTEBOOK.md, tools/gp_chain_bench.py), and the arithmetic one
     # launch may hold.  A fused gp step does real work -- per chain and GP the K* panel and its triangular product,
@@ -484,11 +498,15 @@ class MCMC(object):
         ``noise='numpy'`` keeps the reference's phi of the start point; with ``noise='device'`` it is exact (phi of the
         resumed states, the step counter of the noise continues), so that two runs of n steps equal one of 2 n.
         """
+        if kwargs.get("update", None) == "langevin":      # build-only; refused before any engine is created
+            self._model_langevin_refusals(model, prior, kwargs.get("chains", None) is not None)
         if kwargs.get("chains", None) is not None:
             return self._model_mh_device(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, kwargs)
         if kwargs.get("fused", None) is not None:
             raise ValueError("fused=%r chooses between the device paths of chains=M; the host path has one" % (kwargs.get("fused"),))
         _host_has_no_summary(kwargs)
+        if kwargs.get("update", None) == "langevin":
+            return self._model_mh_langevin_host(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling)
         # RW needs the proposal distribution (:122-126)
         if enka_scaling:
             scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(enka.p, enka.p))
@@ -546,6 +564,61 @@ class MCMC(object):
         self.samples = np.array(samples).T
         self.accept = accept / n_mcmc
 
+    @staticmethod
+    def _model_langevin_refusals(model, prior, device):
+        """What ``model_mh(update='langevin')`` cannot do, host and device alike: every refusal is a ValueError with the reason."""
+        need = "jacobian_device" if device else "jacobian"
+        if getattr(model, "type", None) == "pde" or not hasattr(model, "jacobian") or not hasattr(model, need):
+            raise ValueError("update='langevin' needs the gradient of phi, and %r offers no Jacobian (model.%s; "
+                             "ces_amd.utils.elliptic and banana do): the gradient of lineal and lineal_log is an A^T product "
+                             "and the Darcy and Lorenz models have no adjoint; gp_mh(update='langevin') differentiates the "
+                             "emulator instead" % (model, need))
+        if getattr(model, "flag_noise", False):
+            raise ValueError("update='langevin': a noisy map (flag_noise=True) has no gradient of phi")
+        if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
+            raise ValueError("update='langevin': the prior must expose .mean and .cov (its gradient is cov^{-1} (u - mean))")
+
+    def _model_mh_langevin_host(self, model, n_mcmc, prior, enka, Gamma, delta, enka_scaling):
+        """``model_mh(update='langevin')`` on the host, one chain: the restatement the device is held to.  The scales and
+        the start are the random walk's, phi has the prior term, g = S^T grad phi with
+        grad phi = DG^T Gamma^{-1} (G - y) + cov^{-1} (u - mean) from ``model.jacobian``; the proposal
+        ``u + S (xi - g / 2)``, the test with ``langevin_correction``, and the draws per step in the order of the host
+        ``gp_mh(update='langevin')``: ``np.random.normal(0, 1, p)``, then ``np.random.uniform()``.  A resume scores the
+        resumed state (phi and g)."""
+        p, n = enka.p, enka.n_obs
+        scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(p, p)) if enka_scaling else delta * np.eye(p)
+        Gamma = np.asarray(Gamma, dtype=np.float64).reshape(n, n)
+        mean = np.asarray(prior.mean, dtype=np.float64).reshape(p)
+        cov = np.asarray(prior.cov, dtype=np.float64).reshape(p, p)
+        y = np.asarray(self.y_obs, dtype=np.float64).reshape(n)
+
+        def score(u):
+            yg = np.asarray(enka.G(u.flatten(), model), dtype=np.float64)[:n] - y
+            a = np.linalg.solve(Gamma, yg)
+            w = np.linalg.solve(cov, u.flatten() - mean)
+            DG = np.asarray(model.jacobian(u.flatten()), dtype=np.float64).reshape(n, p)
+            phi = 0.5 * (yg * a).sum() + 0.5 * ((u.flatten() - mean) * w).sum()
+            return phi, scales.T @ (DG.T @ a + w)
+
+        current = enka.Ustar.mean(axis=1)
+        if hasattr(self, "samples"):
+            samples = list(self.samples.T)
+            current = samples[-1]
+        else:
+            samples = [current.flatten()]
+        accept = 0.
+        phi_current, g_current = score(current)
+        for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
+            xi = np.random.normal(0, 1, p)
+            proposal = current + np.matmul(scales, xi - 0.5 * g_current)
+            phi_proposal, g_proposal = score(proposal)
+            if np.log(np.random.uniform()) < phi_current - phi_proposal + self.langevin_correction(xi, g_current, g_proposal):
+                current, phi_current, g_current = np.copy(proposal), phi_proposal, g_proposal
+                accept += 1.
+            samples.append(current.flatten())
+        self.samples = np.array(samples).T
+        self.accept = accept / n_mcmc
+
     def random_walk(self, current, scales, n_dim):
         """ces/sample.py:198-199."""
         return current + np.matmul(scales, np.random.normal(0, 1, n_dim))
@@ -575,7 +648,7 @@ class MCMC(object):
                                  launch: ``eng.mh_run_map`` for a map, ``eng.gp_run`` for the emulator; None where the
                                  sampler has no fused kernel) and, optionally, a fourth hook ``propose(step, U, xi, P)`` that
                                  stands in for ``eng.mh_propose`` on the step path (the Langevin proposal reads the chains' g)
-        langevin                 the sampler takes ``update='langevin'`` (gp_mh; model_mh has no Jacobian on the device)
+        langevin                 the sampler takes ``update='langevin'`` (gp_mh; model_mh for a model with a Jacobian)
         resume_keeps_start_phi   the reference's model_mh scores the START point before it looks for ``self.samples`` and
                                  keeps that phi for the resumed states (ces/sample.py:131-163); its gp_mh scores the resumed
                                  states (:31-39).  True: the first, for ``noise='numpy'`` (``noise='device'`` re-scores the
@@ -600,8 +673,8 @@ class MCMC(object):
             raise ValueError("chains=: the prior must expose .mean and .cov (a frozen scipy.stats.multivariate_normal does)")
         update = kwargs.get("update", None)
         if update == "langevin" and not langevin:
-            raise ValueError("chains=: update='langevin' needs the gradient of phi, and no device map has a Jacobian yet; "
-                             "gp_mh(chains=, update='langevin') differentiates the emulator")
+            raise ValueError("chains=: update='langevin' needs the gradient of phi, and this sampler has no Jacobian on the "
+                             "device; gp_mh(chains=, update='langevin') differentiates the emulator")
         if update not in (None, "pCN", "langevin"):
             raise ValueError("chains=: unknown update %r (None or 'pCN')" % (update,))
         if self.noise not in ("numpy", "device"):
@@ -759,7 +832,9 @@ class MCMC(object):
         if fused and not has_fused:
             raise ValueError("fused=True: %r has no fused chain kernel (ces_amd.utils.elliptic and banana have, noise-free); "
                              "pass fused=None or False for the step path" % (model,))
-        fused = (has_fused and self.FUSED_DEFAULT) if fused is None else bool(fused)
+        langevin = kwargs.get("update", None) == "langevin"      # (model_mh has refused what has no Jacobian)
+        default = self.LANGEVIN_FUSED_DEFAULT if langevin else self.FUSED_DEFAULT
+        fused = (has_fused and default) if fused is None else bool(fused)
         p, n = enka.p, enka.n_obs
 
         def scales_of(update):                            # exactly as the reference forms them (:122-129)
@@ -820,8 +895,31 @@ class MCMC(object):
                 eng.mh_run_map(step, K, U, stride=stride, trace=trace, xi=xi, logu=logu)
             return score_start, score_accept, run_steps if fused else None
 
-        self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_pde if pde else bind, resume_keeps_start_phi=True,
-                        fused=fused)
+        def bind_langevin(eng, M):
+            # the map and its Jacobian of one state at a time, fp64: the chains' own g stays in the engine (mh.lv_g)
+            import torch
+            out = (torch.empty((n, M), dtype=torch.float64, device=eng.device),
+                   torch.empty((n, p, M), dtype=torch.float64, device=eng.device))
+            model.ensure_installed(eng)
+
+            def lv_start(U):
+                model.jacobian_device(eng, U, out=out)
+                eng.mh_langevin_start(U, *out)
+
+            def lv_propose(step, U, xi, P):
+                eng.mh_langevin_propose(step, U, xi=xi, out=P)
+
+            def lv_accept(step, U, P, logu):
+                model.jacobian_device(eng, P, out=out)
+                eng.mh_langevin_accept(step, U, P, *out, logu=logu)
+
+            def run_steps(step, K, U, stride, trace, xi, logu):
+                eng.mh_langevin_run_map(step, K, U, stride=stride, trace=trace, xi=xi, logu=logu)
+            return lv_start, lv_accept, run_steps if fused else None, lv_propose
+
+        # a resume under update='langevin' scores the resumed states whatever the noise: the chains need their g as well as phi
+        self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_langevin if langevin else bind_pde if pde else bind,
+                        resume_keeps_start_phi=not langevin, fused=fused, langevin=langevin)
 
     def _gp_mh_device(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
         import torch

@@ -118,6 +118,14 @@ class _map_hook(object):
         self.ensure_installed(engine)
         return engine.map_apply(U_dev, out=out)
 
+    def jacobian_device(self, engine, U_dev, out=None):
+        """(G, DG) of the columns of ``U_dev`` on the device (build-only): float64 (n_obs, J) and (n_obs, p, J),
+        ``DG[i][q] = dG_i / du_q`` as ``jacobian`` has it on the host (cesx_map_jac).  ``out``: a (G, DG) tuple."""
+        if self.flag_noise:
+            raise ValueError("the device hook evaluates the noise-free map only")
+        self.ensure_installed(engine)
+        return engine.map_jac(U_dev, out=out)
+
 
 class lineal_log(lineal):
     """``A exp(phi) + b`` (ces/utils.py:33-51): ``lineal`` in log-parameters, with the log-Jacobian helpers."""
@@ -195,6 +203,14 @@ class elliptic(_map_hook):
                              [-np.exp(-u1) * (-self.x2**2 + self.x2) * 0.5, self.x2]])
         return [x, y]
 
+    def jacobian(self, theta):
+        """``DG[i][q] = dG_i / dtheta_q`` (build-only name; the entries of ``__call__(theta, dG=True)``, :85-86): (2, 2) for
+        one particle, (2, 2, J) for a (2, J) block, for which the reference's ``dG=True`` has no array to return."""
+        u1, u2 = theta
+        one = np.ones_like(np.asarray(u1, dtype=np.float64))
+        return np.array([[-np.exp(-u1) * (-self.x1**2 + self.x1) * 0.5, self.x1 * one],
+                         [-np.exp(-u1) * (-self.x2**2 + self.x2) * 0.5, self.x2 * one]])
+
     def _map_desc(self):
         return (self.x1, self.x2)
 
@@ -230,6 +246,13 @@ class banana(_map_hook):
         x = u1 * self.a
         y = u2 / self.a - self.b * (u1**2 + self.a**2)
         return np.array([x, y]) + self.flag_noise * np.linalg.cholesky(self.Gamma).dot(np.random.normal(0, 1, [2, ]))
+
+    def jacobian(self, theta):
+        """``DG[i][q] = dG_i / dtheta_q = [[a, 0], [-2 b u1, 1 / a]]`` (build-only: the reference's ``banana`` takes ``dG`` and
+        ignores it, as ``__call__`` here does): (2, 2) for one particle, (2, 2, J) for a (2, J) block."""
+        u1, u2 = theta
+        one = np.ones_like(np.asarray(u1, dtype=np.float64))
+        return np.array([[self.a * one, 0.0 * one], [-2.0 * self.b * u1 * one, one / self.a]])
 
     def _map_desc(self):
         return (self.a, self.b)

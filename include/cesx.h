@@ -515,9 +515,10 @@ int cesx_lorenz_three_apply(cesx_handle h, const void* U_dev, const double* W_in
    (cesx_mh_set_proposal again, then cesx_mh_start). */
 #define CESX_MH_RW   0
 #define CESX_MH_PCN  1
-#define CESX_MH_LANGEVIN 2   /* the preconditioned Langevin proposal of cesx_gp_langevin_* (below); S as for RW, beta ignored.  With
+#define CESX_MH_LANGEVIN 2   /* the preconditioned Langevin proposal of cesx_gp_langevin_* (the emulator) and cesx_mh_langevin_* (a
+                                closed-form map with its Jacobian, cesx_map_jac), both below; S as for RW, beta ignored.  With
                                 this kind cesx_mh_start / _propose / _accept, cesx_gp_start / _accept, cesx_gp_run and
-                                cesx_mh_run_map return CESX_EINVAL and launch nothing: no map has a Jacobian on the device. */
+                                cesx_mh_run_map return CESX_EINVAL and launch nothing: they have no gradient of phi. */
 /* The proposal: kind CESX_MH_RW | CESX_MH_PCN | CESX_MH_LANGEVIN, S_host the p x p LOWER-triangular scale matrix (row-major fp64, computed by the
    caller exactly as ces/sample.py:122-129 does; CESX_EINVAL when an entry above the diagonal is nonzero), beta the pCN
    parameter (0 < beta <= 1; ignored for RW).  Needs the problem (cesx_set_problem). */
@@ -579,6 +580,46 @@ int cesx_map_apply(cesx_handle h, const void* U_dev, void* G_dev, void* stream);
    for n_steps < 1, stride < 1 or a step index >= 2^31.  Neither launches anything. */
 int cesx_mh_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride, void* U_dev, void* trace_dev,
                     const void* xi_dev, const double* logu_dev, void* stream);
+/* G_dev [n_obs][J_local] = the installed map of the columns of U_dev, as cesx_map_apply forms it before it rounds, and
+   DG_dev [n_obs][p][J_local], DG[i][q] = dG_i / du_q -- both fp64 whatever the engine dtype, one column per lane: the layout of
+   cesx_gp_predict_grad's mean_dev / dmean_dev.
+       CESX_MAP_ELLIPTIC   DG = [[-exp(-u1) (-x1^2 + x1) / 2, x1], [-exp(-u1) (-x2^2 + x2) / 2, x2]]      (ces/utils.py:85-86)
+       CESX_MAP_BANANA     DG = [[a, 0], [-2 b u1, 1 / a]]
+   CESX_ESTATE without an installed map, CESX_EUNSUPPORTED for CESX_MAP_EXP (lineal_log's gradient is an A^T product, not an
+   [n][p][J] Jacobian), CESX_EINVAL for a null pointer.  None of these launches anything. */
+int cesx_map_jac(cesx_handle h, const void* U_dev, double* G_dev, double* DG_dev, void* stream);
+/* MCMC.model_mh(chains=M, update='langevin'): the preconditioned Metropolis-adjusted Langevin step of cesx_gp_langevin_* (below)
+   on the TRUE posterior: no cesx_gp_set and no mode.  phi is cesx_mh_start's with the prior term; with G_dev and DG_dev the
+   rows and the Jacobian of cesx_map_jac (or any [n][J] / [n][p][J] fp64 images of a forward map and its Jacobian),
+       a = Gamma^{-1} (G - y),   grad phi = DG^T a + Sigma_prior^{-1} (u - mu),   g = S^T grad phi
+       cesx_mh_langevin_start     phi(U) and g(U); counters cleared
+       cesx_mh_langevin_propose   P = U + S (xi - g(U) / 2); the block (xi_dev, or NULL: the device draw of cesx_mh_propose for
+                                  step_index) is kept in engine memory
+       cesx_mh_langevin_accept    phi(P), g(P) from G_dev, DG_dev at P, then the test
+                                      log u < phi(U) - phi(P) + 1/2 |xi|^2 - 1/2 |xi - (g(U) + g(P)) / 2|^2
+                                  with cesx_mh_accept's log u; accepted columns: U := P, phi := phi(P), g := g(P), counter + 1
+   These are the lv_* kernels of cesx_gp_langevin_* in mode CESX_GP_GAMMA (kernels_gpgrad.hip): a diagonal or a dense
+   (whitened) Gamma, a diagonal or a dense prior, NaN rejects.  The counters, cesx_mh_stats and cesx_mh_phi follow.
+   CESX_ESTATE without cesx_set_problem, a proposal of kind CESX_MH_LANGEVIN or (propose, accept) a cesx_mh_langevin_start;
+   accept also without a propose since the start or the last accept.  CESX_EINVAL for a null pointer, P_dev aliasing U_dev or
+   a step index >= 2^31.  None of these launches anything or touches U_dev or the chains' phi. */
+int cesx_mh_langevin_start(cesx_handle h, const void* U_dev, const double* G_dev, const double* DG_dev, void* stream);
+int cesx_mh_langevin_propose(cesx_handle h, uint64_t step_index, const void* U_dev, const void* xi_dev, void* P_dev, void* stream);
+int cesx_mh_langevin_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* P_dev, const double* G_dev,
+                            const double* DG_dev, const double* logu_dev, void* stream);
+/* cesx_mh_run_map under a Langevin proposal, for CESX_MAP_ELLIPTIC and CESX_MAP_BANANA: n_steps Langevin steps of every chain in
+   ONE launch, one chain per lane, the map, its Jacobian, phi, g and the test above in the lane's registers.  A lane loads
+   its state, phi, counter and g (what cesx_mh_langevin_start / _accept left) and stores them once: afterwards U_dev, the
+   chains' phi, g, the counters and the step count are as n_steps calls of cesx_mh_langevin_propose / cesx_map_jac /
+   cesx_mh_langevin_accept would have left them, so fused launches and single Langevin steps may alternate.  The kernel
+   restates the sums of the step path's kernels in their order (g enters the next proposal: a resume that scores the resumed
+   states through cesx_mh_langevin_start continues a fused run exactly on an fp64 engine).  Noise, trace_dev, stride and the
+   fp32 engine's rounding on the store are cesx_mh_run_map's.
+   CESX_ESTATE without cesx_set_problem, a proposal of kind CESX_MH_LANGEVIN, cesx_mh_langevin_start (or cesx_gp_langevin_start)
+   or an installed map of a fused kind; CESX_EINVAL for a null U_dev, n_steps < 1, stride < 1 or a step index >= 2^31.
+   Neither launches anything. */
+int cesx_mh_langevin_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride, void* U_dev, void* trace_dev,
+                             const void* xi_dev, const double* logu_dev, void* stream);
 
 /* ---- Streaming summaries of the chains' draws (MCMC(..., chains=M, summary=True); kernels_chainsum.hip) --
    The sums behind the pooled mean and covariance, the split R-hat and an effective sample size of a run of
