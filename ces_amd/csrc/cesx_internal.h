@@ -773,6 +773,12 @@ int launch_gp_predict_grad(Engine& e, const void* X, double* mean, double* var, 
 // test with the Langevin correction, U := X, phi and g on the accepted columns
 int launch_gp_langevin(Engine& e, int what, int mode, const void* X, const double* mean, const double* var, const double* dmean,
                        const double* dvar, void* U, void* P, const double* logu, unsigned step, hipStream_t s);
+// kernels_lvlin.hip: the Langevin step on a linear map (cesx_mh_langevin_lineal_*).  launch_lvlin_score is launch_mh_score with
+// the prior term whatever the proposal kind, the Langevin correction from mh.xi / mh.lin_g / mh.lin_gp in the test, and the
+// masked copy of g(P) beside the one of P; launch_lvlin_z: mh.lin_z = mh.xi - mh.lin_g / 2; launch_lvlin_exph: t0 := exp(X) (.) t0
+int launch_lvlin_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s);
+int launch_lvlin_z(Engine& e, hipStream_t s);
+int launch_lvlin_exph(Engine& e, const void* X, void* t0, hipStream_t s);
 // kernels_gp.hip: phi of the states X from the GP rows (mode CESX_GP_GAMMA / _VAR / _GAMMA_VAR); start: into mh.phi,
 // counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double* mean, const double* var, void* U,

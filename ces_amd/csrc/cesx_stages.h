@@ -30,8 +30,16 @@ struct MhState {
     std::vector<double> h_bS;          // [p][p] b S on the host: cesx_mh_run_map passes it by value
     DevBuf<double> lv_g, lv_gp;        // Langevin: [p][J] g = S^T grad phi of the chains' states and of the proposals (kernels_gpgrad.hip)
     DevBuf<double> lv_a, lv_b, lv_gphi; // Langevin: [n][J], [n][J], [p][J] what lv_score keeps per chain: a_i, b_i, grad phi
+    // Langevin on a linear map (cesx_mh_langevin_lineal_*, kernels_lvlin.hip): the gradient is an update launch over these images
+    int lin = 0;                       // 0: no cesx_mh_langevin_lineal_set; 1: lineal (one launch); 2: lineal_log (two launches and exp)
+    bool lin_started = false;          // the LAST start was cesx_mh_langevin_lineal_start: g lives in lin_g, not in lv_g
+    DevBuf<void> lin_Wa, lin_Wa_f;     // lineal: S^T [A^T M | Sigma^{-1}] [rpad][kn + kp]; lineal_log: A^T M [rpad][kn]; both layouts, as W / Wf
+    DevBuf<void> lin_Wb, lin_Wb_f;     // lineal_log: [S^T | S^T Sigma^{-1}] [rpad][2 kp]
+    DevBuf<void> lin_ba, lin_bb;       // [rpad] the biases of the two launches
+    DevBuf<void> lin_g, lin_gp, lin_z; // [p][J] engine dtype: g of the chains' states, of the proposals, and z = xi - g / 2
+    DevBuf<void> lin_t;                // lineal_log: [p][J] t0, then h = exp(X) (.) t0
     bool none() const { return kind < 0; }
-    void drop() { kind = -1; started = false; lv_proposed = false; }      // every buffer is sized by the engine: kept
+    void drop() { kind = -1; started = false; lv_proposed = false; lin = 0; lin_started = false; }      // every buffer is sized by the engine: kept
 };
 
 // ---- GP emulator over the columns (cesx_gp_*, kernels_gp.hip) ----

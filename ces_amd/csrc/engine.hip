@@ -1217,7 +1217,7 @@ int cesx_gp_predict_grad(cesx_handle h, const void* X, double* mean, double* var
 static int langevin_check_state(Engine& e, bool started) {
     if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_gp_langevin: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
     if (e.gp.none()) { e.err = "cesx_gp_langevin: cesx_gp_set has not been called"; return CESX_ESTATE; }
-    if (started && !e.mh.started) { e.err = "cesx_gp_langevin: cesx_gp_langevin_start has not been called"; return CESX_ESTATE; }
+    if (started && (!e.mh.started || e.mh.lin_started)) { e.err = "cesx_gp_langevin: cesx_gp_langevin_start has not been called"; return CESX_ESTATE; }
     return CESX_OK;
 }
 
@@ -1241,6 +1241,7 @@ int cesx_gp_langevin_start(cesx_handle h, int mode, const void* U, const double*
     FLUSH(e);
     TRY(launch_gp_langevin(e, 0, mode, U, mean, var, dmean, dvar, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream));
     e.mh.started = true;
+    e.mh.lin_started = false;
     e.mh.lv_proposed = false;
     e.mh.steps = 0;
     return CESX_OK;
@@ -1849,7 +1850,7 @@ int cesx_map_jac(cesx_handle h, const void* U, double* G, double* DG, void* stre
 // what every cesx_mh_langevin_* call needs before it looks at its own arguments; `started`: a cesx_mh_langevin_start too
 static int mh_langevin_check_state(Engine& e, bool started) {
     if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_mh_langevin: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
-    if (started && !e.mh.started) { e.err = "cesx_mh_langevin: cesx_mh_langevin_start has not been called"; return CESX_ESTATE; }
+    if (started && (!e.mh.started || e.mh.lin_started)) { e.err = "cesx_mh_langevin: cesx_mh_langevin_start has not been called (the last start was not it)"; return CESX_ESTATE; }
     return CESX_OK;
 }
 
@@ -1862,6 +1863,7 @@ int cesx_mh_langevin_start(cesx_handle h, const void* U, const double* G, const 
     FLUSH(e);
     TRY(launch_gp_langevin(e, 0, CESX_GP_GAMMA, U, G, nullptr, DG, nullptr, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream));
     e.mh.started = true;
+    e.mh.lin_started = false;
     e.mh.lv_proposed = false;
     e.mh.steps = 0;
     return CESX_OK;
@@ -1916,6 +1918,232 @@ int cesx_mh_langevin_run_map(cesx_handle h, uint64_t step_index, int n_steps, in
     TRY(launch_mh_langevin_run_map(e, step_index, n_steps, stride, U, trace, xi, logu, (hipStream_t)stream));
     e.mh.lv_proposed = false;              // (a block proposed before the launch belongs to a state the chains have left)
     e.mh.steps += (unsigned long long)n_steps;
+    return CESX_OK;
+}
+
+// ---- the Langevin step on a linear map: the gradient as update launches (include/cesx.h; kernels_lvlin.hip) ----
+
+// a p x ktot fp64 matrix (row-major, its padding columns zero) into the update kernels' [rpad][ktot] layouts, engine dtype
+static int lin_upload(Engine& e, const std::vector<double>& M, int ktot, DevBuf<void>& rm_dev, DevBuf<void>& fm_dev) {
+    const size_t len = (size_t)e.rpad * ktot;
+    std::vector<double> rm(len, 0.0), fm(len, 0.0);
+    const int nkt = ktot / 16;
+    for (int i = 0; i < e.p; ++i)
+        for (int k = 0; k < ktot; ++k) {
+            const double v = M[(size_t)i * ktot + k];
+            rm[(size_t)i * ktot + k] = v;
+            fm[e.cfg.dtype == CESX_F32 ? wf_index(i, k, nkt) : wd_index(i, k, nkt)] = v;
+        }
+    TRY_BUF(rm_dev.ensure(len * e.esz)); TRY_BUF(fm_dev.ensure(len * e.esz));
+    TRY(upload_T(e, rm_dev, rm.data(), len));
+    return upload_T(e, fm_dev, fm.data(), len);
+}
+
+static int lin_upload_bias(Engine& e, const std::vector<double>& b, DevBuf<void>& dev) {
+    std::vector<double> pad(e.rpad, 0.0);
+    std::copy(b.begin(), b.end(), pad.begin());
+    TRY_BUF(dev.ensure((size_t)e.rpad * e.esz));
+    return upload_T(e, dev, pad.data(), e.rpad);
+}
+
+// Failure rule: from the synchronise until the last upload the handle has NO lineal image; a failure leaves it so.
+int cesx_mh_langevin_lineal_set(cesx_handle h, const double* A, const double* b, int exp_params) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!A) { e.err = "cesx_mh_langevin_lineal_set: null pointer"; return CESX_EINVAL; }
+    if (exp_params != 0 && exp_params != 1) { e.err = "cesx_mh_langevin_lineal_set: exp_params must be 0 or 1"; return CESX_EINVAL; }
+    if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_mh_langevin_lineal_set: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
+    const int p = e.p, n = e.n, kp = e.kp, kn = e.kn;
+    for (size_t i = 0; i < (size_t)n * p; ++i)
+        if (!std::isfinite(A[i])) { e.err = "cesx_mh_langevin_lineal_set: A is not finite"; return CESX_EINVAL; }
+    for (int i = 0; b && i < n; ++i)       // (b enters through G alone -- the caller's rows carry it --: checked, not stored)
+        if (!std::isfinite(b[i])) { e.err = "cesx_mh_langevin_lineal_set: b is not finite"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    CESX_HIP(hipDeviceSynchronize());          // (the images below may be read by launches still in flight)
+    if (e.mh.lin_started) e.mh.started = false;        // (the chains' g belonged to the old image)
+    e.mh.lin = 0; e.mh.lin_started = false; e.mh.lv_proposed = false;
+    // B = A^T M, p x n, with M (G~ - y~) = Gamma^{-1} (G - y) for the rows G~ the score kernel reads: Gamma^{-1} itself on the
+    // caller's rows (diagonal), L_Gamma^{-T} on the whitened ones (dense: B[q][i] = sum_{k <= i} A[k][q] Li[i][k])
+    std::vector<double> B((size_t)p * n, 0.0);
+    for (int q = 0; q < p; ++q)
+        for (int i = 0; i < n; ++i) {
+            double acc = 0.0;
+            if (e.whiten) for (int k = 0; k <= i; ++k) acc += A[(size_t)k * p + q] * e.h_Li[(size_t)i * n + k];
+            else acc = A[(size_t)i * p + q] * e.h_gw[i];
+            B[(size_t)q * n + i] = acc;
+        }
+    std::vector<double> Sinv;
+    host_spd_inverse(p, e.h_LSi, Sinv);
+    // S^T X for the lower-triangular scales S (p x p) and X (p x m)
+    const std::vector<double>& S = e.mh.h_bS;
+    auto St_times = [&](const std::vector<double>& X, int m) {
+        std::vector<double> out((size_t)p * m, 0.0);
+        for (int r = 0; r < p; ++r)
+            for (int q = r; q < p; ++q) {
+                const double sv = S[(size_t)q * p + r];
+                if (sv == 0.0) continue;
+                for (int i = 0; i < m; ++i) out[(size_t)r * m + i] += sv * X[(size_t)q * m + i];
+            }
+        return out;
+    };
+    const std::vector<double> StSinv = St_times(Sinv, p);
+    std::vector<double> bias_prior(p, 0.0);            // -S^T Sigma^{-1} mu
+    for (int r = 0; r < p; ++r) {
+        double acc = 0.0;
+        for (int k = 0; k < p; ++k) acc += StSinv[(size_t)r * p + k] * e.h_mu[k];
+        bias_prior[r] = -acc;
+    }
+    auto minus_times_y = [&](const std::vector<double>& X) {       // -X y~ (X p x n)
+        std::vector<double> out(p, 0.0);
+        for (int r = 0; r < p; ++r) {
+            double acc = 0.0;
+            for (int i = 0; i < n; ++i) acc += X[(size_t)r * n + i] * e.h_yw[i];
+            out[r] = -acc;
+        }
+        return out;
+    };
+    if (!exp_params) {
+        // lineal: g = [S^T B | S^T Sigma^{-1}] . [G~ ; X] - S^T B y~ - S^T Sigma^{-1} mu, one launch
+        const int kt = kn + kp;
+        const std::vector<double> StB = St_times(B, n);
+        std::vector<double> W((size_t)p * kt, 0.0), bias = minus_times_y(StB);
+        for (int r = 0; r < p; ++r) {
+            for (int i = 0; i < n; ++i) W[(size_t)r * kt + i] = StB[(size_t)r * n + i];
+            for (int k = 0; k < p; ++k) W[(size_t)r * kt + kn + k] = StSinv[(size_t)r * p + k];
+            bias[r] += bias_prior[r];
+        }
+        TRY(lin_upload(e, W, kt, e.mh.lin_Wa, e.mh.lin_Wa_f));
+        TRY(lin_upload_bias(e, bias, e.mh.lin_ba));
+    } else {
+        // lineal_log: t0 = B . G~ - B y~; h = exp(X) (.) t0; g = [S^T | S^T Sigma^{-1}] . [h ; X] - S^T Sigma^{-1} mu
+        std::vector<double> Wa((size_t)p * kn, 0.0), Wb((size_t)p * 2 * kp, 0.0);
+        for (int r = 0; r < p; ++r) {
+            for (int i = 0; i < n; ++i) Wa[(size_t)r * kn + i] = B[(size_t)r * n + i];
+            for (int k = r; k < p; ++k) Wb[(size_t)r * 2 * kp + k] = S[(size_t)k * p + r];
+            for (int k = 0; k < p; ++k) Wb[(size_t)r * 2 * kp + kp + k] = StSinv[(size_t)r * p + k];
+        }
+        TRY(lin_upload(e, Wa, kn, e.mh.lin_Wa, e.mh.lin_Wa_f));
+        TRY(lin_upload_bias(e, minus_times_y(B), e.mh.lin_ba));
+        TRY(lin_upload(e, Wb, 2 * kp, e.mh.lin_Wb, e.mh.lin_Wb_f));
+        TRY(lin_upload_bias(e, bias_prior, e.mh.lin_bb));
+        TRY_BUF(e.mh.lin_t.ensure((size_t)p * (size_t)e.J * e.esz));
+    }
+    if (!e.diag_sigma) {                       // the prior sum runs over w = L_Sigma^{-1} (X - mu): the random walk's images (a Langevin proposal has none)
+        TRY(mh_upload_tri(e, e.h_LSi.data(), e.mh.Li, e.mh.Li_f));
+        std::vector<double> lb(e.rpad, 0.0);
+        for (int i = 0; i < p; ++i) {
+            double acc = 0.0;
+            for (int k = 0; k <= i; ++k) acc += e.h_LSi[(size_t)i * p + k] * e.h_mu[k];
+            lb[i] = -acc;
+        }
+        TRY_BUF(e.mh.lb.ensure((size_t)e.rpad * e.esz));
+        TRY(upload_T(e, e.mh.lb, lb.data(), e.rpad));
+        TRY_BUF(e.mh.w.ensure((size_t)p * (size_t)e.J * e.esz));
+    }
+    const size_t blk = (size_t)p * (size_t)e.J * e.esz;
+    TRY_BUF(e.mh.lin_g.ensure(blk)); TRY_BUF(e.mh.lin_gp.ensure(blk)); TRY_BUF(e.mh.lin_z.ensure(blk));
+    e.mh.lin = exp_params ? 2 : 1;
+    return CESX_OK;
+}
+
+// g = S^T grad phi of the states X with their data rows Gw (whitened for a dense Gamma) into `out`
+static int lin_grad(Engine& e, const void* X, const void* Gw, void* out, hipStream_t s) {
+    if (e.mh.lin == 1)
+        return launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.lin_Wa, .Wf = e.mh.lin_Wa_f, .ktot = e.kn + e.kp, .bias = e.mh.lin_ba,
+                                             .src = {{Gw, e.n, 0, 0}, {X, e.p, 0, 0}}, .nsrc = 2, .out = out}, s);
+    TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.lin_Wa, .Wf = e.mh.lin_Wa_f, .ktot = e.kn, .bias = e.mh.lin_ba,
+                                      .src = {{Gw, e.n, 0, 0}}, .nsrc = 1, .out = e.mh.lin_t}, s));
+    TRY(launch_lvlin_exph(e, X, e.mh.lin_t, s));
+    return launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.lin_Wb, .Wf = e.mh.lin_Wb_f, .ktot = 2 * e.kp, .bias = e.mh.lin_bb,
+                                         .src = {{e.mh.lin_t, e.p, 0, 0}, {X, e.p, 0, 0}}, .nsrc = 2, .out = out}, s);
+}
+
+// phi and g of the states X with their forward map G (start: into the engine's phi and g; accept: the test, U := X, g := g(X))
+static int lin_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s) {
+    WHITEN(e, G, s, true);
+    if (!e.diag_sigma)
+        TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.Li, .Wf = e.mh.Li_f, .ktot = e.kp, .bias = e.mh.lb,
+                                          .src = {{X, e.p, 0, 1}}, .nsrc = 1, .out = e.mh.w}, s));
+    TRY(lin_grad(e, X, G, start ? e.mh.lin_g.get() : e.mh.lin_gp.get(), s));
+    return launch_lvlin_score(e, start, X, G, U, logu, step, s);
+}
+
+// what every cesx_mh_langevin_lineal_* call behind the set needs before it looks at its own arguments
+static int lin_check_state(Engine& e, bool started) {
+    if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN || !e.mh.lin) { e.err = "cesx_mh_langevin_lineal: no lineal image (cesx_mh_langevin_lineal_set after cesx_mh_set_proposal with CESX_MH_LANGEVIN)"; return CESX_ESTATE; }
+    if (started && !(e.mh.started && e.mh.lin_started)) { e.err = "cesx_mh_langevin_lineal: the last start was not cesx_mh_langevin_lineal_start"; return CESX_ESTATE; }
+    return CESX_OK;
+}
+
+int cesx_mh_langevin_lineal_start(cesx_handle h, const void* U, const void* G, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(lin_check_state(e, false));
+    if (!U || !G) { e.err = "cesx_mh_langevin_lineal_start: null pointer"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(lin_score(e, true, U, G, nullptr, nullptr, 0u, (hipStream_t)stream));
+    e.mh.started = true;
+    e.mh.lin_started = true;
+    e.mh.lv_proposed = false;
+    e.mh.steps = 0;
+    return CESX_OK;
+}
+
+int cesx_mh_langevin_lineal_propose(cesx_handle h, uint64_t step_index, const void* U, const void* xi, void* P, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(lin_check_state(e, true));
+    if (!U || !P) { e.err = "cesx_mh_langevin_lineal_propose: null pointer"; return CESX_EINVAL; }
+    if (U == P) { e.err = "cesx_mh_langevin_lineal_propose: P must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_langevin_lineal_propose: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    hipStream_t s = (hipStream_t)stream;
+    // the block stays in engine memory: the accept step needs it again
+    if (xi) CESX_HIP(hipMemcpyAsync(e.mh.xi, xi, (size_t)e.p * (size_t)e.J * e.esz, hipMemcpyDeviceToDevice, s));
+    else TRY(launch_noise(e, mh_step_word(step_index), e.mh.xi, s));
+    TRY(launch_lvlin_z(e, s));
+    // P = U + S z: the random walk's triangular launch on z = xi - g / 2
+    TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.W, .Wf = e.mh.Wf, .ktot = e.kp,
+                                      .src = {{e.mh.lin_z, e.p, 0, 1}}, .nsrc = 1, .add1 = {U, nullptr, 1.0}, .out = P}, s));
+    e.mh.lv_proposed = true;
+    return CESX_OK;
+}
+
+int cesx_mh_langevin_lineal_accept(cesx_handle h, uint64_t step_index, void* U, const void* P, const void* GP, const double* logu,
+                                   void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(lin_check_state(e, true));
+    if (!e.mh.lv_proposed) { e.err = "cesx_mh_langevin_lineal_accept: no cesx_mh_langevin_lineal_propose since the start or the last accept"; return CESX_ESTATE; }
+    if (!U || !P || !GP) { e.err = "cesx_mh_langevin_lineal_accept: null pointer"; return CESX_EINVAL; }
+    if (U == P) { e.err = "cesx_mh_langevin_lineal_accept: P must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_langevin_lineal_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(lin_score(e, false, P, GP, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    e.mh.lv_proposed = false;
+    ++e.mh.steps;
+    return CESX_OK;
+}
+
+int cesx_mh_langevin_lineal_g(cesx_handle h, double* g_host) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(lin_check_state(e, true));
+    if (!g_host) { e.err = "cesx_mh_langevin_lineal_g: null pointer"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    const size_t len = (size_t)e.p * (size_t)e.J;
+    CESX_HIP(hipDeviceSynchronize());
+    if (e.cfg.dtype == CESX_F64) {
+        CESX_HIP(hipMemcpy(g_host, e.mh.lin_g, len * 8, hipMemcpyDeviceToHost));
+    } else {
+        std::vector<float> tmp(len);
+        CESX_HIP(hipMemcpy(tmp.data(), e.mh.lin_g, len * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < len; ++i) g_host[i] = (double)tmp[i];
+    }
     return CESX_OK;
 }
 

@@ -37,6 +37,8 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_darcy_set_streamed", "cesx_darcy_workspace_bytes", "cesx_lorenz_set", "cesx_lorenz_apply",
            "cesx_lorenz_three_set", "cesx_lorenz_three_apply", "cesx_map_set", "cesx_map_apply", "cesx_mh_run_map",
            "cesx_map_jac", "cesx_mh_langevin_start", "cesx_mh_langevin_propose", "cesx_mh_langevin_accept", "cesx_mh_langevin_run_map",
+           "cesx_mh_langevin_lineal_set", "cesx_mh_langevin_lineal_start", "cesx_mh_langevin_lineal_propose",
+           "cesx_mh_langevin_lineal_accept", "cesx_mh_langevin_lineal_g",
            "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read",
            "cesx_chain_hist_begin", "cesx_chain_hist_add", "cesx_chain_hist_read")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
@@ -304,6 +306,11 @@ def load_library(path=None):
     lib.cesx_mh_langevin_propose.argtypes = [vp, u64, vp, vp, vp, vp]
     lib.cesx_mh_langevin_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
     lib.cesx_mh_langevin_run_map.argtypes = [vp, u64, i32, i32, vp, vp, vp, vp, vp]
+    lib.cesx_mh_langevin_lineal_set.argtypes = [vp, dp, dp, i32]
+    lib.cesx_mh_langevin_lineal_start.argtypes = [vp, vp, vp, vp]
+    lib.cesx_mh_langevin_lineal_propose.argtypes = [vp, u64, vp, vp, vp, vp]
+    lib.cesx_mh_langevin_lineal_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+    lib.cesx_mh_langevin_lineal_g.argtypes = [vp, dp]
     lib.cesx_chain_summary_begin.argtypes = [vp, i32, vp]
     lib.cesx_chain_summary_add.argtypes = [vp, vp, i32, vp]
     lib.cesx_chain_summary_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1413,6 +1420,65 @@ class Engine:
                                                           None if xi is None else xi.data_ptr(),
                                                           None if logu is None else logu.data_ptr(), self._stream()))
         self._keep_mh_run = (U, trace, xi, logu)
+
+    # -- the Langevin step on a linear map: the gradient as update launches (include/cesx.h, cesx_mh_langevin_lineal_*) --
+    def _lvlin_check(self, who, tensors):
+        for name, t, rows, dt in tensors:
+            if t is not None and (t.dtype != dt or tuple(t.shape) != (rows, self.J) or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError("%s: %s must be a contiguous %s tensor of shape %s" % (who, name, dt, (rows, self.J)))
+
+    def mh_langevin_lineal_set(self, A, b=None, exp_params=False):
+        """Form and upload the gradient images of the linear map ``A X + b`` (``exp_params``: ``A exp(X) + b``) for the
+        installed problem and Langevin proposal (cesx_mh_langevin_lineal_set): ``A`` (n_obs, p), ``b`` None, a scalar or
+        (n_obs,).  ``set_problem`` and ``mh_set_proposal`` drop the images."""
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+        if A.shape != (self.n_obs, self.p):
+            raise ValueError("mh_langevin_lineal_set: A must be (n_obs, p) = %s, got %s" % ((self.n_obs, self.p), A.shape))
+        if b is not None:
+            b = np.asarray(b, dtype=np.float64)
+            if b.ndim > 1 or (b.ndim == 1 and b.shape[0] != self.n_obs):
+                raise ValueError("mh_langevin_lineal_set: b must be None, a scalar or (n_obs,), got %s" % (b.shape,))
+            b = np.ascontiguousarray(np.broadcast_to(b, (self.n_obs,)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_langevin_lineal_set(self._h, _dptr(A), None if b is None else _dptr(b), int(bool(exp_params))))
+
+    def mh_langevin_lineal_start(self, U, G):
+        """phi (with the prior term) and g = S^T grad phi of the current states ``U`` (p, J) from their forward map ``G``
+        (n_obs, J), both engine dtype; counters cleared (cesx_mh_langevin_lineal_start)."""
+        self._lvlin_check("mh_langevin_lineal_start", (("U", U, self.p, self.torch_dtype), ("G", G, self.n_obs, self.torch_dtype)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_langevin_lineal_start(self._h, U.data_ptr(), G.data_ptr(), self._stream()))
+        self._keep_ll_s = (U, G)
+
+    def mh_langevin_lineal_propose(self, step_index, U, xi=None, out=None):
+        """P = U + S (xi - g(U) / 2) (cesx_mh_langevin_lineal_propose); xi None: drawn on device in the MH counter domain
+        of step_index.  The engine keeps the block for ``mh_langevin_lineal_accept``."""
+        out = self.empty(self.p) if out is None else out
+        self._lvlin_check("mh_langevin_lineal_propose", (("U", U, self.p, self.torch_dtype), ("xi", xi, self.p, self.torch_dtype),
+                                                         ("out", out, self.p, self.torch_dtype)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_langevin_lineal_propose(self._h, int(step_index), U.data_ptr(),
+                                                                 None if xi is None else xi.data_ptr(), out.data_ptr(), self._stream()))
+        self._keep_ll_p = (U, xi, out)
+        return out
+
+    def mh_langevin_lineal_accept(self, step_index, U, P, GP, logu=None):
+        """phi(P) and g(P) from the map ``GP`` at P, the test with the Langevin correction, U := P and g := g(P) on the
+        accepted columns (cesx_mh_langevin_lineal_accept); logu as in ``mh_accept``."""
+        self._lvlin_check("mh_langevin_lineal_accept", (("U", U, self.p, self.torch_dtype), ("P", P, self.p, self.torch_dtype),
+                                                        ("GP", GP, self.n_obs, self.torch_dtype)))
+        if logu is not None and (logu.dtype != torch.float64 or logu.numel() != self.J or not logu.is_contiguous() or not logu.is_cuda):
+            raise ValueError("mh_langevin_lineal_accept: logu must be a contiguous float64 device tensor of J values")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_langevin_lineal_accept(self._h, int(step_index), U.data_ptr(), P.data_ptr(), GP.data_ptr(),
+                                                                None if logu is None else logu.data_ptr(), self._stream()))
+        self._keep_ll_a = (U, P, GP, logu)
+
+    def mh_langevin_lineal_g(self):
+        """The chains' g = S^T grad phi, float64 (p, J) on the host (cesx_mh_langevin_lineal_g; synchronises)."""
+        buf = np.zeros((self.p, self.J), dtype=np.float64)
+        self._check(self.lib.cesx_mh_langevin_lineal_g(self._h, _dptr(buf)))
+        return buf
 
     # -- streaming summaries of the chains' draws (include/cesx.h, cesx_chain_summary_*) --
     def chain_summary_begin(self, n_draws):

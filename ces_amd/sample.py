@@ -87,8 +87,14 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          On the device the step path is ``cesx_mh_langevin_*`` (the emulator's lv_* kernels on G and DG) and
                          ``fused=True`` the fused kernel ``mh_langevin_map_kernel`` (``cesx_mh_langevin_run_map``: the chain and its
                          g in one lane's registers); ``fused=None`` is ``LANGEVIN_FUSED_DEFAULT``.  A resume always scores the
-                         resumed states (phi and g).  A model without a Jacobian (``lineal``, ``lineal_log``, Darcy, every
-                         'pde' model) and ``flag_noise=True`` raise ``ValueError`` before an engine is created.
+                         resumed states (phi and g).  The linear maps take it after ``model.enable_gradient()``
+                         (``ces_amd.utils.lineal`` / ``lineal_log``, opt-in) at any p: their vector-Jacobian product
+                         A^T Gamma^{-1} (G - y) (``lineal_log``: times exp(u)) is a GEMM, so with ``chains=M`` the step is
+                         ``cesx_mh_langevin_lineal_*`` -- the gradient on the update kernels from images the engine forms
+                         once (``model.langevin_device``), z = xi - g / 2 and the random walk's triangular launch for the
+                         proposal, and one accept kernel (kernels_lvlin.hip) -- with no Jacobian image and no fused kernel
+                         (``fused=True`` raises).  A model without a Jacobian (a plain ``lineal`` / ``lineal_log``, Darcy,
+                         every 'pde' model) and ``flag_noise=True`` raise ``ValueError`` before an engine is created.
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -497,6 +503,10 @@ class MCMC(object):
         ``chains=M`` (build-only) runs M chains on the device (module docstring).  There a resume with
         ``noise='numpy'`` keeps the reference's phi of the start point; with ``noise='device'`` it is exact (phi of the
         resumed states, the step counter of the noise continues), so that two runs of n steps equal one of 2 n.
+        ``update='langevin'`` (build-only): the Metropolis-adjusted Langevin step for a model that offers its gradient --
+        ``elliptic`` and ``banana`` (``jacobian`` / ``jacobian_device``), ``lineal`` and ``lineal_log`` after
+        ``enable_gradient()`` (``jacobian`` / ``langevin_device``: the adjoint launches of cesx_mh_langevin_lineal_*, at any
+        p); module docstring.
         """
         if kwargs.get("update", None) == "langevin":      # build-only; refused before any engine is created
             self._model_langevin_refusals(model, prior, kwargs.get("chains", None) is not None)
@@ -568,11 +578,12 @@ class MCMC(object):
     def _model_langevin_refusals(model, prior, device):
         """What ``model_mh(update='langevin')`` cannot do, host and device alike: every refusal is a ValueError with the reason."""
         need = "jacobian_device" if device else "jacobian"
-        if getattr(model, "type", None) == "pde" or not hasattr(model, "jacobian") or not hasattr(model, need):
+        has = hasattr(model, need) or (device and hasattr(model, "langevin_device"))      # (langevin_device: the adjoint launch of the linear maps)
+        if getattr(model, "type", None) == "pde" or not hasattr(model, "jacobian") or not has:
             raise ValueError("update='langevin' needs the gradient of phi, and %r offers no Jacobian (model.%s; "
-                             "ces_amd.utils.elliptic and banana do): the gradient of lineal and lineal_log is an A^T product "
-                             "and the Darcy and Lorenz models have no adjoint; gp_mh(update='langevin') differentiates the "
-                             "emulator instead" % (model, need))
+                             "ces_amd.utils.elliptic and banana do, lineal and lineal_log after enable_gradient(): their "
+                             "gradient is an A^T product); the Darcy and Lorenz models have no adjoint; "
+                             "gp_mh(update='langevin') differentiates the emulator instead" % (model, need))
         if getattr(model, "flag_noise", False):
             raise ValueError("update='langevin': a noisy map (flag_noise=True) has no gradient of phi")
         if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
@@ -917,6 +928,33 @@ class MCMC(object):
                 eng.mh_langevin_run_map(step, K, U, stride=stride, trace=trace, xi=xi, logu=logu)
             return lv_start, lv_accept, run_steps if fused else None, lv_propose
 
+        def bind_langevin_lineal(eng, M):
+            # a linear map (lineal / lineal_log after enable_gradient()): the gradient is an A^T product of the engine's own
+            # (cesx_mh_langevin_lineal_*), so a step is the forward map and the engine's launches -- no Jacobian image
+            takes_out = hook_takes_out(model.forward_device)
+            G, GP = eng.empty(n), eng.empty(n)
+            model.langevin_device(eng)
+
+            def fwd(u, out):
+                if takes_out:
+                    return model.forward_device(eng, u, out=out)
+                out.copy_(model.forward_device(eng, u))
+                return out
+
+            def lv_start(U):
+                fwd(U, G)
+                eng.mh_langevin_lineal_start(U, G)
+
+            def lv_propose(step, U, xi, P):
+                eng.mh_langevin_lineal_propose(step, U, xi=xi, out=P)
+
+            def lv_accept(step, U, P, logu):
+                fwd(P, GP)
+                eng.mh_langevin_lineal_accept(step, U, P, GP, logu=logu)
+            return lv_start, lv_accept, None, lv_propose
+
+        if langevin and not hasattr(model, "jacobian_device"):
+            bind_langevin = bind_langevin_lineal
         # a resume under update='langevin' scores the resumed states whatever the noise: the chains need their g as well as phi
         self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_langevin if langevin else bind_pde if pde else bind,
                         resume_keeps_start_phi=not langevin, fused=fused, langevin=langevin)

@@ -85,6 +85,34 @@ class lineal(object):
             self._dev_token = engine.forward_set_lineal(np.asarray(self.A), b)      # (another model may have installed its map)
             self._dev_A, self._dev_b, self._dev_fp = self.A, self.b, fp
 
+    _exp_params = False        # lineal_log: the map acts on exp(theta)
+
+    def enable_gradient(self):
+        """Offer the gradient of the map to ``MCMC.model_mh(update='langevin')`` (build-only, opt-in: without this call the
+        instance has neither attribute and the sampler refuses it as before).  The instance gains
+
+        ``jacobian(theta)``          on the host, (n_obs, p): ``A`` (``lineal_log``: ``A * exp(theta)[None, :]``)
+        ``langevin_device(engine)``  with ``chains=M``: installs the map and hands A and b to the engine's adjoint images
+                                     (cesx_mh_langevin_lineal_set), after which the Langevin step never forms a Jacobian: its
+                                     gradient is an A^T product on the update kernels.
+        Returns ``self``."""
+        def jacobian(theta):
+            A = np.asarray(self.A, dtype=np.float64)
+            if not self._exp_params:
+                return A.copy()
+            return A * np.exp(np.asarray(theta, dtype=np.float64).reshape(-1))[None, :]
+
+        def langevin_device(engine):
+            self.ensure_installed(engine)
+            b = None
+            if np.ndim(self.b) > 0 or self.b != 0:
+                b = np.broadcast_to(np.asarray(self.b, dtype=np.float64), (self.n_obs,))
+            engine.mh_langevin_lineal_set(np.asarray(self.A, dtype=np.float64), b, exp_params=self._exp_params)
+
+        self.jacobian = jacobian
+        self.langevin_device = langevin_device
+        return self
+
 
 class _map_hook(object):
     """The device hook of the closed-form maps (build-only): one descriptor (``_map_desc``) installed in the engine's map
@@ -133,6 +161,7 @@ class lineal_log(lineal):
     engine_lineal = False      # G's moments do NOT follow from U's through A (ShardedUpdate.lineal_fast_ok): A acts on exp(U)
     map_kind = "exp"
     fused_kind = False
+    _exp_params = True
 
     def __init__(self, A, flag_noise=False):
         super().__init__(A, flag_noise=flag_noise)

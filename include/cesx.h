@@ -620,6 +620,34 @@ int cesx_mh_langevin_accept(cesx_handle h, uint64_t step_index, void* U_dev, con
    Neither launches anything. */
 int cesx_mh_langevin_run_map(cesx_handle h, uint64_t step_index, int n_steps, int stride, void* U_dev, void* trace_dev,
                              const void* xi_dev, const double* logu_dev, void* stream);
+/* The same Langevin step for the LINEAR maps at any p (ces_amd.utils lineal: G = A X + b; lineal_log: G = A exp(X) + b, exp_params
+   1), where an [n][p][J] Jacobian image is out of the question: the step needs only the vector-Jacobian product
+       t = A^T Gamma^{-1} (G - y)   (lineal_log: exp(X) (.) that),   grad phi = t + Sigma^{-1} (X - mu),   g = S^T grad phi,
+   which is a GEMM on the update kernels (kernels_lvlin.hip holds the rest).  phi, the proposal, the test, log u, the noise
+   block and its counter words are cesx_mh_langevin_*'s; no log-Jacobian term is added for exp_params.
+       cesx_mh_langevin_lineal_set       forms the coefficient images on the host in fp64 from A_host [n_obs][p] and the engine's Gamma,
+                                         y, Sigma, mu (cesx_set_problem) and S (cesx_mh_set_proposal), and uploads them.  b_host
+                                         ([n_obs] or NULL) is checked and not stored: it reaches the gradient through G_dev alone.
+                                         cesx_set_problem and cesx_mh_set_proposal drop the images.  Synchronises.
+       cesx_mh_langevin_lineal_start     phi(U) and g(U) from U_dev and G_dev = the map at U ([n_obs][J_local], engine dtype); counters cleared
+       cesx_mh_langevin_lineal_propose   P = U + S (xi - g(U) / 2); the block is kept in engine memory
+       cesx_mh_langevin_lineal_accept    phi(P), g(P) from G_dev at P, the test, and on the accepted columns U := P, phi := phi(P),
+                                         g := g(P), counter + 1.  NaN anywhere in a chain's sums rejects that chain alone.
+       cesx_mh_langevin_lineal_g         the chains' g, fp64 on the host, [p][J_local]; synchronises
+   phi equals cesx_mh_start's for the same problem bit for bit; g, g(P) and z = xi - g / 2 are [p][J_local] blocks of the engine
+   dtype in engine memory.  The two families share phi, the counters, cesx_mh_stats and cesx_mh_phi, but not g: after a
+   cesx_mh_langevin_lineal_start, cesx_mh_langevin_propose / _accept / _run_map return CESX_ESTATE until a start of their own,
+   and the other way round.
+   CESX_ESTATE: set without cesx_set_problem or a proposal of kind CESX_MH_LANGEVIN; start without a set; propose, accept and g
+   unless the LAST start was cesx_mh_langevin_lineal_start; accept also without a propose since the start or the last accept.
+   CESX_EINVAL for a null pointer (b_host, xi_dev and logu_dev may be NULL), exp_params other than 0 or 1, a non-finite A or b,
+   P_dev aliasing U_dev or a step index >= 2^31.  None of these launches anything or touches U_dev, phi or the counters. */
+int cesx_mh_langevin_lineal_set(cesx_handle h, const double* A_host, const double* b_host, int exp_params);
+int cesx_mh_langevin_lineal_start(cesx_handle h, const void* U_dev, const void* G_dev, void* stream);
+int cesx_mh_langevin_lineal_propose(cesx_handle h, uint64_t step_index, const void* U_dev, const void* xi_dev, void* P_dev, void* stream);
+int cesx_mh_langevin_lineal_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* P_dev, const void* G_dev,
+                                   const double* logu_dev, void* stream);
+int cesx_mh_langevin_lineal_g(cesx_handle h, double* g_host);
 
 /* ---- Streaming summaries of the chains' draws (MCMC(..., chains=M, summary=True); kernels_chainsum.hip) --
    The sums behind the pooled mean and covariance, the split R-hat and an effective sample size of a run of
