@@ -831,6 +831,14 @@ int launch_mh_run_map(Engine& e, uint64_t step_index, int n_steps, int stride, v
 int launch_map_jac(Engine& e, const void* U, double* G, double* DG, hipStream_t s);
 int launch_mh_langevin_run_map(Engine& e, uint64_t step_index, int n_steps, int stride, void* U, void* trace, const void* xi,
                                const double* logu, hipStream_t s);
+// kernels_hmc.hip: the leapfrog step on the rows and gradients lv_score reads (cesx_mh_hmc_* / cesx_gp_hmc_*).  what 0: r (mh.hm_r)
+// and the first Q from U, the block in mh.xi and mh.lv_g; 1: phi(Q), g(Q), the full kick, Q advanced in place; 2: the last Q
+// with its rows, the half kick, the test, U := Q, phi and g on the accepted columns.  kernels_maps.hip: n_steps such steps of
+// `leapfrog` positions each in one launch for the installed map of a fused kind
+int launch_hmc(Engine& e, int what, int mode, void* Q, const double* mean, const double* var, const double* dmean,
+               const double* dvar, void* U, const double* logu, unsigned step, hipStream_t s);
+int launch_mh_hmc_run_map(Engine& e, uint64_t step_index, int n_steps, int leapfrog, int stride, void* U, void* trace,
+                          const void* xi, const double* logu, hipStream_t s);
 
 // kernels_chainsum.hip: the stage behind cesx_chain_summary_* (include/cesx.h); the entry points have checked the state
 int chainsum_begin(Engine& e, long long n_draws);

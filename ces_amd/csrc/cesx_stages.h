@@ -30,6 +30,9 @@ struct MhState {
     std::vector<double> h_bS;          // [p][p] b S on the host: cesx_mh_run_map passes it by value
     DevBuf<double> lv_g, lv_gp;        // Langevin: [p][J] g = S^T grad phi of the chains' states and of the proposals (kernels_gpgrad.hip)
     DevBuf<double> lv_a, lv_b, lv_gphi; // Langevin: [n][J], [n][J], [p][J] what lv_score keeps per chain: a_i, b_i, grad phi
+    // HMC under a Langevin proposal (cesx_mh_hmc_* / cesx_gp_hmc_*, kernels_hmc.hip): the chains' phi, g and noise block are the Langevin step's
+    bool hm_begun = false;             // a cesx_mh_hmc_begin since the start or the last accept: xi and hm_r belong to a trajectory in flight
+    DevBuf<double> hm_r;               // [p][J] the momentum r of the trajectory in flight
     // Langevin on a linear map (cesx_mh_langevin_lineal_*, kernels_lvlin.hip): the gradient is an update launch over these images
     int lin = 0;                       // 0: no cesx_mh_langevin_lineal_set; 1: lineal (one launch); 2: lineal_log (two launches and exp)
     bool lin_started = false;          // the LAST start was cesx_mh_langevin_lineal_start: g lives in lin_g, not in lv_g
@@ -39,7 +42,7 @@ struct MhState {
     DevBuf<void> lin_g, lin_gp, lin_z; // [p][J] engine dtype: g of the chains' states, of the proposals, and z = xi - g / 2
     DevBuf<void> lin_t;                // lineal_log: [p][J] t0, then h = exp(X) (.) t0
     bool none() const { return kind < 0; }
-    void drop() { kind = -1; started = false; lv_proposed = false; lin = 0; lin_started = false; }      // every buffer is sized by the engine: kept
+    void drop() { kind = -1; started = false; lv_proposed = false; hm_begun = false; lin = 0; lin_started = false; }      // every buffer is sized by the engine: kept
 };
 
 // ---- GP emulator over the columns (cesx_gp_*, kernels_gp.hip) ----

@@ -905,7 +905,7 @@ int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) 
     if (e.cfg.dtype == CESX_F64 || kind == CESX_MH_LANGEVIN) TRY_BUF(e.mh.xi.ensure((size_t)p * (size_t)e.J * e.esz));
     if (kind == CESX_MH_LANGEVIN) {            // what the lv_* kernels keep per chain (kernels_gpgrad.hip)
         TRY_BUF(e.mh.lv_g.ensure((size_t)p * (size_t)e.J * 8)); TRY_BUF(e.mh.lv_gp.ensure((size_t)p * (size_t)e.J * 8));
-        TRY_BUF(e.mh.lv_gphi.ensure((size_t)p * (size_t)e.J * 8));
+        TRY_BUF(e.mh.lv_gphi.ensure((size_t)p * (size_t)e.J * 8)); TRY_BUF(e.mh.hm_r.ensure((size_t)p * (size_t)e.J * 8));
         TRY_BUF(e.mh.lv_a.ensure((size_t)e.n * (size_t)e.J * 8)); TRY_BUF(e.mh.lv_b.ensure((size_t)e.n * (size_t)e.J * 8));
     }
     TRY_BUF(e.mh.phi.ensure((size_t)e.J * 8)); TRY_BUF(e.mh.cnt.ensure((size_t)e.J * 8));
@@ -1242,7 +1242,7 @@ int cesx_gp_langevin_start(cesx_handle h, int mode, const void* U, const double*
     TRY(launch_gp_langevin(e, 0, mode, U, mean, var, dmean, dvar, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream));
     e.mh.started = true;
     e.mh.lin_started = false;
-    e.mh.lv_proposed = false;
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;
     e.mh.steps = 0;
     return CESX_OK;
 }
@@ -1261,7 +1261,7 @@ int cesx_gp_langevin_propose(cesx_handle h, uint64_t step_index, const void* U, 
     if (xi) CESX_HIP(hipMemcpyAsync(e.mh.xi, xi, (size_t)e.p * (size_t)e.J * e.esz, hipMemcpyDeviceToDevice, s));
     else TRY(launch_noise(e, mh_step_word(step_index), e.mh.xi, s));
     TRY(launch_gp_langevin(e, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, const_cast<void*>(U), P, nullptr, 0u, s));
-    e.mh.lv_proposed = true;
+    e.mh.lv_proposed = true; e.mh.hm_begun = false;      // (the block of a trajectory in flight is overwritten)
     return CESX_OK;
 }
 
@@ -1278,7 +1278,7 @@ int cesx_gp_langevin_accept(cesx_handle h, int mode, uint64_t step_index, void* 
     SET_DEVICE(e);
     FLUSH(e);
     TRY(launch_gp_langevin(e, 2, mode, P, mean, var, dmean, dvar, U, nullptr, logu, mh_step_word(step_index), (hipStream_t)stream));
-    e.mh.lv_proposed = false;
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;
     ++e.mh.steps;
     return CESX_OK;
 }
@@ -1864,7 +1864,7 @@ int cesx_mh_langevin_start(cesx_handle h, const void* U, const double* G, const 
     TRY(launch_gp_langevin(e, 0, CESX_GP_GAMMA, U, G, nullptr, DG, nullptr, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream));
     e.mh.started = true;
     e.mh.lin_started = false;
-    e.mh.lv_proposed = false;
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;
     e.mh.steps = 0;
     return CESX_OK;
 }
@@ -1883,7 +1883,7 @@ int cesx_mh_langevin_propose(cesx_handle h, uint64_t step_index, const void* U, 
     if (xi) CESX_HIP(hipMemcpyAsync(e.mh.xi, xi, (size_t)e.p * (size_t)e.J * e.esz, hipMemcpyDeviceToDevice, s));
     else TRY(launch_noise(e, mh_step_word(step_index), e.mh.xi, s));
     TRY(launch_gp_langevin(e, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, const_cast<void*>(U), P, nullptr, 0u, s));
-    e.mh.lv_proposed = true;
+    e.mh.lv_proposed = true; e.mh.hm_begun = false;      // (the block of a trajectory in flight is overwritten)
     return CESX_OK;
 }
 
@@ -1899,7 +1899,7 @@ int cesx_mh_langevin_accept(cesx_handle h, uint64_t step_index, void* U, const v
     SET_DEVICE(e);
     FLUSH(e);
     TRY(launch_gp_langevin(e, 2, CESX_GP_GAMMA, P, G, nullptr, DG, nullptr, U, nullptr, logu, mh_step_word(step_index), (hipStream_t)stream));
-    e.mh.lv_proposed = false;
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;
     ++e.mh.steps;
     return CESX_OK;
 }
@@ -1916,7 +1916,112 @@ int cesx_mh_langevin_run_map(cesx_handle h, uint64_t step_index, int n_steps, in
     SET_DEVICE(e);
     FLUSH(e);
     TRY(launch_mh_langevin_run_map(e, step_index, n_steps, stride, U, trace, xi, logu, (hipStream_t)stream));
-    e.mh.lv_proposed = false;              // (a block proposed before the launch belongs to a state the chains have left)
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;              // (a block proposed before the launch belongs to a state the chains have left)
+    e.mh.steps += (unsigned long long)n_steps;
+    return CESX_OK;
+}
+
+// ---- leapfrog HMC under a Langevin proposal (include/cesx.h; kernels_hmc.hip, mh_hmc_map_kernel of kernels_maps.hip) ----
+
+// what every cesx_mh_hmc_* / cesx_gp_hmc_* call needs before it looks at its own arguments; `begun`: a cesx_mh_hmc_begin too
+static int hmc_check_state(Engine& e, bool begun) {
+    if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_hmc: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
+    if (!e.mh.started || e.mh.lin_started) { e.err = "cesx_hmc: cesx_mh_langevin_start / cesx_gp_langevin_start has not been called (the last start was not one of them)"; return CESX_ESTATE; }
+    if (begun && !e.mh.hm_begun) { e.err = "cesx_hmc: no cesx_mh_hmc_begin since the start or the last accept"; return CESX_ESTATE; }
+    return CESX_OK;
+}
+
+int cesx_mh_hmc_begin(cesx_handle h, uint64_t step_index, const void* U, const void* xi, void* Q, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hmc_check_state(e, false));
+    if (!U || !Q) { e.err = "cesx_mh_hmc_begin: null pointer"; return CESX_EINVAL; }
+    if (U == Q) { e.err = "cesx_mh_hmc_begin: Q must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_hmc_begin: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    hipStream_t s = (hipStream_t)stream;
+    // the block stays in engine memory, as the Langevin proposal keeps it: the accept step needs |xi|^2
+    if (xi) CESX_HIP(hipMemcpyAsync(e.mh.xi, xi, (size_t)e.p * (size_t)e.J * e.esz, hipMemcpyDeviceToDevice, s));
+    else TRY(launch_noise(e, mh_step_word(step_index), e.mh.xi, s));
+    TRY(launch_hmc(e, 0, 0, Q, nullptr, nullptr, nullptr, nullptr, const_cast<void*>(U), nullptr, 0u, s));
+    e.mh.hm_begun = true;
+    e.mh.lv_proposed = false;              // (a Langevin proposal's block is overwritten)
+    return CESX_OK;
+}
+
+int cesx_mh_hmc_leap(cesx_handle h, void* Q, const double* G, const double* DG, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hmc_check_state(e, true));
+    if (!Q || !G || !DG) { e.err = "cesx_mh_hmc_leap: null pointer"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    return launch_hmc(e, 1, CESX_GP_GAMMA, Q, G, nullptr, DG, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream);
+}
+
+int cesx_mh_hmc_accept(cesx_handle h, uint64_t step_index, void* U, const void* Q, const double* G, const double* DG,
+                       const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hmc_check_state(e, true));
+    if (!U || !Q || !G || !DG) { e.err = "cesx_mh_hmc_accept: null pointer"; return CESX_EINVAL; }
+    if (U == Q) { e.err = "cesx_mh_hmc_accept: Q must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_hmc_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_hmc(e, 2, CESX_GP_GAMMA, const_cast<void*>(Q), G, nullptr, DG, nullptr, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    e.mh.hm_begun = false;
+    ++e.mh.steps;
+    return CESX_OK;
+}
+
+int cesx_gp_hmc_leap(cesx_handle h, int mode, void* Q, const double* mean, const double* var, const double* dmean,
+                     const double* dvar, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hmc_check_state(e, true));
+    if (e.gp.none()) { e.err = "cesx_gp_hmc_leap: cesx_gp_set has not been called"; return CESX_ESTATE; }
+    if (!Q) { e.err = "cesx_gp_hmc_leap: null pointer"; return CESX_EINVAL; }
+    TRY(langevin_check_mode(e, mode, mean, var, dmean, dvar));
+    SET_DEVICE(e);
+    FLUSH(e);
+    return launch_hmc(e, 1, mode, Q, mean, var, dmean, dvar, nullptr, nullptr, 0u, (hipStream_t)stream);
+}
+
+int cesx_gp_hmc_accept(cesx_handle h, int mode, uint64_t step_index, void* U, const void* Q, const double* mean,
+                       const double* var, const double* dmean, const double* dvar, const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hmc_check_state(e, true));
+    if (e.gp.none()) { e.err = "cesx_gp_hmc_accept: cesx_gp_set has not been called"; return CESX_ESTATE; }
+    if (!U || !Q) { e.err = "cesx_gp_hmc_accept: null pointer"; return CESX_EINVAL; }
+    if (U == Q) { e.err = "cesx_gp_hmc_accept: Q must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_gp_hmc_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    TRY(langevin_check_mode(e, mode, mean, var, dmean, dvar));
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_hmc(e, 2, mode, const_cast<void*>(Q), mean, var, dmean, dvar, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    e.mh.hm_begun = false;
+    ++e.mh.steps;
+    return CESX_OK;
+}
+
+int cesx_mh_hmc_run_map(cesx_handle h, uint64_t step_index, int n_steps, int leapfrog, int stride, void* U, void* trace,
+                        const void* xi, const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!U) { e.err = "cesx_mh_hmc_run_map: null pointer"; return CESX_EINVAL; }
+    if (n_steps < 1 || stride < 1) { e.err = "cesx_mh_hmc_run_map: n_steps and stride must be >= 1"; return CESX_EINVAL; }
+    if (leapfrog < 1 || leapfrog > CESX_HMC_LEAPFROG_MAX) { e.err = "cesx_mh_hmc_run_map: leapfrog must be in 1 .. 64"; return CESX_EINVAL; }
+    if ((long long)n_steps * leapfrog > CESX_HMC_LAUNCH_GRADS_MAX) { e.err = "cesx_mh_hmc_run_map: n_steps * leapfrog is limited to 4096 gradient evaluations per launch"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull || step_index + (uint64_t)n_steps > 0x80000000ull) { e.err = "cesx_mh_hmc_run_map: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    TRY(hmc_check_state(e, false));
+    if (!e.mp.fused()) { e.err = "cesx_mh_hmc_run_map: no map of a fused kind is installed (cesx_map_set: CESX_MAP_ELLIPTIC or CESX_MAP_BANANA)"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(launch_mh_hmc_run_map(e, step_index, n_steps, leapfrog, stride, U, trace, xi, logu, (hipStream_t)stream));
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;      // (a block drawn before the launch belongs to a state the chains have left)
     e.mh.steps += (unsigned long long)n_steps;
     return CESX_OK;
 }
@@ -1962,7 +2067,7 @@ int cesx_mh_langevin_lineal_set(cesx_handle h, const double* A, const double* b,
     FLUSH(e);
     CESX_HIP(hipDeviceSynchronize());          // (the images below may be read by launches still in flight)
     if (e.mh.lin_started) e.mh.started = false;        // (the chains' g belonged to the old image)
-    e.mh.lin = 0; e.mh.lin_started = false; e.mh.lv_proposed = false;
+    e.mh.lin = 0; e.mh.lin_started = false; e.mh.lv_proposed = false; e.mh.hm_begun = false;
     // B = A^T M, p x n, with M (G~ - y~) = Gamma^{-1} (G - y) for the rows G~ the score kernel reads: Gamma^{-1} itself on the
     // caller's rows (diagonal), L_Gamma^{-T} on the whitened ones (dense: B[q][i] = sum_{k <= i} A[k][q] Li[i][k])
     std::vector<double> B((size_t)p * n, 0.0);
@@ -2086,7 +2191,7 @@ int cesx_mh_langevin_lineal_start(cesx_handle h, const void* U, const void* G, v
     TRY(lin_score(e, true, U, G, nullptr, nullptr, 0u, (hipStream_t)stream));
     e.mh.started = true;
     e.mh.lin_started = true;
-    e.mh.lv_proposed = false;
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;
     e.mh.steps = 0;
     return CESX_OK;
 }
@@ -2108,7 +2213,7 @@ int cesx_mh_langevin_lineal_propose(cesx_handle h, uint64_t step_index, const vo
     // P = U + S z: the random walk's triangular launch on z = xi - g / 2
     TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.W, .Wf = e.mh.Wf, .ktot = e.kp,
                                       .src = {{e.mh.lin_z, e.p, 0, 1}}, .nsrc = 1, .add1 = {U, nullptr, 1.0}, .out = P}, s));
-    e.mh.lv_proposed = true;
+    e.mh.lv_proposed = true; e.mh.hm_begun = false;      // (the block of a trajectory in flight is overwritten)
     return CESX_OK;
 }
 
@@ -2124,7 +2229,7 @@ int cesx_mh_langevin_lineal_accept(cesx_handle h, uint64_t step_index, void* U, 
     SET_DEVICE(e);
     FLUSH(e);
     TRY(lin_score(e, false, P, GP, U, logu, mh_step_word(step_index), (hipStream_t)stream));
-    e.mh.lv_proposed = false;
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;
     ++e.mh.steps;
     return CESX_OK;
 }

@@ -25,6 +25,10 @@
 //                            log u < phi(U) - phi(P) + |xi|^2 / 2 - |xi - (g(U) + g(P)) / 2|^2 / 2  ->  U, phi, g := those of P
 //                        The chains' g comes from and goes back to mh.lv_g, where the lv_* kernels keep it: fused launches and
 //                        single Langevin steps alternate.
+//   mh_hmc_map_kernel    mh_langevin_map_kernel with the leapfrog loop inside (MCMC.model_mh(chains=M, update='hmc'), include/cesx.h,
+//                        cesx_mh_hmc_run_map): per step r = xi - g(U) / 2, then `leapfrog` times x = x + S r, phi(x), g(x),
+//                        r = r - g(x) (half at the last), and the test with both kinetic energies.  It shares phi, g and the
+//                        counters with the kernel above and with the hm_* step kernels (kernels_hmc.hip).
 //
 // The noise is the step path's: xi row r of global chain gj at MH step s from philox(gj, r / 4, s | 2^31) through normal4 in
 // fp64 (what noise_kernel<double> draws for an fp64 engine -- for EITHER engine dtype here, so that an fp32 engine's launch is
@@ -533,6 +537,138 @@ int launch_mh_langevin_run_map(Engine& e, uint64_t step_index, int n_steps, int 
     case CESX_MAP_ELLIPTIC: return f32 ? mh_langevin_map_t<float, MapElliptic>(e, a, s) : mh_langevin_map_t<double, MapElliptic>(e, a, s);
     case CESX_MAP_BANANA: return f32 ? mh_langevin_map_t<float, MapBanana>(e, a, s) : mh_langevin_map_t<double, MapBanana>(e, a, s);
     default: e.err = "cesx_mh_langevin_run_map: the installed map has no fused kernel"; return CESX_ESTATE;
+    }
+}
+
+// ---- the fused HMC kernel ----
+
+// mh_langevin_map_kernel with the leapfrog loop inside (include/cesx.h, cesx_mh_hmc_run_map): per step the lane draws xi, forms
+// r = xi - g(U) / 2 and walks `leapfrog` positions x = x + S r, scoring each with map_lv_score and kicking r by g(x) (by
+// g(x) / 2 at the last), then tests log u < phi(U) - phi(x) + (|xi|^2 / 2 - |r|^2 / 2).  The sums are the hm_* kernels'
+// (kernels_hmc.hip) in their order, so on an fp64 engine the launch leaves the step path's U, phi and g bit for bit; the chain,
+// phi, g, r, xi's norm and the Jacobian stay in the lane's registers, and the trajectory is fp64 whatever the engine dtype
+// (the step path of an fp32 engine rounds Q after every leapfrog; this kernel rounds on the stores alone).
+template <typename T, typename Map, int DENSE>
+__global__ __launch_bounds__(MAP_THREADS)
+void mh_hmc_map_kernel(const Map map, const MapLangevinProblem<Map::P, Map::N> q, const MapRunArgs a, double* __restrict__ lv_g,
+                       const int leapfrog) {
+    constexpr int P = Map::P, N = Map::N, NQ = (P + 3) / 4;
+    const long long j = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
+    if (j >= a.J) return;
+    // the lane's own addresses in vector registers, as in mh_run_map_kernel
+    T* __restrict__ Uj = (T*)a.U + j;
+    double* __restrict__ gj_p = lv_g + j;
+    T* __restrict__ tp = a.trace ? (T*)a.trace + j : nullptr;
+    const T* __restrict__ xp = a.xi ? (const T*)a.xi + j : nullptr;
+    const double* __restrict__ lp = a.logu ? a.logu + j : nullptr;
+    const unsigned long long gj = (unsigned long long)(a.j_offset + j);
+    double u[P], gu[P];
+#pragma unroll
+    for (int r = 0; r < P; ++r) { u[r] = (double)Uj[(size_t)r * a.J]; gu[r] = gj_p[(size_t)r * a.J]; }
+    double ph = a.phi[j];
+    unsigned long long cnt = a.cnt[j];
+    int since = 0;
+    for (int k = 0; k < a.n_steps; ++k) {
+        const unsigned step = a.step0 + (unsigned)k;          // (step0 carries the MH domain bit): ONE step index whatever leapfrog is
+        double x[P], rm[P], gx[P], n1 = 0.0;
+        {   // ---- begin: r = xi - g(U) / 2 and |xi|^2, hm_begin_kernel's and hm_accept_kernel's sums ----
+            double z[4 * NQ];
+            if (xp) {
+#pragma unroll
+                for (int r = 0; r < P; ++r) z[r] = (double)xp[(size_t)r * a.J];
+                xp += (size_t)P * a.J;
+            } else {
+#pragma unroll
+                for (int c = 0; c < NQ; ++c)
+                    normal4(philox4x32_10((uint32_t)gj, (uint32_t)(gj >> 32), (uint32_t)c, step, a.seed_lo, a.seed_hi), z + 4 * c);
+            }
+#pragma unroll
+            for (int r = 0; r < P; ++r) { rm[r] = z[r] - 0.5 * gu[r]; n1 = fma(z[r], z[r], n1); x[r] = u[r]; }
+        }
+        // ---- the trajectory (any NaN or infinity ends in a false comparison, as on the step path) ----
+        double php = 0.0;
+        for (int l = 1; l <= leapfrog; ++l) {
+#pragma unroll
+            for (int r = 0; r < P; ++r) {
+                double acc = 0.0;
+#pragma unroll
+                for (int c = 0; c <= r; ++c) acc = fma(q.S[r * (r + 1) / 2 + c], rm[c], acc);
+                x[r] = x[r] + acc;
+            }
+            double g[N], DG[N][P];
+            map.map_jac(x, g, DG);
+            php = map_lv_score<P, N, DENSE>(q, x, g, DG, gx);
+            if (l < leapfrog) {
+#pragma unroll
+                for (int r = 0; r < P; ++r) rm[r] = rm[r] - gx[r];
+                if (!(php - php == 0.0)) rm[0] = __builtin_nan("");
+            }
+        }
+        double n2 = 0.0;
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            const double d = rm[r] - 0.5 * gx[r];
+            n2 = fma(d, d, n2);
+        }
+        double lu;
+        if (lp) { lu = *lp; lp += a.J; }
+        else lu = mh_log_uniform(gj, step, a.seed_lo, a.seed_hi);
+        if (lu < ph - php + (0.5 * n1 - 0.5 * n2)) {
+#pragma unroll
+            for (int r = 0; r < P; ++r) { u[r] = x[r]; gu[r] = gx[r]; }
+            ph = php;
+            cnt += 1ull;
+        }
+        if (tp && ++since == a.stride) {
+            since = 0;
+#pragma unroll
+            for (int r = 0; r < P; ++r) tp[(size_t)r * a.J] = (T)u[r];
+            tp += (size_t)P * a.J;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < P; ++r) { Uj[(size_t)r * a.J] = (T)u[r]; gj_p[(size_t)r * a.J] = gu[r]; }
+    a.phi[j] = ph;
+    a.cnt[j] = cnt;
+}
+
+template <typename T, typename Map>
+static int mh_hmc_map_t(Engine& e, const MapRunArgs& a, int leapfrog, hipStream_t s) {
+    constexpr int P = Map::P, N = Map::N;
+    MapLangevinProblem<P, N> q{};                   // (filled as mh_langevin_map_t fills it: lv_score's numbers)
+    for (int r = 0; r < N; ++r) {
+        for (int k = 0; k <= r; ++k) q.Lg[r * (r + 1) / 2 + k] = e.whiten ? e.h_Li[(size_t)r * N + k] : k == r ? e.h_gw[r] : 0.0;
+        q.y[r] = e.h_yw[r];
+    }
+    for (int r = 0; r < P; ++r) {
+        for (int k = 0; k <= r; ++k) {
+            q.S[r * (r + 1) / 2 + k] = e.mh.h_bS[(size_t)r * P + k];
+            q.Ls[r * (r + 1) / 2 + k] = e.diag_sigma ? (k == r ? e.h_sw[r] : 0.0) : e.h_LSi[(size_t)r * P + k];
+        }
+        q.mu[r] = e.h_mu[r];
+    }
+    const long long blocks = (e.J + MAP_THREADS - 1) / MAP_THREADS;
+    if (blocks >= (1LL << 31)) { e.err = "cesx_mh_hmc_run_map: too many chains for one launch"; return CESX_EUNSUPPORTED; }
+    double* lv_g = e.mh.lv_g.get();
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(MAP_THREADS), 0, s, Map(e.mp.desc.prm), q, a, lv_g, leapfrog); };
+    switch ((e.whiten ? 1 : 0) | (e.diag_sigma ? 0 : 2)) {
+    case 0: launch(mh_hmc_map_kernel<T, Map, 0>); break;
+    case 1: launch(mh_hmc_map_kernel<T, Map, 1>); break;
+    case 2: launch(mh_hmc_map_kernel<T, Map, 2>); break;
+    default: launch(mh_hmc_map_kernel<T, Map, 3>); break;
+    }
+    CESX_HIP(hipGetLastError());
+    return CESX_OK;
+}
+
+int launch_mh_hmc_run_map(Engine& e, uint64_t step_index, int n_steps, int leapfrog, int stride, void* U, void* trace,
+                          const void* xi, const double* logu, hipStream_t s) {
+    const MapRunArgs a = map_run_args(e, step_index, n_steps, stride, U, trace, xi, logu);
+    const bool f32 = e.cfg.dtype == CESX_F32;
+    switch (e.mp.desc.kind) {
+    case CESX_MAP_ELLIPTIC: return f32 ? mh_hmc_map_t<float, MapElliptic>(e, a, leapfrog, s) : mh_hmc_map_t<double, MapElliptic>(e, a, leapfrog, s);
+    case CESX_MAP_BANANA: return f32 ? mh_hmc_map_t<float, MapBanana>(e, a, leapfrog, s) : mh_hmc_map_t<double, MapBanana>(e, a, leapfrog, s);
+    default: e.err = "cesx_mh_hmc_run_map: the installed map has no fused kernel"; return CESX_ESTATE;
     }
 }
 

@@ -19,7 +19,7 @@ F32, F64 = 0, 1
 UPDATES = {"eks": 0, "aldi": 1, "aldi_constant": 2}
 TIME_STEPS = {None: 0, "spectral": 1, "constant": 2, "adaptive": 3, "mix": 4}
 ABI_VERSION = 10
-MH_KINDS = {None: 0, "pCN": 1, "langevin": 2}     # kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN; build-only: CESX_MH_LANGEVIN (gp_mh and model_mh)
+MH_KINDS = {None: 0, "pCN": 1, "langevin": 2, "hmc": 2}     # ('hmc' runs under the Langevin proposal: cesx_mh_hmc_*) kwargs['update'] of MCMC.model_mh (ces/sample.py:165-168) -> CESX_MH_RW / CESX_MH_PCN; build-only: CESX_MH_LANGEVIN (gp_mh and model_mh)
 
 EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error", "cesx_set_problem",
            "cesx_step", "cesx_result", "cesx_moments_len", "cesx_colsum", "cesx_set_shift",
@@ -39,6 +39,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_map_jac", "cesx_mh_langevin_start", "cesx_mh_langevin_propose", "cesx_mh_langevin_accept", "cesx_mh_langevin_run_map",
            "cesx_mh_langevin_lineal_set", "cesx_mh_langevin_lineal_start", "cesx_mh_langevin_lineal_propose",
            "cesx_mh_langevin_lineal_accept", "cesx_mh_langevin_lineal_g",
+           "cesx_mh_hmc_begin", "cesx_mh_hmc_leap", "cesx_mh_hmc_accept", "cesx_gp_hmc_leap", "cesx_gp_hmc_accept", "cesx_mh_hmc_run_map",
            "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read",
            "cesx_chain_hist_begin", "cesx_chain_hist_add", "cesx_chain_hist_read")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
@@ -311,6 +312,12 @@ def load_library(path=None):
     lib.cesx_mh_langevin_lineal_propose.argtypes = [vp, u64, vp, vp, vp, vp]
     lib.cesx_mh_langevin_lineal_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp]
     lib.cesx_mh_langevin_lineal_g.argtypes = [vp, dp]
+    lib.cesx_mh_hmc_begin.argtypes = [vp, u64, vp, vp, vp, vp]
+    lib.cesx_mh_hmc_leap.argtypes = [vp, vp, vp, vp, vp]
+    lib.cesx_mh_hmc_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gp_hmc_leap.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gp_hmc_accept.argtypes = [vp, i32, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cesx_mh_hmc_run_map.argtypes = [vp, u64, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.cesx_chain_summary_begin.argtypes = [vp, i32, vp]
     lib.cesx_chain_summary_add.argtypes = [vp, vp, i32, vp]
     lib.cesx_chain_summary_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1419,6 +1426,70 @@ class Engine:
                                                           None if trace is None or trace.numel() == 0 else trace.data_ptr(),
                                                           None if xi is None else xi.data_ptr(),
                                                           None if logu is None else logu.data_ptr(), self._stream()))
+        self._keep_mh_run = (U, trace, xi, logu)
+
+    # -- leapfrog HMC under a Langevin proposal (include/cesx.h, cesx_mh_hmc_* / cesx_gp_hmc_*): after mh_langevin_start / gp_langevin_start --
+    def mh_hmc_begin(self, step_index, U, xi=None, out=None):
+        """r = xi - g(U) / 2 and the first leapfrog position Q = U + S r (cesx_mh_hmc_begin; the map's and the emulator's);
+        xi None: drawn on device in the MH counter domain of step_index.  The engine keeps the block and r."""
+        out = self.empty(self.p) if out is None else out
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_hmc_begin(self._h, int(step_index), U.data_ptr(),
+                                                   None if xi is None else xi.data_ptr(), out.data_ptr(), self._stream()))
+        self._keep_hm_b = (U, xi, out)
+        return out
+
+    def mh_hmc_leap(self, Q, G, DG):
+        """phi(Q), g(Q) from the map ``G`` and the Jacobian ``DG`` at Q (``map_jac``), the full kick r = r - g(Q) and the next
+        position Q = Q + S r in place (cesx_mh_hmc_leap)."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_hmc_leap(self._h, Q.data_ptr(), G.data_ptr(), DG.data_ptr(), self._stream()))
+        self._keep_hm_l = (Q, G, DG)
+
+    def mh_hmc_accept(self, step_index, U, Q, G, DG, logu=None):
+        """phi(Q), g(Q) at the last position, the half kick, the test log u < phi(U) - phi(Q) + |xi|^2 / 2 - |r|^2 / 2, U := Q on
+        the accepted columns (cesx_mh_hmc_accept); logu as in ``mh_accept``."""
+        if logu is not None:
+            assert logu.dtype == torch.float64 and logu.numel() == self.J and logu.is_contiguous()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_hmc_accept(self._h, int(step_index), U.data_ptr(), Q.data_ptr(), G.data_ptr(),
+                                                    DG.data_ptr(), None if logu is None else logu.data_ptr(), self._stream()))
+        self._keep_hm_a = (U, Q, G, DG, logu)
+
+    def gp_hmc_leap(self, mode, Q, mean, var, dmean, dvar):
+        """``mh_hmc_leap`` on the GP rows and gradients at Q (``gp_predict_grad``) in likelihood mode ``mode`` (cesx_gp_hmc_leap)."""
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_hmc_leap(self._h, GP_MODES[mode], Q.data_ptr(), ptr(mean), ptr(var), ptr(dmean), ptr(dvar),
+                                                  self._stream()))
+        self._keep_hm_l = (Q, mean, var, dmean, dvar)
+
+    def gp_hmc_accept(self, mode, step_index, U, Q, mean, var, dmean, dvar, logu=None):
+        """``mh_hmc_accept`` on the GP rows and gradients at the last Q in likelihood mode ``mode`` (cesx_gp_hmc_accept)."""
+        if logu is not None:
+            assert logu.dtype == torch.float64 and logu.numel() == self.J and logu.is_contiguous()
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_gp_hmc_accept(self._h, GP_MODES[mode], int(step_index), U.data_ptr(), Q.data_ptr(),
+                                                    ptr(mean), ptr(var), ptr(dmean), ptr(dvar), ptr(logu), self._stream()))
+        self._keep_hm_a = (U, Q, mean, var, dmean, dvar, logu)
+
+    def mh_hmc_run_map(self, step_index, n_steps, leapfrog, U, stride=1, trace=None, xi=None, logu=None):
+        """``n_steps`` HMC steps of ``leapfrog`` positions each of every chain in one launch with the installed map of a fused
+        kind (cesx_mh_hmc_run_map; ``n_steps * leapfrog <= 4096``), after ``mh_langevin_start``; the engine's phi, g, counters
+        and step count follow.  The other arguments are ``mh_run_map``'s."""
+        n_steps, stride, leapfrog = int(n_steps), int(stride), int(leapfrog)
+        for name, t, shape, dt in (("U", U, (self.p, self.J), self.torch_dtype),
+                                   ("trace", trace, (max(n_steps, 0) // max(stride, 1), self.p, self.J), self.torch_dtype),
+                                   ("xi", xi, (n_steps, self.p, self.J), self.torch_dtype),
+                                   ("logu", logu, (n_steps, self.J), torch.float64)):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError("mh_hmc_run_map: %s must be a contiguous %s tensor of shape %s" % (name, dt, shape))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_hmc_run_map(self._h, int(step_index), n_steps, leapfrog, stride, U.data_ptr(),
+                                                     None if trace is None or trace.numel() == 0 else trace.data_ptr(),
+                                                     None if xi is None else xi.data_ptr(),
+                                                     None if logu is None else logu.data_ptr(), self._stream()))
         self._keep_mh_run = (U, trace, xi, logu)
 
     # -- the Langevin step on a linear map: the gradient as update launches (include/cesx.h, cesx_mh_langevin_lineal_*) --

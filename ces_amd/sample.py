@@ -95,6 +95,26 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          proposal, and one accept kernel (kernels_lvlin.hip) -- with no Jacobian image and no fused kernel
                          (``fused=True`` raises).  A model without a Jacobian (a plain ``lineal`` / ``lineal_log``, Darcy,
                          every 'pde' model) and ``flag_noise=True`` raise ``ValueError`` before an engine is created.
+  kwarg ``update='hmc'``  model_mh and gp_mh, on the host (one chain) and with ``chains=M``: Hamiltonian Monte Carlo with kwarg
+                         ``leapfrog=L`` (an integer in [1, 64], default 4) leapfrog steps per accept test, on the pieces of
+                         ``update='langevin'`` -- its scales S (so ``delta`` is the leapfrog step; the mass matrix is
+                         (S S^T)^-1), its g(u) = S^T grad phi(u), its phi with the prior term, its draws (xi, then u: ONE of each
+                         per step whatever L is, so a run sees the noise of a Langevin run with the same seed):
+                             r = xi - g(U) / 2;  Q = U;  L times  Q = Q + S r,  r = r - g(Q)  (r = r - g(Q) / 2 the last time);
+                             accepted when  log u < phi(U) + |xi|^2 / 2 - phi(Q) - |r|^2 / 2.
+                         At L = 1 this is the Langevin step term for term.  A NaN or an infinity anywhere in a trajectory
+                         rejects.  With ``chains=M`` the proposal kind and the start are the Langevin step's
+                         (``cesx_mh_langevin_start`` / ``cesx_gp_langevin_start``), the step path is ``cesx_mh_hmc_begin`` and per
+                         leapfrog ``model.jacobian_device`` or ``cesx_gp_predict_grad`` and ``cesx_mh_hmc_leap`` / ``_accept``
+                         (``cesx_gp_hmc_*`` on the emulator; kernels_hmc.hip), and for ``elliptic`` and ``banana`` ``fused=True``
+                         the fused kernel ``mh_hmc_map_kernel`` (``cesx_mh_hmc_run_map``: the trajectory in one lane's registers,
+                         at most ``HMC_GRADS_MAX`` gradient evaluations per launch, so a launch is ``HMC_GRADS_MAX // L`` steps at
+                         the most); ``fused=None`` is ``LANGEVIN_FUSED_DEFAULT``; the emulator refuses ``fused=True``.
+                         ``summary=``, ``burn=``, ``marginals=``, ``start=``, ``noise=``, sharded noise, resume (the resumed
+                         states are scored through the Langevin start) and ``trace_stride`` work as for ``update='langevin'``.
+                         It refuses what ``update='langevin'`` refuses, and the linear maps with or without
+                         ``enable_gradient()`` (no GEMM-form leapfrog yet: a follow-up); ``leapfrog=`` with any other
+                         ``update`` raises ``ValueError`` too.  No step or trajectory-length adaptation.
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -338,6 +358,7 @@ class MCMC(object):
             raise ImportError("MCMC.gp_mh needs a trained GP emulator: pass gpmodels= or train enka.gpmodels with "
                               "ces_amd.emulate.train_gps (the reference builds it with GPflow, ces/emulate.py, which is "
                               "not installed; ces/sample.py fails when it imports gpflow, :8)")
+        self._hmc_leapfrog(kwargs)                        # build-only; refused before any engine is created
         if kwargs.get("chains", None) is not None:
             return self._gp_mh_device(enka, n_mcmc, prior, delta, enka_scaling, kwargs)
         if kwargs.get("fused", None) is not None:
@@ -347,7 +368,7 @@ class MCMC(object):
                              % (kwargs.get("sigma_form"),))
         _host_has_no_summary(kwargs)
         from . import emulate
-        if kwargs.get("update", None) == "langevin":      # build-only
+        if kwargs.get("update", None) in ("langevin", "hmc"):      # build-only
             return self._gp_mh_langevin_host(enka, n_mcmc, prior, delta, enka_scaling, kwargs)
         if enka_scaling:
             scales = delta * np.linalg.cholesky(np.cov(enka.Ustar))
@@ -405,6 +426,49 @@ class MCMC(object):
         self.samples = np.array(samples).T
         self.accept = accept / n_mcmc
 
+    HMC_LEAPFROG_DEFAULT, HMC_LEAPFROG_MAX = 4, 64        # CESX_HMC_LEAPFROG_MAX
+    HMC_GRADS_MAX = 4096                                  # CESX_HMC_LAUNCH_GRADS_MAX: gradient evaluations per fused launch
+
+    @staticmethod
+    def _hmc_leapfrog(kwargs):
+        """L of ``update='hmc'`` (kwarg ``leapfrog``, an integer in [1, 64], default 4), or None for every other update --
+        which ``leapfrog=`` does not go with.  Every refusal is a ValueError."""
+        L, update = kwargs.get("leapfrog", None), kwargs.get("update", None)
+        if update != "hmc":
+            if L is not None:
+                raise ValueError("leapfrog=%r counts the leapfrog steps of update='hmc'; update=%r has none" % (L, update))
+            return None
+        L = MCMC.HMC_LEAPFROG_DEFAULT if L is None else L
+        if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= L <= MCMC.HMC_LEAPFROG_MAX:
+            raise ValueError("update='hmc': leapfrog must be an integer in [1, %d], got %r" % (MCMC.HMC_LEAPFROG_MAX, L))
+        return int(L)
+
+    @staticmethod
+    def _as_hmc(refusals, *args):
+        """``update='hmc'`` refuses what ``update='langevin'`` refuses, by the same function: its ValueError under hmc's name."""
+        try:
+            refusals(*args)
+        except ValueError as exc:
+            raise ValueError(str(exc).replace("update='langevin'", "update='hmc'"))
+
+    @staticmethod
+    def hmc_trajectory(score, scales, current, g_current, xi, leapfrog):
+        """The leapfrog trajectory of one HMC step from ``current`` (p,) with g = S^T grad phi there: r = xi - g / 2, then
+        ``leapfrog`` times q = q + S r, (phi, g) = ``score(q)``, r = r - g (r = r - g / 2 at the last).  A non-finite phi in
+        mid-trajectory poisons r, as the kernels do.  Returns (q, phi(q), g(q), r)."""
+        r = xi - 0.5 * g_current
+        q = current
+        for l in range(1, leapfrog + 1):
+            q = q + np.matmul(scales, r)
+            phi_q, g_q = score(q)
+            if l < leapfrog:
+                r = r - g_q
+                if not np.isfinite(phi_q):
+                    r = r * np.nan
+            else:
+                r = r - 0.5 * g_q
+        return q, phi_q, g_q, r
+
     @staticmethod
     def _langevin_refusals(kwargs, prior):
         """What ``gp_mh(update='langevin')`` cannot do, host and device alike: every refusal is a ValueError with the reason."""
@@ -453,7 +517,11 @@ class MCMC(object):
         """``gp_mh(update='langevin')`` on the host, one chain (module docstring): the restatement the device is held to.
         The scales, the start, the resume (phi and g of the resumed state) and the draws per step are the random walk's."""
         from . import emulate
-        self._langevin_refusals(kwargs, prior)
+        leapfrog = self._hmc_leapfrog(kwargs)             # None: the Langevin step
+        if leapfrog is None:
+            self._langevin_refusals(kwargs, prior)
+        else:
+            self._as_hmc(self._langevin_refusals, kwargs, prior)
         p = enka.p
         scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(p, p)) if enka_scaling else delta * np.eye(p)
         Gamma, compounded = kwargs.get("Gamma", None), bool(kwargs.get("noise_compounded", False))
@@ -463,7 +531,7 @@ class MCMC(object):
                 rows = emulate.predict_gps(enka, u.reshape(1, -1), gpmodels=kwargs.get("gpmodels", None),
                                            nugget=kwargs.get("nugget", True), grad=True)
             except ValueError as exc:
-                raise ValueError("update='langevin': %s" % exc)
+                raise ValueError("update=%r: %s" % (kwargs.get("update"), exc))
             phi, grad = self.langevin_phi_grad(*rows, u.reshape(1, -1), self.y_obs, Gamma, compounded, prior.mean, prior.cov)
             return phi[0], scales.T @ grad[0]
 
@@ -477,9 +545,14 @@ class MCMC(object):
         phi_current, g_current = score(current)
         for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
             xi = np.random.normal(0, 1, p)
-            proposal = current + np.matmul(scales, xi - 0.5 * g_current)
-            phi_proposal, g_proposal = score(proposal)
-            if np.log(np.random.uniform()) < phi_current - phi_proposal + self.langevin_correction(xi, g_current, g_proposal):
+            if leapfrog is None:
+                proposal = current + np.matmul(scales, xi - 0.5 * g_current)
+                phi_proposal, g_proposal = score(proposal)
+                corr = self.langevin_correction(xi, g_current, g_proposal)
+            else:                                         # update='hmc': the kinetic energies stand where the correction stands
+                proposal, phi_proposal, g_proposal, r = self.hmc_trajectory(score, scales, current, g_current, xi, leapfrog)
+                corr = 0.5 * (xi * xi).sum() - 0.5 * (r * r).sum()
+            if np.log(np.random.uniform()) < phi_current - phi_proposal + corr:
                 current, phi_current, g_current = np.copy(proposal), phi_proposal, g_proposal
                 accept += 1.
             samples.append(current)
@@ -508,15 +581,18 @@ class MCMC(object):
         ``enable_gradient()`` (``jacobian`` / ``langevin_device``: the adjoint launches of cesx_mh_langevin_lineal_*, at any
         p); module docstring.
         """
-        if kwargs.get("update", None) == "langevin":      # build-only; refused before any engine is created
+        leapfrog = self._hmc_leapfrog(kwargs)             # build-only; refused before any engine is created
+        if kwargs.get("update", None) == "langevin":
             self._model_langevin_refusals(model, prior, kwargs.get("chains", None) is not None)
+        if leapfrog is not None:
+            self._model_hmc_refusals(model, prior, kwargs.get("chains", None) is not None)
         if kwargs.get("chains", None) is not None:
             return self._model_mh_device(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, kwargs)
         if kwargs.get("fused", None) is not None:
             raise ValueError("fused=%r chooses between the device paths of chains=M; the host path has one" % (kwargs.get("fused"),))
         _host_has_no_summary(kwargs)
-        if kwargs.get("update", None) == "langevin":
-            return self._model_mh_langevin_host(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling)
+        if kwargs.get("update", None) in ("langevin", "hmc"):
+            return self._model_mh_langevin_host(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, leapfrog=leapfrog)
         # RW needs the proposal distribution (:122-126)
         if enka_scaling:
             scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(enka.p, enka.p))
@@ -589,7 +665,17 @@ class MCMC(object):
         if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
             raise ValueError("update='langevin': the prior must expose .mean and .cov (its gradient is cov^{-1} (u - mean))")
 
-    def _model_mh_langevin_host(self, model, n_mcmc, prior, enka, Gamma, delta, enka_scaling):
+    @staticmethod
+    def _model_hmc_refusals(model, prior, device):
+        """What ``model_mh(update='hmc')`` cannot do: the linear maps (their gradient is a GEMM on the update kernels, and a
+        GEMM-form leapfrog is a follow-up), then everything ``update='langevin'`` refuses."""
+        if getattr(model, "model_name", None) in ("lineal", "lineal_log") or hasattr(model, "langevin_device"):
+            raise ValueError("update='hmc': %r is a linear map, with or without enable_gradient(); its gradient is an A^T "
+                             "product on the update kernels and there is no GEMM-form leapfrog yet (a follow-up) -- run "
+                             "update='langevin' after enable_gradient(), or update='hmc' on elliptic / banana" % (model,))
+        MCMC._as_hmc(MCMC._model_langevin_refusals, model, prior, device)
+
+    def _model_mh_langevin_host(self, model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, leapfrog=None):
         """``model_mh(update='langevin')`` on the host, one chain: the restatement the device is held to.  The scales and
         the start are the random walk's, phi has the prior term, g = S^T grad phi with
         grad phi = DG^T Gamma^{-1} (G - y) + cov^{-1} (u - mean) from ``model.jacobian``; the proposal
@@ -621,9 +707,14 @@ class MCMC(object):
         phi_current, g_current = score(current)
         for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
             xi = np.random.normal(0, 1, p)
-            proposal = current + np.matmul(scales, xi - 0.5 * g_current)
-            phi_proposal, g_proposal = score(proposal)
-            if np.log(np.random.uniform()) < phi_current - phi_proposal + self.langevin_correction(xi, g_current, g_proposal):
+            if leapfrog is None:
+                proposal = current + np.matmul(scales, xi - 0.5 * g_current)
+                phi_proposal, g_proposal = score(proposal)
+                corr = self.langevin_correction(xi, g_current, g_proposal)
+            else:                                         # update='hmc' (``leapfrog`` positions per test): module docstring
+                proposal, phi_proposal, g_proposal, r = self.hmc_trajectory(score, scales, current, g_current, xi, leapfrog)
+                corr = 0.5 * (xi * xi).sum() - 0.5 * (r * r).sum()
+            if np.log(np.random.uniform()) < phi_current - phi_proposal + corr:
                 current, phi_current, g_current = np.copy(proposal), phi_proposal, g_proposal
                 accept += 1.
             samples.append(current.flatten())
@@ -648,7 +739,7 @@ class MCMC(object):
         return self._mh_eng
 
     def _mh_device(self, enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi, fused=False,
-                   fused_work=0, langevin=False):
+                   fused_work=0, langevin=False, fused_steps_max=None):
         """M = kwargs['chains'] chains on the engine: what ``model_mh(chains=)`` and ``gp_mh(chains=)`` have in common.
 
         Gamma                    the data covariance handed to ``set_problem``
@@ -659,7 +750,9 @@ class MCMC(object):
                                  launch: ``eng.mh_run_map`` for a map, ``eng.gp_run`` for the emulator; None where the
                                  sampler has no fused kernel) and, optionally, a fourth hook ``propose(step, U, xi, P)`` that
                                  stands in for ``eng.mh_propose`` on the step path (the Langevin proposal reads the chains' g)
-        langevin                 the sampler takes ``update='langevin'`` (gp_mh; model_mh for a model with a Jacobian)
+        langevin                 the sampler takes ``update='langevin'`` and ``'hmc'`` (gp_mh; model_mh for a model with a Jacobian)
+        fused_steps_max          the longest fused launch in steps (None: ``FUSED_STEPS_MAX``; update='hmc': ``HMC_GRADS_MAX``
+                                 over the leapfrog count).  ``run_steps`` may return the launches it made (None: one)
         resume_keeps_start_phi   the reference's model_mh scores the START point before it looks for ``self.samples`` and
                                  keeps that phi for the resumed states (ces/sample.py:131-163); its gp_mh scores the resumed
                                  states (:31-39).  True: the first, for ``noise='numpy'`` (``noise='device'`` re-scores the
@@ -683,11 +776,11 @@ class MCMC(object):
         if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
             raise ValueError("chains=: the prior must expose .mean and .cov (a frozen scipy.stats.multivariate_normal does)")
         update = kwargs.get("update", None)
-        if update == "langevin" and not langevin:
-            raise ValueError("chains=: update='langevin' needs the gradient of phi, and this sampler has no Jacobian on the "
+        if update in ("langevin", "hmc") and not langevin:
+            raise ValueError("chains=: update='langevin' / 'hmc' needs the gradient of phi, and this sampler has no Jacobian on the "
                              "device; gp_mh(chains=, update='langevin') differentiates the emulator")
-        if update not in (None, "pCN", "langevin"):
-            raise ValueError("chains=: unknown update %r (None or 'pCN')" % (update,))
+        if update not in (None, "pCN", "langevin", "hmc"):
+            raise ValueError("chains=: unknown update %r (None, 'pCN', 'langevin' or 'hmc')" % (update,))
         if self.noise not in ("numpy", "device"):
             raise ValueError("noise must be 'numpy' or 'device', got %r" % (self.noise,))
         stride = max(1, int(self.trace_stride))
@@ -759,7 +852,7 @@ class MCMC(object):
             # The trace buffer is allocated once per run; each launch's trace crosses to the host once.
             esz = eng.np_dtype.itemsize
             per_step = -(-M * p * esz // stride) + (M * (p * esz + 8) if self.noise == "numpy" else 0)     # trace; xi and log u
-            K_max, chunks = fused_chunks(n_mcmc, stride, self.FUSED_STEPS_MAX, self.FUSED_BUFFER_BYTES, per_step,
+            K_max, chunks = fused_chunks(n_mcmc, stride, fused_steps_max or self.FUSED_STEPS_MAX, self.FUSED_BUFFER_BYTES, per_step,
                                          self.GP_FUSED_WORK if fused_work else None, fused_work)
             trace = torch.empty((min(K_max, n_mcmc) // stride, p, M), dtype=eng.torch_dtype, device=eng.device)
             for i, K in enumerate(tqdm(chunks, desc="MCMC samples: ", disable=self.mute_bar)):
@@ -773,8 +866,7 @@ class MCMC(object):
                     xi_t = torch.as_tensor(xi, device=eng.device).to(eng.torch_dtype).contiguous()
                     logu_t = torch.as_tensor(logu, dtype=torch.float64, device=eng.device)
                 tr = trace[:K // stride]
-                run_steps(base + k0, K, U, stride, tr, xi_t, logu_t)
-                self.fused_launches += 1
+                self.fused_launches += run_steps(base + k0, K, U, stride, tr, xi_t, logu_t) or 1
                 if summary:                               # the launch's states after the steps s = k0 + stride (t + 1) > burn
                     t0 = max(0, burn // stride - k0 // stride)
                     if t0 < K // stride:
@@ -843,7 +935,8 @@ class MCMC(object):
         if fused and not has_fused:
             raise ValueError("fused=True: %r has no fused chain kernel (ces_amd.utils.elliptic and banana have, noise-free); "
                              "pass fused=None or False for the step path" % (model,))
-        langevin = kwargs.get("update", None) == "langevin"      # (model_mh has refused what has no Jacobian)
+        leapfrog = self._hmc_leapfrog(kwargs)             # update='hmc': the Langevin proposal, start and default, L positions per test
+        langevin = kwargs.get("update", None) in ("langevin", "hmc")      # (model_mh has refused what has no Jacobian)
         default = self.LANGEVIN_FUSED_DEFAULT if langevin else self.FUSED_DEFAULT
         fused = (has_fused and default) if fused is None else bool(fused)
         p, n = enka.p, enka.n_obs
@@ -928,6 +1021,43 @@ class MCMC(object):
                 eng.mh_langevin_run_map(step, K, U, stride=stride, trace=trace, xi=xi, logu=logu)
             return lv_start, lv_accept, run_steps if fused else None, lv_propose
 
+        def bind_hmc(eng, M):
+            # bind_langevin with the leapfrog loop on the host: per position the map and its Jacobian at Q, then the kick
+            import torch
+            out = (torch.empty((n, M), dtype=torch.float64, device=eng.device),
+                   torch.empty((n, p, M), dtype=torch.float64, device=eng.device))
+            model.ensure_installed(eng)
+            cap = self.HMC_GRADS_MAX // leapfrog
+
+            def hm_start(U):                              # the Langevin start: phi and g of the states
+                model.jacobian_device(eng, U, out=out)
+                eng.mh_langevin_start(U, *out)
+
+            def hm_begin(step, U, xi, Q):
+                eng.mh_hmc_begin(step, U, xi=xi, out=Q)
+
+            def hm_accept(step, U, Q, logu):
+                for _ in range(leapfrog - 1):
+                    model.jacobian_device(eng, Q, out=out)
+                    eng.mh_hmc_leap(Q, *out)
+                model.jacobian_device(eng, Q, out=out)
+                eng.mh_hmc_accept(step, U, Q, *out, logu=logu)
+
+            def run_steps(step, K, U, stride, trace, xi, logu):
+                if K <= cap:
+                    eng.mh_hmc_run_map(step, K, leapfrog, U, stride=stride, trace=trace, xi=xi, logu=logu)
+                    return 1
+                # a trace_stride longer than a launch may be (fused_chunks then makes K = stride: at most one kept state, the
+                # last): launches of at most ``cap`` steps without a trace, and the state they leave
+                for k0 in range(0, K, cap):
+                    k1 = min(K, k0 + cap)
+                    eng.mh_hmc_run_map(step + k0, k1 - k0, leapfrog, U, xi=None if xi is None else xi[k0:k1],
+                                       logu=None if logu is None else logu[k0:k1])
+                if trace is not None and trace.shape[0]:
+                    trace[0].copy_(U)
+                return -(-K // cap)
+            return hm_start, hm_accept, run_steps if fused else None, hm_begin
+
         def bind_langevin_lineal(eng, M):
             # a linear map (lineal / lineal_log after enable_gradient()): the gradient is an A^T product of the engine's own
             # (cesx_mh_langevin_lineal_*), so a step is the forward map and the engine's launches -- no Jacobian image
@@ -955,9 +1085,12 @@ class MCMC(object):
 
         if langevin and not hasattr(model, "jacobian_device"):
             bind_langevin = bind_langevin_lineal
+        if leapfrog is not None:
+            bind_langevin = bind_hmc
         # a resume under update='langevin' scores the resumed states whatever the noise: the chains need their g as well as phi
         self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_langevin if langevin else bind_pde if pde else bind,
-                        resume_keeps_start_phi=not langevin, fused=fused, langevin=langevin)
+                        resume_keeps_start_phi=not langevin, fused=fused, langevin=langevin,
+                        fused_steps_max=None if leapfrog is None else self.HMC_GRADS_MAX // leapfrog)
 
     def _gp_mh_device(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
         import torch
@@ -973,12 +1106,16 @@ class MCMC(object):
         if fused and kwargs.get("pca_tools", None) is not None:
             raise ValueError("fused=True: the dense and the projected Sigma of pca_tools stay on the step path (the fused chain "
                              "kernel scores Gamma, diag(gvars) and diag(Gamma) + diag(gvars)); pass fused=None or False")
-        langevin = kwargs.get("update", None) == "langevin"
+        leapfrog = self._hmc_leapfrog(kwargs)             # update='hmc': the Langevin proposal and start, L positions per test
+        langevin = kwargs.get("update", None) in ("langevin", "hmc")
         if langevin:
             if fused:
-                raise ValueError("fused=True: update='langevin' runs on the step path (the fused chain kernel has no gradient "
-                                 "phase); pass fused=None or False")
-            self._langevin_refusals(kwargs, prior)
+                raise ValueError("fused=True: update=%r runs on the step path (the fused chain kernel has no gradient "
+                                 "phase); pass fused=None or False" % (kwargs.get("update"),))
+            if leapfrog is None:
+                self._langevin_refusals(kwargs, prior)
+            else:
+                self._as_hmc(self._langevin_refusals, kwargs, prior)
         fused = self.GP_FUSED_DEFAULT if fused is None else bool(fused)
         if kwargs.get("separable", False):
             raise ValueError("chains=: separable predicts one point at a time" + host)
@@ -1038,9 +1175,9 @@ class MCMC(object):
         except ValueError as exc:
             raise ValueError("chains=: %s" % exc)
         if langevin and np.any(np.asarray(img["family"]) == 1):
-            raise ValueError("chains=, update='langevin': GP %d has a Matern12 kernel, which is not differentiable at its "
+            raise ValueError("chains=, update=%r: GP %d has a Matern12 kernel, which is not differentiable at its "
                              "training points; train the emulator with RBF, Matern32 or Matern52"
-                             % int(np.nonzero(np.asarray(img["family"]) == 1)[0][0]))
+                             % (kwargs.get("update"), int(np.nonzero(np.asarray(img["family"]) == 1)[0][0])))
 
         def scales_of(update):                            # (:23-26; pCN takes the same scales)
             return delta * np.linalg.cholesky(np.cov(enka.Ustar)) if enka_scaling else delta * np.eye(p)
@@ -1069,6 +1206,18 @@ class MCMC(object):
                 def lv_accept(step, U, P, logu):
                     eng.gp_predict_grad(P, nugget=nugget, var=want_var, out=out)
                     eng.gp_langevin_accept(mode, step, U, P, *out, logu=logu)
+
+                def hm_begin(step, U, xi, Q):             # update='hmc': the same start, then per position the rows at Q and the kick
+                    eng.mh_hmc_begin(step, U, xi=xi, out=Q)
+
+                def hm_accept(step, U, Q, logu):
+                    for _ in range(leapfrog - 1):
+                        eng.gp_predict_grad(Q, nugget=nugget, var=want_var, out=out)
+                        eng.gp_hmc_leap(mode, Q, *out)
+                    eng.gp_predict_grad(Q, nugget=nugget, var=want_var, out=out)
+                    eng.gp_hmc_accept(mode, step, U, Q, *out, logu=logu)
+                if leapfrog is not None:
+                    return lv_start, hm_accept, None, hm_begin
                 return lv_start, lv_accept, None, lv_propose
 
             def score_start(U):

@@ -648,6 +648,57 @@ int cesx_mh_langevin_lineal_propose(cesx_handle h, uint64_t step_index, const vo
 int cesx_mh_langevin_lineal_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* P_dev, const void* G_dev,
                                    const double* logu_dev, void* stream);
 int cesx_mh_langevin_lineal_g(cesx_handle h, double* g_host);
+/* MCMC.model_mh / gp_mh(chains=M, update='hmc', leapfrog=L): Hamiltonian Monte Carlo with L leapfrog steps per accept test, on
+   the pieces of the Langevin step above -- the proposal kind is CESX_MH_LANGEVIN (no kind of its own), the start is
+   cesx_mh_langevin_start (a map) or cesx_gp_langevin_start (the emulator), which leave phi and g = S^T grad phi of the chains,
+   and phi, g, the noise block, the counters, cesx_mh_stats and cesx_mh_phi are the Langevin step's.  HMC steps, single Langevin
+   steps and fused launches of either may therefore alternate on one handle.  With S the scale (the mass matrix is
+   (S S^T)^{-1} and the leapfrog step 1: delta is the leapfrog step as it is the Langevin step) one step of a chain at U is
+       xi ~ N(0, I_p);   r = xi - g(U) / 2;   Q = U
+       l = 1 .. L:   Q = Q + S r;   phi(Q), g(Q);   r = r - g(Q)  (l < L)   or   r = r - g(Q) / 2  (l = L)
+       log u < phi(U) - phi(Q) + (|xi|^2 / 2 - |r|^2 / 2);   accepted columns: U := Q, phi := phi(Q), g := g(Q), counter + 1
+   At L = 1 this is the Langevin step term for term (r = xi - (g(U) + g(Q)) / 2), and the first position is
+   cesx_mh_langevin_propose's P bit for bit.  A step consumes ONE step index whatever L is: the block and log u are the counter
+   words of cesx_mh_langevin_propose / _accept for that index, so a run sees the noise of a Langevin run with the same seed.
+       cesx_mh_hmc_begin    r (an engine-owned [p][J_local] fp64 block) and the first position Q_dev = U + S r.  The block
+                            (xi_dev, engine dtype, or NULL: the device draw for step_index) is kept in engine memory.  Shared
+                            by the map and the emulator.  It ends a pending cesx_*_langevin_propose, as such a propose ends a
+                            trajectory in flight: both keep their block in the same memory.
+       cesx_mh_hmc_leap     phi(Q), g(Q) from G_dev, DG_dev = cesx_map_jac at Q_dev (or any [n][J] / [n][p][J] fp64 images), the
+                            full kick, and the next position written over Q_dev.  Called L - 1 times.
+       cesx_mh_hmc_accept   phi(Q), g(Q) at the last position, the half kick, the two norms, the test with cesx_mh_accept's log u
+       cesx_gp_hmc_leap / cesx_gp_hmc_accept   the same on the rows and gradients of cesx_gp_predict_grad at Q_dev in likelihood
+                            mode `mode` (cesx_gp_langevin_*'s modes and their NULL rules)
+   r, g, phi and every sum are fp64 in a fixed order (rows ascending): runs are bit-identical.  An fp32 engine stores Q_dev
+   rounded after every leapfrog -- the forward map reads that array.  A NaN or an infinity anywhere in a trajectory (phi, g,
+   r, Q) makes the comparison false: the chain stays and its phi and g are untouched.
+   cesx_mh_hmc_run_map: n_steps such steps of every chain in ONE launch for CESX_MAP_ELLIPTIC and CESX_MAP_BANANA, one chain per
+   lane with the trajectory in its registers -- cesx_mh_langevin_run_map with the leapfrog loop inside.  It restates the step
+   path's sums in their order: on an fp64 engine it leaves U_dev, phi and g as n_steps times begin / (cesx_map_jac, leap)
+   x (L - 1) / cesx_map_jac / accept leave them, bit for bit (a resume that scores the resumed states through
+   cesx_mh_langevin_start continues a fused run exactly).  The trajectory is fp64 whatever the engine dtype; an fp32 engine
+   rounds on the trace store and at the end of the launch.  Noise, trace_dev and stride are cesx_mh_run_map's.  A launch is
+   bounded: n_steps * leapfrog <= CESX_HMC_LAUNCH_GRADS_MAX gradient evaluations.  cesx_mh_stats counts one step per accept
+   and n_steps per fused launch.
+   CESX_ESTATE without cesx_set_problem, a proposal of kind CESX_MH_LANGEVIN or a cesx_mh_langevin_start /
+   cesx_gp_langevin_start as the LAST start (not cesx_mh_langevin_lineal_start: the linear maps have no leapfrog yet); leap and
+   accept also without a cesx_mh_hmc_begin since the start or the last accept; the cesx_gp_hmc_* calls without cesx_gp_set;
+   run_map without an installed map of a fused kind.  CESX_EINVAL for a null pointer (xi_dev, logu_dev and trace_dev may be
+   NULL), Q_dev aliasing U_dev, leapfrog outside 1 .. CESX_HMC_LEAPFROG_MAX, n_steps < 1, stride < 1,
+   n_steps * leapfrog > CESX_HMC_LAUNCH_GRADS_MAX, a step index >= 2^31, or what cesx_gp_langevin_* refuses of a mode.  None of
+   these launches anything or touches U_dev, the chains' phi, g or the counters. */
+#define CESX_HMC_LEAPFROG_MAX 64
+#define CESX_HMC_LAUNCH_GRADS_MAX 4096
+int cesx_mh_hmc_begin(cesx_handle h, uint64_t step_index, const void* U_dev, const void* xi_dev, void* Q_dev, void* stream);
+int cesx_mh_hmc_leap(cesx_handle h, void* Q_dev, const double* G_dev, const double* DG_dev, void* stream);
+int cesx_mh_hmc_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* Q_dev, const double* G_dev,
+                       const double* DG_dev, const double* logu_dev, void* stream);
+int cesx_gp_hmc_leap(cesx_handle h, int mode, void* Q_dev, const double* mean_dev, const double* var_dev, const double* dmean_dev,
+                     const double* dvar_dev, void* stream);
+int cesx_gp_hmc_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev, const void* Q_dev, const double* mean_dev,
+                       const double* var_dev, const double* dmean_dev, const double* dvar_dev, const double* logu_dev, void* stream);
+int cesx_mh_hmc_run_map(cesx_handle h, uint64_t step_index, int n_steps, int leapfrog, int stride, void* U_dev, void* trace_dev,
+                        const void* xi_dev, const double* logu_dev, void* stream);
 
 /* ---- Streaming summaries of the chains' draws (MCMC(..., chains=M, summary=True); kernels_chainsum.hip) --
    The sums behind the pooled mean and covariance, the split R-hat and an effective sample size of a run of
