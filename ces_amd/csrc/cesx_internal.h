@@ -839,6 +839,9 @@ int launch_hmc(Engine& e, int what, int mode, void* Q, const double* mean, const
                const double* dvar, void* U, const double* logu, unsigned step, hipStream_t s);
 int launch_mh_hmc_run_map(Engine& e, uint64_t step_index, int n_steps, int leapfrog, int stride, void* U, void* trace,
                           const void* xi, const double* logu, hipStream_t s);
+// kernels_adapt.hip: the step-size recursion behind an armed handle's accept (cesx_mh_adapt_*): mh.ad_alpha -> mh.ad_state, a
+// row of mh.ad_hist.  While mh.ad_armed, launch_hmc launches the ADAPT instantiations, which read mh.ad_state[0]
+int launch_adapt_update(Engine& e, hipStream_t s);
 
 // kernels_chainsum.hip: the stage behind cesx_chain_summary_* (include/cesx.h); the entry points have checked the state
 int chainsum_begin(Engine& e, long long n_draws);

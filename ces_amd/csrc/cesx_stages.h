@@ -41,8 +41,16 @@ struct MhState {
     DevBuf<void> lin_ba, lin_bb;       // [rpad] the biases of the two launches
     DevBuf<void> lin_g, lin_gp, lin_z; // [p][J] engine dtype: g of the chains' states, of the proposals, and z = xi - g / 2
     DevBuf<void> lin_t;                // lineal_log: [p][J] t0, then h = exp(X) (.) t0
+    // pooled step-size adaptation (cesx_mh_adapt_*, kernels_adapt.hip): while armed the hm_* launches take e S for S
+    bool ad_armed = false;             // a cesx_mh_adapt_set since the last cesx_mh_set_proposal / cesx_set_problem
+    int ad_n = 0, ad_done = 0;         // adaptation steps asked for, and accepts made (each followed by ad_update_kernel)
+    double ad_target = 0.0, ad_gain = 0.0, ad_kappa = 0.0;
+    DevBuf<double> ad_alpha;           // [J] the chains' acceptance probabilities of the step in hand
+    DevBuf<double> ad_state;           // [4] e, log e, log ebar, t
+    DevBuf<double> ad_hist;            // [ad_n][2] row t - 1: e_t, abar_t
     bool none() const { return kind < 0; }
-    void drop() { kind = -1; started = false; lv_proposed = false; hm_begun = false; lin = 0; lin_started = false; }      // every buffer is sized by the engine: kept
+    // every buffer is sized by the engine: kept -- but the adaptation's history, which its step count sizes
+    void drop() { kind = -1; started = false; lv_proposed = false; hm_begun = false; lin = 0; lin_started = false; ad_armed = false; ad_n = 0; ad_done = 0; ad_hist.reset(); }
 };
 
 // ---- GP emulator over the columns (cesx_gp_*, kernels_gp.hip) ----

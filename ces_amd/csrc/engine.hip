@@ -1213,8 +1213,16 @@ int cesx_gp_predict_grad(cesx_handle h, const void* X, double* mean, double* var
 
 // ---- the Langevin step of gp_mh(chains=, update='langevin') (kernels_gpgrad.hip) ----
 
+// an armed handle (cesx_mh_adapt_set) runs adaptation steps through cesx_mh_hmc_begin / _leap / _accept and cesx_gp_hmc_leap /
+// _accept alone: every other step of the Langevin family would move the chains at a step the recursion does not see
+static int adapt_refuses(Engine& e) {
+    if (e.mh.ad_armed) { e.err = "the handle is armed for step-size adaptation (cesx_mh_adapt_set): its steps are cesx_mh_hmc_begin / _leap / _accept and cesx_gp_hmc_leap / _accept; cesx_mh_adapt_read, then cesx_mh_set_proposal, ends the phase"; return CESX_ESTATE; }
+    return CESX_OK;
+}
+
 // what every cesx_gp_langevin_* call needs before it looks at its own arguments; `started`: a cesx_gp_langevin_start too
 static int langevin_check_state(Engine& e, bool started) {
+    if (started) TRY(adapt_refuses(e));
     if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_gp_langevin: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
     if (e.gp.none()) { e.err = "cesx_gp_langevin: cesx_gp_set has not been called"; return CESX_ESTATE; }
     if (started && (!e.mh.started || e.mh.lin_started)) { e.err = "cesx_gp_langevin: cesx_gp_langevin_start has not been called"; return CESX_ESTATE; }
@@ -1849,6 +1857,7 @@ int cesx_map_jac(cesx_handle h, const void* U, double* G, double* DG, void* stre
 
 // what every cesx_mh_langevin_* call needs before it looks at its own arguments; `started`: a cesx_mh_langevin_start too
 static int mh_langevin_check_state(Engine& e, bool started) {
+    if (started) TRY(adapt_refuses(e));
     if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_mh_langevin: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
     if (started && (!e.mh.started || e.mh.lin_started)) { e.err = "cesx_mh_langevin: cesx_mh_langevin_start has not been called (the last start was not it)"; return CESX_ESTATE; }
     return CESX_OK;
@@ -1928,6 +1937,7 @@ static int hmc_check_state(Engine& e, bool begun) {
     if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_hmc: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
     if (!e.mh.started || e.mh.lin_started) { e.err = "cesx_hmc: cesx_mh_langevin_start / cesx_gp_langevin_start has not been called (the last start was not one of them)"; return CESX_ESTATE; }
     if (begun && !e.mh.hm_begun) { e.err = "cesx_hmc: no cesx_mh_hmc_begin since the start or the last accept"; return CESX_ESTATE; }
+    if (e.mh.ad_armed && e.mh.ad_done >= e.mh.ad_n) { e.err = "cesx_hmc: the adaptation steps of cesx_mh_adapt_set are done: read the multiplier (cesx_mh_adapt_read), then set the proposal (cesx_mh_set_proposal)"; return CESX_ESTATE; }
     return CESX_OK;
 }
 
@@ -1971,6 +1981,7 @@ int cesx_mh_hmc_accept(cesx_handle h, uint64_t step_index, void* U, const void* 
     SET_DEVICE(e);
     FLUSH(e);
     TRY(launch_hmc(e, 2, CESX_GP_GAMMA, const_cast<void*>(Q), G, nullptr, DG, nullptr, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    if (e.mh.ad_armed) { TRY(launch_adapt_update(e, (hipStream_t)stream)); ++e.mh.ad_done; }
     e.mh.hm_begun = false;
     ++e.mh.steps;
     return CESX_OK;
@@ -2002,6 +2013,7 @@ int cesx_gp_hmc_accept(cesx_handle h, int mode, uint64_t step_index, void* U, co
     SET_DEVICE(e);
     FLUSH(e);
     TRY(launch_hmc(e, 2, mode, const_cast<void*>(Q), mean, var, dmean, dvar, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    if (e.mh.ad_armed) { TRY(launch_adapt_update(e, (hipStream_t)stream)); ++e.mh.ad_done; }
     e.mh.hm_begun = false;
     ++e.mh.steps;
     return CESX_OK;
@@ -2016,6 +2028,7 @@ int cesx_mh_hmc_run_map(cesx_handle h, uint64_t step_index, int n_steps, int lea
     if (leapfrog < 1 || leapfrog > CESX_HMC_LEAPFROG_MAX) { e.err = "cesx_mh_hmc_run_map: leapfrog must be in 1 .. 64"; return CESX_EINVAL; }
     if ((long long)n_steps * leapfrog > CESX_HMC_LAUNCH_GRADS_MAX) { e.err = "cesx_mh_hmc_run_map: n_steps * leapfrog is limited to 4096 gradient evaluations per launch"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull || step_index + (uint64_t)n_steps > 0x80000000ull) { e.err = "cesx_mh_hmc_run_map: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    TRY(adapt_refuses(e));
     TRY(hmc_check_state(e, false));
     if (!e.mp.fused()) { e.err = "cesx_mh_hmc_run_map: no map of a fused kind is installed (cesx_map_set: CESX_MAP_ELLIPTIC or CESX_MAP_BANANA)"; return CESX_ESTATE; }
     SET_DEVICE(e);
@@ -2023,6 +2036,50 @@ int cesx_mh_hmc_run_map(cesx_handle h, uint64_t step_index, int n_steps, int lea
     TRY(launch_mh_hmc_run_map(e, step_index, n_steps, leapfrog, stride, U, trace, xi, logu, (hipStream_t)stream));
     e.mh.lv_proposed = false; e.mh.hm_begun = false;      // (a block drawn before the launch belongs to a state the chains have left)
     e.mh.steps += (unsigned long long)n_steps;
+    return CESX_OK;
+}
+
+// ---- pooled step-size adaptation of the leapfrog step (include/cesx.h; kernels_adapt.hip, the ADAPT kernels of kernels_hmc.hip) ----
+
+// Failure rule: an argument or state error leaves the handle as it was; behind them a failed allocation leaves it unarmed.
+int cesx_mh_adapt_set(cesx_handle h, int n_steps, double target, double gain, double kappa) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (n_steps < 1 || n_steps > CESX_ADAPT_STEPS_MAX) { e.err = "cesx_mh_adapt_set: n_steps must be in 1 .. 65536"; return CESX_EINVAL; }
+    if (!(target > 0.0 && target < 1.0)) { e.err = "cesx_mh_adapt_set: target must lie in (0, 1)"; return CESX_EINVAL; }
+    if (!(gain > 0.0) || !std::isfinite(gain)) { e.err = "cesx_mh_adapt_set: gain must be finite and > 0"; return CESX_EINVAL; }
+    if (!(kappa > 0.5 && kappa <= 1.0)) { e.err = "cesx_mh_adapt_set: kappa must lie in (0.5, 1]"; return CESX_EINVAL; }
+    if (e.J != e.Jg) { e.err = "cesx_mh_adapt_set: sharded chains (J_local != J_global) are not pooled: the mean acceptance would need a reduce across ranks"; return CESX_EUNSUPPORTED; }
+    if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_mh_adapt_set: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    CESX_HIP(hipDeviceSynchronize());          // (an earlier phase's launches may still read the state)
+    e.mh.ad_armed = false;
+    TRY_BUF(e.mh.ad_alpha.ensure((size_t)e.J * 8));
+    TRY_BUF(e.mh.ad_state.ensure(4 * 8));
+    TRY_BUF(e.mh.ad_hist.alloc((size_t)n_steps * 2 * 8));
+    const double st[4] = {1.0, 0.0, 0.0, 0.0};          // e_1 = 1, log e_1 = 0, log ebar_0 = 0, t = 0
+    CESX_HIP(hipMemcpy(e.mh.ad_state, st, sizeof st, hipMemcpyHostToDevice));
+    e.mh.ad_n = n_steps; e.mh.ad_done = 0;
+    e.mh.ad_target = target; e.mh.ad_gain = gain; e.mh.ad_kappa = kappa;
+    e.mh.hm_begun = false;                     // (a trajectory begun at S is not finished at e S)
+    e.mh.ad_armed = true;
+    return CESX_OK;
+}
+
+int cesx_mh_adapt_read(cesx_handle h, double* multiplier, int* steps_done, double* history) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!multiplier || !steps_done) { e.err = "cesx_mh_adapt_read: null pointer"; return CESX_EINVAL; }
+    if (!e.mh.ad_armed) { e.err = "cesx_mh_adapt_read: the handle is not armed (cesx_mh_adapt_set after cesx_mh_set_proposal)"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    CESX_HIP(hipDeviceSynchronize());
+    double st[4];
+    CESX_HIP(hipMemcpy(st, e.mh.ad_state, sizeof st, hipMemcpyDeviceToHost));
+    *multiplier = std::exp(st[2]);             // ebar_A; no step yet: log ebar_0 = 0, the multiplier 1
+    *steps_done = e.mh.ad_done;
+    if (history && e.mh.ad_done > 0)
+        CESX_HIP(hipMemcpy(history, e.mh.ad_hist, (size_t)e.mh.ad_done * 2 * 8, hipMemcpyDeviceToHost));
     return CESX_OK;
 }
 
@@ -2057,6 +2114,7 @@ int cesx_mh_langevin_lineal_set(cesx_handle h, const double* A, const double* b,
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!A) { e.err = "cesx_mh_langevin_lineal_set: null pointer"; return CESX_EINVAL; }
     if (exp_params != 0 && exp_params != 1) { e.err = "cesx_mh_langevin_lineal_set: exp_params must be 0 or 1"; return CESX_EINVAL; }
+    TRY(adapt_refuses(e));
     if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_mh_langevin_lineal_set: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
     const int p = e.p, n = e.n, kp = e.kp, kn = e.kn;
     for (size_t i = 0; i < (size_t)n * p; ++i)
@@ -2176,6 +2234,7 @@ static int lin_score(Engine& e, bool start, const void* X, const void* G, void* 
 
 // what every cesx_mh_langevin_lineal_* call behind the set needs before it looks at its own arguments
 static int lin_check_state(Engine& e, bool started) {
+    TRY(adapt_refuses(e));
     if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN || !e.mh.lin) { e.err = "cesx_mh_langevin_lineal: no lineal image (cesx_mh_langevin_lineal_set after cesx_mh_set_proposal with CESX_MH_LANGEVIN)"; return CESX_ESTATE; }
     if (started && !(e.mh.started && e.mh.lin_started)) { e.err = "cesx_mh_langevin_lineal: the last start was not cesx_mh_langevin_lineal_start"; return CESX_ESTATE; }
     return CESX_OK;

@@ -40,6 +40,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_mh_langevin_lineal_set", "cesx_mh_langevin_lineal_start", "cesx_mh_langevin_lineal_propose",
            "cesx_mh_langevin_lineal_accept", "cesx_mh_langevin_lineal_g",
            "cesx_mh_hmc_begin", "cesx_mh_hmc_leap", "cesx_mh_hmc_accept", "cesx_gp_hmc_leap", "cesx_gp_hmc_accept", "cesx_mh_hmc_run_map",
+           "cesx_mh_adapt_set", "cesx_mh_adapt_read",
            "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read",
            "cesx_chain_hist_begin", "cesx_chain_hist_add", "cesx_chain_hist_read")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
@@ -318,6 +319,8 @@ def load_library(path=None):
     lib.cesx_gp_hmc_leap.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     lib.cesx_gp_hmc_accept.argtypes = [vp, i32, u64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cesx_mh_hmc_run_map.argtypes = [vp, u64, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.cesx_mh_adapt_set.argtypes = [vp, i32, C.c_double, C.c_double, C.c_double]
+    lib.cesx_mh_adapt_read.argtypes = [vp, dp, C.POINTER(C.c_int32), dp]
     lib.cesx_chain_summary_begin.argtypes = [vp, i32, vp]
     lib.cesx_chain_summary_add.argtypes = [vp, vp, i32, vp]
     lib.cesx_chain_summary_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1491,6 +1494,24 @@ class Engine:
                                                      None if xi is None else xi.data_ptr(),
                                                      None if logu is None else logu.data_ptr(), self._stream()))
         self._keep_mh_run = (U, trace, xi, logu)
+
+    # -- pooled step-size adaptation of the leapfrog step (include/cesx.h, cesx_mh_adapt_*): after mh_set_proposal('langevin' / 'hmc') --
+    def mh_adapt_set(self, n_steps, target, gain=2.0, kappa=0.75):
+        """Arm the handle for ``n_steps`` adaptation steps towards the mean acceptance ``target`` (cesx_mh_adapt_set): until
+        the next ``mh_set_proposal`` the ``mh_hmc_*`` / ``gp_hmc_*`` steps run at e S and every accept updates e on the device."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_adapt_set(self._h, int(n_steps), float(target), float(gain), float(kappa)))
+
+    def mh_adapt_read(self):
+        """``dict(multiplier, steps, history (steps, 2))`` of the adaptation phase: the averaged multiplier, the steps made and
+        per step (e_t, mean acceptance probability) (cesx_mh_adapt_read; synchronises)."""
+        mult, done = C.c_double(0.0), C.c_int32(0)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_adapt_read(self._h, C.byref(mult), C.byref(done), None))
+            hist = np.zeros((int(done.value), 2), dtype=np.float64)      # (sized by the count the engine reports; steps are made by this thread alone)
+            if done.value:
+                self._check(self.lib.cesx_mh_adapt_read(self._h, C.byref(mult), C.byref(done), _dptr(hist)))
+        return dict(multiplier=float(mult.value), steps=int(done.value), history=hist)
 
     # -- the Langevin step on a linear map: the gradient as update launches (include/cesx.h, cesx_mh_langevin_lineal_*) --
     def _lvlin_check(self, who, tensors):

@@ -114,7 +114,29 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          states are scored through the Langevin start) and ``trace_stride`` work as for ``update='langevin'``.
                          It refuses what ``update='langevin'`` refuses, and the linear maps with or without
                          ``enable_gradient()`` (no GEMM-form leapfrog yet: a follow-up); ``leapfrog=`` with any other
-                         ``update`` raises ``ValueError`` too.  No step or trajectory-length adaptation.
+                         ``update`` raises ``ValueError`` too.  No trajectory-length adaptation; the step: ``adapt=``.
+  kwarg ``adapt``        model_mh and gp_mh under ``update='langevin'`` and ``'hmc'``, on the host (one chain) and with ``chains=M``:
+                         pooled step-size adaptation.  ``None`` / ``False``: off; ``True``: 100 steps; an int A: A steps; or a dict
+                         with ``steps`` (100, 1 .. 65 536), ``target`` (0.574 under 'langevin', 0.651 under 'hmc'), ``gain`` (2)
+                         and ``kappa`` (0.75); an unknown key raises ``ValueError``.  The first A of the call's ``n_mcmc`` steps
+                         run at e S with one multiplier e shared by all chains (e_1 = 1; include/cesx.h, cesx_mh_adapt_*):
+                             r = xi - (e / 2) g(U);  Q = U + e S r;  L - 1 times  r = r - e g(Q),  Q = Q + e S r;  r = r - (e / 2) g(Q);
+                             d = phi(U) - phi(Q) + |xi|^2 / 2 - |r|^2 / 2;  accepted when log u < d;  alpha = min(1, exp d), 0 for a NaN;
+                             log e_{t+1} = log e_t + (gain / sqrt(t)) (mean_j alpha_j - target);
+                             log ebar_t = t^-kappa log e_{t+1} + (1 - t^-kappa) log ebar_{t-1}
+                         ('langevin' is L = 1; the draws are the sampler's own, one xi and one u per step).  With ``chains=M``
+                         they run on the step path whatever ``fused`` says, the mean and the recursion in ``ad_update_kernel``
+                         behind every accept (kernels_adapt.hip): no synchronisation with the host inside the phase.  They are
+                         kept in the trace like any other step.  Then ``delta' = float(delta) * ebar_A``, the scales are formed
+                         again from ``delta'`` (a fresh run with ``delta=delta'`` sees the same bits), phi and g are re-scored
+                         and the remaining ``n_mcmc - A`` steps run as without ``adapt=``, fused or not.  ``self.adapt`` is a
+                         dict ``steps``, ``target``, ``multiplier``, ``delta`` (= delta'), ``accept_history`` and
+                         ``multiplier_history`` (A,): the mean acceptance probability of every adaptation step and the e it ran
+                         with; ``self.accept`` and ``self.accept_chains`` cover the steps at the frozen step.  A call without
+                         ``adapt=`` removes ``self.adapt``.  ``ValueError`` before an engine is created: another ``update`` (the
+                         random walk's and pCN's proposals are update launches), a linear map (its Langevin step is the GEMM
+                         form of kernels_lvlin.hip: a follow-up), ``A >= n_mcmc``, with ``chains=`` ``A % trace_stride != 0``
+                         and ``summary=True`` with ``burn < A``.  Sharded chains are not pooled (``CESX_EUNSUPPORTED``).
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
   ``self.engine_dtype``, ``self.noise`` ('numpy' | 'device'), ``self.seed``, ``self.device``, ``self.trace_stride``
@@ -306,6 +328,53 @@ def marginal_quantiles(marginals, q):
     return out
 
 
+ADAPT_KEYS = ("steps", "target", "gain", "kappa")
+ADAPT_STEPS_DEFAULT, ADAPT_STEPS_MAX = 100, 65536         # CESX_ADAPT_STEPS_MAX
+ADAPT_TARGETS = {"langevin": 0.574, "hmc": 0.651}         # the optimal acceptance of MALA, and of HMC
+ADAPT_GAIN, ADAPT_KAPPA = 2.0, 0.75
+
+
+def adapt_spec(adapt, update):
+    """What ``adapt=`` asks for: ``None`` (off: ``None`` / ``False``) or a dict ``steps``, ``target``, ``gain``, ``kappa``.
+    ``True`` is 100 steps, an int A is A steps, a dict may hold the four keys (``target`` defaults to 0.574 under
+    ``update='langevin'`` and 0.651 under ``'hmc'``, ``gain`` to 2, ``kappa`` to 0.75).  Pure; every refusal is a ValueError."""
+    if adapt is None or adapt is False:
+        return None
+    if update not in ADAPT_TARGETS:
+        raise ValueError("adapt=%r adapts the step of update='langevin' and 'hmc' (the multiplier scales the leapfrog step of "
+                         "the gradient kernels); update=%r proposes through an update launch, whose scales are an image of "
+                         "the proposal: tune delta by hand there" % (adapt, update))
+    if adapt is True:
+        adapt = {}
+    elif isinstance(adapt, (int, np.integer)):
+        adapt = dict(steps=adapt)
+    if not isinstance(adapt, dict):
+        raise ValueError("adapt must be None, False, True, an integer or a dict with keys from %s, got %r" % (ADAPT_KEYS, adapt))
+    unknown = [k for k in adapt if k not in ADAPT_KEYS]
+    if unknown:
+        raise ValueError("adapt: unknown key(s) %s (known: %s)" % (sorted(map(str, unknown)), ", ".join(ADAPT_KEYS)))
+    steps = adapt.get("steps", ADAPT_STEPS_DEFAULT)
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= ADAPT_STEPS_MAX:
+        raise ValueError("adapt: steps must be an integer in [1, %d], got %r" % (ADAPT_STEPS_MAX, steps))
+    vals = {}
+    for name, default, ok, what in (("target", ADAPT_TARGETS[update], lambda v: 0.0 < v < 1.0, "in (0, 1)"),
+                                    ("gain", ADAPT_GAIN, lambda v: np.isfinite(v) and v > 0.0, "finite and > 0"),
+                                    ("kappa", ADAPT_KAPPA, lambda v: 0.5 < v <= 1.0, "in (0.5, 1]")):
+        v = adapt.get(name, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not ok(v):
+            raise ValueError("adapt: %s must be a number %s, got %r" % (name, what, v))
+        vals[name] = float(v)
+    return dict(steps=int(steps), **vals)
+
+
+def adapt_recursion(log_e, log_ebar, t, abar, target, gain, kappa):
+    """Step t >= 1 of the recursion of include/cesx.h (cesx_mh_adapt_*): ``(log e_{t+1}, log ebar_t)`` from ``log e_t``,
+    ``log ebar_{t-1}`` and the mean acceptance probability ``abar`` of step t."""
+    log_e = log_e + gain / np.sqrt(float(t)) * (abar - target)
+    w = float(t) ** -kappa
+    return log_e, w * log_e + (1.0 - w) * log_ebar
+
+
 class MCMC(object):
     """Metropolis-Hastings samplers of ces/sample.py (:12-202)."""
 
@@ -358,7 +427,13 @@ class MCMC(object):
             raise ImportError("MCMC.gp_mh needs a trained GP emulator: pass gpmodels= or train enka.gpmodels with "
                               "ces_amd.emulate.train_gps (the reference builds it with GPflow, ces/emulate.py, which is "
                               "not installed; ces/sample.py fails when it imports gpflow, :8)")
-        self._hmc_leapfrog(kwargs)                        # build-only; refused before any engine is created
+        leapfrog = self._hmc_leapfrog(kwargs)             # build-only; refused before any engine is created
+        if kwargs.get("adapt", None) not in (None, False) and kwargs.get("update", None) in ("langevin", "hmc"):
+            if leapfrog is None:                          # (what update= refuses stays refused, with its own message)
+                self._langevin_refusals(kwargs, prior)
+            else:
+                self._as_hmc(self._langevin_refusals, kwargs, prior)
+        self._adapt_of(kwargs, n_mcmc)
         if kwargs.get("chains", None) is not None:
             return self._gp_mh_device(enka, n_mcmc, prior, delta, enka_scaling, kwargs)
         if kwargs.get("fused", None) is not None:
@@ -442,6 +517,70 @@ class MCMC(object):
         if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= L <= MCMC.HMC_LEAPFROG_MAX:
             raise ValueError("update='hmc': leapfrog must be an integer in [1, %d], got %r" % (MCMC.HMC_LEAPFROG_MAX, L))
         return int(L)
+
+    def _adapt_of(self, kwargs, n_mcmc, model=None):
+        """The ``adapt_spec`` of a call, or None; what ``adapt=`` does not go with is a ValueError here, before an engine is
+        created.  A call without ``adapt=`` removes ``self.adapt``: the attribute is always the last call's."""
+        spec = adapt_spec(kwargs.get("adapt", None), kwargs.get("update", None))
+        if spec is None:
+            self.__dict__.pop("adapt", None)
+            return None
+        A = spec["steps"]
+        if model is not None and (getattr(model, "model_name", None) in ("lineal", "lineal_log") or hasattr(model, "langevin_device")):
+            raise ValueError("adapt=: %r is a linear map, whose Langevin step is the GEMM form of kernels_lvlin.hip (the "
+                             "gradient on the update kernels); the multiplier lives in the leapfrog kernels: a follow-up -- "
+                             "tune delta by hand, or adapt on elliptic / banana or on the emulator (gp_mh)" % (model,))
+        if A >= int(n_mcmc):
+            raise ValueError("adapt=: the first %d of the call's n_mcmc steps adapt, and n_mcmc = %d leaves none at the step "
+                             "found" % (A, int(n_mcmc)))
+        if kwargs.get("chains", None) is not None:
+            stride = max(1, int(self.trace_stride))
+            if A % stride:
+                raise ValueError("adapt=: %d adaptation steps at trace_stride %d: the state after the last of them must be a "
+                                 "kept one, and fused launches start on a stride boundary; make steps a multiple of the stride"
+                                 % (A, stride))
+            burn = kwargs.get("burn", None)
+            if kwargs.get("summary", None) is True and (isinstance(burn, bool) or not isinstance(burn, (int, np.integer)) or burn < A):
+                raise ValueError("adapt=: summary=True with burn=%r would summarise states drawn while the step still moved; "
+                                 "pass burn >= %d (the adaptation steps)" % (burn, A))
+        return spec
+
+    def _adapt_host(self, spec, score, scales, current, leapfrog, samples):
+        """The adaptation phase on the host, one chain (M = 1 of include/cesx.h, cesx_mh_adapt_*): ``spec['steps']`` steps from
+        ``current`` at e S, e following the recursion; every state is appended to ``samples``.  ``score`` is the sampler's own
+        (phi, g = S^T grad phi).  Returns (the last state, the multiplier ebar_A, the history (A, 2) of (e_t, alpha_t))."""
+        L = 1 if leapfrog is None else leapfrog
+        p = scales.shape[0]
+        phi, g = score(current)
+        log_e = log_ebar = 0.0
+        hist = np.zeros((spec["steps"], 2))
+        for t in range(1, spec["steps"] + 1):
+            e = float(np.exp(log_e))
+            xi = np.random.normal(0, 1, p)
+            with np.errstate(invalid="ignore", over="ignore"):
+                r = xi - 0.5 * e * g
+                q = current + e * np.matmul(scales, r)
+                for l in range(1, L + 1):
+                    phi_q, g_q = score(q)
+                    if l < L:
+                        r = r - e * g_q
+                        if not np.isfinite(phi_q):
+                            r = r * np.nan
+                        q = q + e * np.matmul(scales, r)
+                    else:
+                        r = r - 0.5 * e * g_q
+                d = phi - phi_q + (0.5 * (xi * xi).sum() - 0.5 * (r * r).sum())
+                alpha = 1.0 if d >= 0 else float(np.exp(d)) if d < 0 else 0.0
+            if np.log(np.random.uniform()) < d:
+                current, phi, g = np.copy(q), phi_q, g_q
+            samples.append(current.flatten())
+            hist[t - 1] = e, alpha
+            log_e, log_ebar = adapt_recursion(log_e, log_ebar, t, alpha, spec["target"], spec["gain"], spec["kappa"])
+        return current, float(np.exp(log_ebar)), hist
+
+    def _adapt_result(self, spec, multiplier, delta, hist):
+        self.adapt = dict(steps=spec["steps"], target=spec["target"], multiplier=float(multiplier), delta=float(delta),
+                          accept_history=np.array(hist[:, 1]), multiplier_history=np.array(hist[:, 0]))
 
     @staticmethod
     def _as_hmc(refusals, *args):
@@ -542,6 +681,13 @@ class MCMC(object):
         else:
             samples = [current.flatten()]
         accept = 0.
+        adapt = self._adapt_of(kwargs, n_mcmc)
+        if adapt:                                         # the first steps at e S; then the scales re-formed from delta', phi and g re-scored
+            current, mult, hist = self._adapt_host(adapt, score, scales, current, leapfrog, samples)
+            delta = float(delta) * mult
+            scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(p, p)) if enka_scaling else delta * np.eye(p)
+            self._adapt_result(adapt, mult, delta, hist)
+            n_mcmc = n_mcmc - adapt["steps"]
         phi_current, g_current = score(current)
         for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
             xi = np.random.normal(0, 1, p)
@@ -586,13 +732,14 @@ class MCMC(object):
             self._model_langevin_refusals(model, prior, kwargs.get("chains", None) is not None)
         if leapfrog is not None:
             self._model_hmc_refusals(model, prior, kwargs.get("chains", None) is not None)
+        adapt = self._adapt_of(kwargs, n_mcmc, model)
         if kwargs.get("chains", None) is not None:
             return self._model_mh_device(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, kwargs)
         if kwargs.get("fused", None) is not None:
             raise ValueError("fused=%r chooses between the device paths of chains=M; the host path has one" % (kwargs.get("fused"),))
         _host_has_no_summary(kwargs)
         if kwargs.get("update", None) in ("langevin", "hmc"):
-            return self._model_mh_langevin_host(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, leapfrog=leapfrog)
+            return self._model_mh_langevin_host(model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, leapfrog=leapfrog, adapt=adapt)
         # RW needs the proposal distribution (:122-126)
         if enka_scaling:
             scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(enka.p, enka.p))
@@ -675,7 +822,7 @@ class MCMC(object):
                              "update='langevin' after enable_gradient(), or update='hmc' on elliptic / banana" % (model,))
         MCMC._as_hmc(MCMC._model_langevin_refusals, model, prior, device)
 
-    def _model_mh_langevin_host(self, model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, leapfrog=None):
+    def _model_mh_langevin_host(self, model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, leapfrog=None, adapt=None):
         """``model_mh(update='langevin')`` on the host, one chain: the restatement the device is held to.  The scales and
         the start are the random walk's, phi has the prior term, g = S^T grad phi with
         grad phi = DG^T Gamma^{-1} (G - y) + cov^{-1} (u - mean) from ``model.jacobian``; the proposal
@@ -704,6 +851,12 @@ class MCMC(object):
         else:
             samples = [current.flatten()]
         accept = 0.
+        if adapt:                                         # the first steps at e S; then the scales re-formed from delta', phi and g re-scored
+            current, mult, hist = self._adapt_host(adapt, score, scales, current, leapfrog, samples)
+            delta = float(delta) * mult
+            scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(p, p)) if enka_scaling else delta * np.eye(p)
+            self._adapt_result(adapt, mult, delta, hist)
+            n_mcmc = n_mcmc - adapt["steps"]
         phi_current, g_current = score(current)
         for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
             xi = np.random.normal(0, 1, p)
@@ -739,7 +892,7 @@ class MCMC(object):
         return self._mh_eng
 
     def _mh_device(self, enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi, fused=False,
-                   fused_work=0, langevin=False, fused_steps_max=None):
+                   fused_work=0, langevin=False, fused_steps_max=None, adapt=None, bind_adapt=None, delta=1.):
         """M = kwargs['chains'] chains on the engine: what ``model_mh(chains=)`` and ``gp_mh(chains=)`` have in common.
 
         Gamma                    the data covariance handed to ``set_problem``
@@ -761,6 +914,12 @@ class MCMC(object):
                                  ``score_accept``
         fused_work               the arithmetic of one fused step of all chains, in the units of ``GP_FUSED_WORK`` (0: a launch
                                  is capped by ``FUSED_STEPS_MAX`` and ``FUSED_BUFFER_BYTES`` alone)
+        adapt, bind_adapt, delta ``adapt_spec``'s dict (``_adapt_of`` has refused what it does not go with): the call's first
+                                 ``adapt['steps']`` steps run on the step path of an armed engine (``eng.mh_adapt_set``) through
+                                 the hooks of ``bind_adapt(eng, M)`` -- the leapfrog hooks, L = 1 for update='langevin' --;
+                                 then ``eng.mh_adapt_read`` (the one synchronisation), the scales re-formed by
+                                 ``scales_of(update, delta * multiplier)``, ``mh_set_proposal``, ``bind`` and ``score_start``
+                                 again, and the remaining steps as without it.  ``self.adapt`` holds what was found
         ``self.fused_launches`` is the number of fused launches of the call, 0 on the step path.
         ``kwargs['summary'] = True`` (with ``kwargs['burn']`` steps left out) keeps the kept states on the device and sums
         them there (``eng.chain_summary_*``): ``self.summary`` (``finalise_summary``) instead of a trace in ``self.samples``,
@@ -822,7 +981,9 @@ class MCMC(object):
         eng = self._mh_engine(p, n, M)
         eng.set_problem(np.asarray(self.y_obs, dtype=np.float64).reshape(n), Gamma, mu, cov, mu)
         eng.mh_set_proposal(update, scales, kwargs.get("beta", 0.5))
-        score_start, score_accept, run_steps, propose = (tuple(bind(eng, M)) + (None,))[:4]
+        if adapt:                                         # armed: the leapfrog launches run at e S until the next mh_set_proposal
+            eng.mh_adapt_set(adapt["steps"], adapt["target"], adapt["gain"], adapt["kappa"])
+        score_start, score_accept, run_steps, propose = (tuple((bind_adapt if adapt else bind)(eng, M)) + (None,))[:4]
         P = eng.empty(p)
         self.fused_launches = 0
 
@@ -845,18 +1006,18 @@ class MCMC(object):
         if marg:                                          # and are counted there: cesx_chain_hist_*, the same slices
             eng.chain_hist_begin(marg["edges"], marg["edges2d"], marg["pairs"])
 
-        if fused:
+        def run_fused(k_first, n_steps):
             # launches of at most K_max steps (cesx_mh_run_map / cesx_gp_run; fused_chunks): K_max a multiple of the stride --
             # so that a launch's own count of kept states continues the run's -- and small enough that one launch's noise and
             # trace stay under the budget and, for the emulator, its arithmetic under GP_FUSED_WORK.
             # The trace buffer is allocated once per run; each launch's trace crosses to the host once.
             esz = eng.np_dtype.itemsize
             per_step = -(-M * p * esz // stride) + (M * (p * esz + 8) if self.noise == "numpy" else 0)     # trace; xi and log u
-            K_max, chunks = fused_chunks(n_mcmc, stride, fused_steps_max or self.FUSED_STEPS_MAX, self.FUSED_BUFFER_BYTES, per_step,
+            K_max, chunks = fused_chunks(n_steps, stride, fused_steps_max or self.FUSED_STEPS_MAX, self.FUSED_BUFFER_BYTES, per_step,
                                          self.GP_FUSED_WORK if fused_work else None, fused_work)
-            trace = torch.empty((min(K_max, n_mcmc) // stride, p, M), dtype=eng.torch_dtype, device=eng.device)
+            trace = torch.empty((min(K_max, n_steps) // stride, p, M), dtype=eng.torch_dtype, device=eng.device)
             for i, K in enumerate(tqdm(chunks, desc="MCMC samples: ", disable=self.mute_bar)):
-                k0 = i * K_max
+                k0 = k_first + i * K_max
                 xi_t = logu_t = None
                 if self.noise == "numpy":                 # the step loop's draws in the step loop's order, stacked
                     xi, logu = np.empty((K, p, M)), np.empty((K, M))
@@ -877,8 +1038,9 @@ class MCMC(object):
                     kept.extend(tr.cpu().numpy().astype(np.float64))
             if (summary or n_mcmc % stride) and n_mcmc > 0:   # the run's last state, where the trace does not hold it
                 kept.append(eng.to_host(U))
-        else:
-            for k in tqdm(range(n_mcmc), desc="MCMC samples: ", disable=self.mute_bar):
+
+        def run_step_path(k_first, n_steps):
+            for k in tqdm(range(k_first, k_first + n_steps), desc="MCMC samples: ", disable=self.mute_bar):
                 step = base + k
                 xi_t = logu_t = None
                 if self.noise == "numpy":                     # the reference's draws in the reference's order
@@ -900,6 +1062,21 @@ class MCMC(object):
                         kept.append(eng.to_host(U))
                 elif (k + 1) % stride == 0 or k + 1 == n_mcmc:
                     kept.append(eng.to_host(U))
+
+        first = 0
+        if adapt:
+            # the adaptation steps on the step path whatever ``fused`` says, kept in the trace like any other step; then the
+            # join: read (the one synchronisation), delta' = delta * multiplier, the scales re-formed from delta' by
+            # scales_of's own expression (a fresh run with delta=delta' sees the same bits), the proposal, the hooks, phi and g
+            first = adapt["steps"]
+            run_step_path(0, first)
+            found = eng.mh_adapt_read()
+            delta = float(delta) * found["multiplier"]
+            self._adapt_result(adapt, found["multiplier"], delta, found["history"])
+            eng.mh_set_proposal(update, scales_of(update, delta), kwargs.get("beta", 0.5))
+            score_start, score_accept, run_steps, propose = (tuple(bind(eng, M)) + (None,))[:4]
+            score_start(U)
+        (run_fused if fused else run_step_path)(first, n_mcmc - first)
         if summary:
             self.summary = finalise_summary(eng.chain_summary_read(), n_draws, M)
         self.__dict__.pop("marginals", None)             # a call without marginals= leaves no earlier call's counts behind
@@ -915,7 +1092,7 @@ class MCMC(object):
             new = new[:, :, 0]
         self.samples = new if prev is None else np.concatenate([prev, new], axis=1)
         self.accept = rate
-        self.accept_chains = per.astype(np.float64) / max(1, n_mcmc)
+        self.accept_chains = per.astype(np.float64) / max(1, n_mcmc - first)
         self.samples_device = U
         self._mh_next_step = base + n_mcmc
 
@@ -941,7 +1118,7 @@ class MCMC(object):
         fused = (has_fused and default) if fused is None else bool(fused)
         p, n = enka.p, enka.n_obs
 
-        def scales_of(update):                            # exactly as the reference forms them (:122-129)
+        def scales_of(update, delta=delta):               # exactly as the reference forms them (:122-129)
             if enka_scaling:
                 scales = delta * np.linalg.cholesky(np.cov(enka.Ustar).reshape(p, p))
             else:
@@ -1021,7 +1198,7 @@ class MCMC(object):
                 eng.mh_langevin_run_map(step, K, U, stride=stride, trace=trace, xi=xi, logu=logu)
             return lv_start, lv_accept, run_steps if fused else None, lv_propose
 
-        def bind_hmc(eng, M):
+        def bind_hmc(eng, M, leapfrog=leapfrog, fused=fused):
             # bind_langevin with the leapfrog loop on the host: per position the map and its Jacobian at Q, then the kick
             import torch
             out = (torch.empty((n, M), dtype=torch.float64, device=eng.device),
@@ -1087,10 +1264,12 @@ class MCMC(object):
             bind_langevin = bind_langevin_lineal
         if leapfrog is not None:
             bind_langevin = bind_hmc
+        adapt = self._adapt_of(kwargs, n_mcmc, model)     # (model_mh has refused what it does not go with)
         # a resume under update='langevin' scores the resumed states whatever the noise: the chains need their g as well as phi
         self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_langevin if langevin else bind_pde if pde else bind,
                         resume_keeps_start_phi=not langevin, fused=fused, langevin=langevin,
-                        fused_steps_max=None if leapfrog is None else self.HMC_GRADS_MAX // leapfrog)
+                        fused_steps_max=None if leapfrog is None else self.HMC_GRADS_MAX // leapfrog, adapt=adapt, delta=delta,
+                        bind_adapt=lambda eng, M: bind_hmc(eng, M, leapfrog or 1, False))      # (the step path; 'langevin' is L = 1)
 
     def _gp_mh_device(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
         import torch
@@ -1179,10 +1358,10 @@ class MCMC(object):
                              "training points; train the emulator with RBF, Matern32 or Matern52"
                              % (kwargs.get("update"), int(np.nonzero(np.asarray(img["family"]) == 1)[0][0])))
 
-        def scales_of(update):                            # (:23-26; pCN takes the same scales)
+        def scales_of(update, delta=delta):               # (:23-26; pCN takes the same scales)
             return delta * np.linalg.cholesky(np.cov(enka.Ustar)) if enka_scaling else delta * np.eye(p)
 
-        def bind(eng, M):
+        def bind(eng, M, leapfrog=leapfrog):
             eng.gp_set(img)
             if mode == "dense":
                 eng.gp_dense_set(VD_k, mG, logdet)
@@ -1243,4 +1422,5 @@ class MCMC(object):
         Jp = (int(img["Jt"]) + 15) // 16 * 16
         work = int(kwargs["chains"]) * n_gp * Jp * (Jp // 2 + p + 8) if fused else 0
         self._mh_device(enka, n_mcmc, prior, kwargs, G, scales_of, bind, resume_keeps_start_phi=False, fused=fused,
-                        fused_work=work, langevin=True)
+                        fused_work=work, langevin=True, adapt=self._adapt_of(kwargs, n_mcmc), delta=delta,
+                        bind_adapt=lambda eng, M: bind(eng, M, leapfrog or 1))      # (the leapfrog hooks; 'langevin' is L = 1)

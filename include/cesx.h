@@ -699,6 +699,41 @@ int cesx_gp_hmc_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev
                        const double* var_dev, const double* dmean_dev, const double* dvar_dev, const double* logu_dev, void* stream);
 int cesx_mh_hmc_run_map(cesx_handle h, uint64_t step_index, int n_steps, int leapfrog, int stride, void* U_dev, void* trace_dev,
                         const void* xi_dev, const double* logu_dev, void* stream);
+/* MCMC.model_mh / gp_mh(chains=M, adapt=): pooled step-size adaptation of the leapfrog step above (kernels_adapt.hip and the
+   ADAPT instantiations of kernels_hmc.hip).  One scalar multiplier e, shared by all chains, e_1 = 1.  Adaptation step
+   t = 1 .. n_steps is the HMC step with e S in place of S, written without rescaling anything stored (g = S^T grad phi as the
+   Langevin step keeps it):
+       r = xi - (e / 2) g(U);   Q = U + e S r
+       L - 1 times:   phi(Q), g(Q);   r = r - e g(Q);   Q = Q + e S r
+       last:          phi(Q), g(Q);   r = r - (e / 2) g(Q)
+       d = phi(U) - phi(Q) + (|xi|^2 / 2 - |r|^2 / 2);   accepted iff log u < d
+       alpha_j = 1 if d >= 0, exp(d) if d < 0, 0 if d is NaN
+   (the Langevin step is L = 1).  Behind the accept, in the same call and on the same stream, ad_update_kernel takes
+   abar_t = (1 / M) sum_j alpha_j -- fp64, a fixed order, no atomics -- and
+       log e_{t+1} = log e_t + (gain / sqrt(t)) (abar_t - target)
+       log ebar_t  = t^-kappa log e_{t+1} + (1 - t^-kappa) log ebar_{t-1},      log ebar_0 = 0
+   a Robbins-Monro recursion on the mean acceptance probability with a polynomially weighted average of its iterates.  The
+   next step's kernels read e_{t+1} from device memory; stream order hands it over and nothing synchronises with the host
+   inside the phase.  The result is multiplier = ebar_{n_steps}.  The draws are the sampler's own: one block and one log u per
+   step under the step index the caller passes.
+       cesx_mh_adapt_set    after cesx_mh_set_proposal with CESX_MH_LANGEVIN: allocates alpha [J], the state and the history,
+                            sets t = 0 and e = 1 and ARMS the handle.  While armed, cesx_mh_hmc_begin / _leap / _accept and
+                            cesx_gp_hmc_leap / _accept launch the ADAPT kernels, every accept is followed by the recursion, and
+                            after n_steps accepts they return CESX_ESTATE (read, then set the proposal).  While armed,
+                            cesx_mh_hmc_run_map, every cesx_*_langevin_propose / _accept / _run_map and the
+                            cesx_mh_langevin_lineal_* family return CESX_ESTATE and launch nothing.  The starts
+                            (cesx_mh_langevin_start, cesx_gp_langevin_start) stay available.  cesx_mh_set_proposal and
+                            cesx_set_problem disarm the handle and drop the state.
+       cesx_mh_adapt_read   synchronises; multiplier = ebar_t of the steps made (1 before the first), steps_done, and into
+                            history_host (or NULL) steps_done rows (e_t, abar_t): the multiplier step t ran with and the mean
+                            acceptance probability it met.  The handle stays armed.
+   CESX_EINVAL: n_steps outside 1 .. CESX_ADAPT_STEPS_MAX, target outside (0, 1), gain <= 0, kappa outside (0.5, 1], a null
+   pointer.  CESX_EUNSUPPORTED: a shard (J_local != J_global; pooling across ranks is a reduce this engine does not make).
+   CESX_ESTATE: cesx_mh_adapt_set without a proposal of kind CESX_MH_LANGEVIN, cesx_mh_adapt_read on a handle that is not
+   armed.  None of these launches anything or touches U_dev, the chains' phi, g or the counters. */
+#define CESX_ADAPT_STEPS_MAX 65536
+int cesx_mh_adapt_set(cesx_handle h, int n_steps, double target, double gain, double kappa);
+int cesx_mh_adapt_read(cesx_handle h, double* multiplier, int* steps_done, double* history_host);
 
 /* ---- Streaming summaries of the chains' draws (MCMC(..., chains=M, summary=True); kernels_chainsum.hip) --
    The sums behind the pooled mean and covariance, the split R-hat and an effective sample size of a run of
