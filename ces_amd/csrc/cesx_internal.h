@@ -779,6 +779,11 @@ int launch_gp_langevin(Engine& e, int what, int mode, const void* X, const doubl
 int launch_lvlin_score(Engine& e, bool start, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s);
 int launch_lvlin_z(Engine& e, hipStream_t s);
 int launch_lvlin_exph(Engine& e, const void* X, void* t0, hipStream_t s);
+// kernels_hmclin.hip: the leapfrog step on a linear map (cesx_mh_hmc_lineal_*).  launch_hl_kick: begin -- r = mh.xi - (e / 2) mh.lin_g
+// (unarmed: launch_lvlin_z, r in mh.lin_z) --, otherwise r -= e mh.lin_gp; armed: r in mh.lin_r and z = e r into mh.lin_z.
+// launch_hl_accept: launch_lvlin_score's accept with |r - (e / 2) g_Q|^2 from the momentum block as the second norm, and alpha armed
+int launch_hl_kick(Engine& e, bool begin, hipStream_t s);
+int launch_hl_accept(Engine& e, const void* X, const void* G, void* U, const double* logu, unsigned step, hipStream_t s);
 // kernels_gp.hip: phi of the states X from the GP rows (mode CESX_GP_GAMMA / _VAR / _GAMMA_VAR); start: into mh.phi,
 // counters cleared; otherwise the accept test of step word `step` and the masked copy X -> U
 int launch_gp_score(Engine& e, int mode, bool start, const void* X, const double* mean, const double* var, void* U,

@@ -41,6 +41,9 @@ struct MhState {
     DevBuf<void> lin_ba, lin_bb;       // [rpad] the biases of the two launches
     DevBuf<void> lin_g, lin_gp, lin_z; // [p][J] engine dtype: g of the chains' states, of the proposals, and z = xi - g / 2
     DevBuf<void> lin_t;                // lineal_log: [p][J] t0, then h = exp(X) (.) t0
+    // leapfrog on a linear map (cesx_mh_hmc_lineal_*, kernels_hmclin.hip): the momentum r lives in lin_z; armed, r in lin_r and z = e r in lin_z
+    DevBuf<void> lin_r;                // [p][J] engine dtype: the momentum of an armed handle's trajectory (allocated by its first begin)
+    int hl_leaps = 0;                  // cesx_mh_hmc_lineal_leap calls since the begin
     // pooled step-size adaptation (cesx_mh_adapt_*, kernels_adapt.hip): while armed the hm_* launches take e S for S
     bool ad_armed = false;             // a cesx_mh_adapt_set since the last cesx_mh_set_proposal / cesx_set_problem
     int ad_n = 0, ad_done = 0;         // adaptation steps asked for, and accepts made (each followed by ad_update_kernel)

@@ -2311,6 +2311,89 @@ int cesx_mh_langevin_lineal_g(cesx_handle h, double* g_host) {
     return CESX_OK;
 }
 
+// ---- the leapfrog step on a linear map: the Langevin step's launches around a momentum block (include/cesx.h; kernels_hmclin.hip) ----
+
+// lin_check_state(e, true) without its blanket refusal of an armed handle; `begun`: a cesx_mh_hmc_lineal_begin too
+static int hl_check_state(Engine& e, bool begun) {
+    if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN || !e.mh.lin) { e.err = "cesx_mh_hmc_lineal: no lineal image (cesx_mh_langevin_lineal_set after cesx_mh_set_proposal with CESX_MH_LANGEVIN)"; return CESX_ESTATE; }
+    if (!(e.mh.started && e.mh.lin_started)) { e.err = "cesx_mh_hmc_lineal: the last start was not cesx_mh_langevin_lineal_start"; return CESX_ESTATE; }
+    if (begun && !e.mh.hm_begun) { e.err = "cesx_mh_hmc_lineal: no cesx_mh_hmc_lineal_begin since the start or the last accept"; return CESX_ESTATE; }
+    if (e.mh.ad_armed && e.mh.ad_done >= e.mh.ad_n) { e.err = "cesx_mh_hmc_lineal: the adaptation steps of cesx_mh_adapt_set are done: read the multiplier (cesx_mh_adapt_read), then set the proposal (cesx_mh_set_proposal)"; return CESX_ESTATE; }
+    return CESX_OK;
+}
+
+// out = Q + S z with z in mh.lin_z: the triangular launch of cesx_mh_langevin_lineal_propose (out never aliases Q: the callers refuse it)
+static int hl_drift(Engine& e, const void* Q, void* out, hipStream_t s) {
+    return launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.W, .Wf = e.mh.Wf, .ktot = e.kp,
+                                         .src = {{e.mh.lin_z, e.p, 0, 1}}, .nsrc = 1, .add1 = {Q, nullptr, 1.0}, .out = out}, s);
+}
+
+int cesx_mh_hmc_lineal_begin(cesx_handle h, uint64_t step_index, const void* U, const void* xi, void* Q, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hl_check_state(e, false));
+    if (!U || !Q) { e.err = "cesx_mh_hmc_lineal_begin: null pointer"; return CESX_EINVAL; }
+    if (U == Q) { e.err = "cesx_mh_hmc_lineal_begin: Q must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_hmc_lineal_begin: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    hipStream_t s = (hipStream_t)stream;
+    if (e.mh.ad_armed) TRY_BUF(e.mh.lin_r.ensure((size_t)e.p * (size_t)e.J * e.esz));      // (r beside z = e r)
+    // the block stays in engine memory, as the Langevin proposal keeps it: the accept step needs |xi|^2
+    if (xi) CESX_HIP(hipMemcpyAsync(e.mh.xi, xi, (size_t)e.p * (size_t)e.J * e.esz, hipMemcpyDeviceToDevice, s));
+    else TRY(launch_noise(e, mh_step_word(step_index), e.mh.xi, s));
+    TRY(launch_hl_kick(e, true, s));
+    TRY(hl_drift(e, U, Q, s));
+    e.mh.hm_begun = true; e.mh.hl_leaps = 0;
+    e.mh.lv_proposed = false;              // (a Langevin proposal's block is overwritten)
+    return CESX_OK;
+}
+
+int cesx_mh_hmc_lineal_leap(cesx_handle h, const void* Q, const void* GQ, void* Qnext, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hl_check_state(e, true));
+    if (!Q || !GQ || !Qnext) { e.err = "cesx_mh_hmc_lineal_leap: null pointer"; return CESX_EINVAL; }
+    if (Q == Qnext) { e.err = "cesx_mh_hmc_lineal_leap: Qnext must not alias Q (the drift launch reads Q while it writes Qnext)"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    hipStream_t s = (hipStream_t)stream;
+    WHITEN(e, GQ, s, true);
+    TRY(lin_grad(e, Q, GQ, e.mh.lin_gp.get(), s));      // (no phi: neither the score kernel nor the Li product of a dense Sigma)
+    TRY(launch_hl_kick(e, false, s));
+    TRY(hl_drift(e, Q, Qnext, s));
+    ++e.mh.hl_leaps;
+    return CESX_OK;
+}
+
+int cesx_mh_hmc_lineal_accept(cesx_handle h, uint64_t step_index, void* U, const void* Q, const void* GQ, const double* logu,
+                              void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hl_check_state(e, true));
+    if (!U || !Q || !GQ) { e.err = "cesx_mh_hmc_lineal_accept: null pointer"; return CESX_EINVAL; }
+    if (U == Q) { e.err = "cesx_mh_hmc_lineal_accept: Q must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_mh_hmc_lineal_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    hipStream_t s = (hipStream_t)stream;
+    if (!e.mh.ad_armed && e.mh.hl_leaps == 0) {
+        // L = 1: xi, g(U) and g(Q) are the Langevin accept's inputs, and its launches give its bits
+        TRY(lin_score(e, false, Q, GQ, U, logu, mh_step_word(step_index), s));
+    } else {
+        WHITEN(e, GQ, s, true);
+        if (!e.diag_sigma)
+            TRY(launch_update(e, UpdateLaunch{.out_rows = e.p, .W = e.mh.Li, .Wf = e.mh.Li_f, .ktot = e.kp, .bias = e.mh.lb,
+                                              .src = {{Q, e.p, 0, 1}}, .nsrc = 1, .out = e.mh.w}, s));
+        TRY(lin_grad(e, Q, GQ, e.mh.lin_gp.get(), s));
+        TRY(launch_hl_accept(e, Q, GQ, U, logu, mh_step_word(step_index), s));
+        if (e.mh.ad_armed) { TRY(launch_adapt_update(e, s)); ++e.mh.ad_done; }
+    }
+    e.mh.hm_begun = false;
+    ++e.mh.steps;
+    return CESX_OK;
+}
+
 // ---- Streaming summaries of the chains' draws (MCMC(..., chains=M, summary=True); kernels_chainsum.hip) ----
 
 int cesx_chain_summary_begin(cesx_handle h, int n_draws, void* stream) {

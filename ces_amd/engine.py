@@ -39,6 +39,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_map_jac", "cesx_mh_langevin_start", "cesx_mh_langevin_propose", "cesx_mh_langevin_accept", "cesx_mh_langevin_run_map",
            "cesx_mh_langevin_lineal_set", "cesx_mh_langevin_lineal_start", "cesx_mh_langevin_lineal_propose",
            "cesx_mh_langevin_lineal_accept", "cesx_mh_langevin_lineal_g",
+           "cesx_mh_hmc_lineal_begin", "cesx_mh_hmc_lineal_leap", "cesx_mh_hmc_lineal_accept",
            "cesx_mh_hmc_begin", "cesx_mh_hmc_leap", "cesx_mh_hmc_accept", "cesx_gp_hmc_leap", "cesx_gp_hmc_accept", "cesx_mh_hmc_run_map",
            "cesx_mh_adapt_set", "cesx_mh_adapt_read",
            "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read",
@@ -313,6 +314,9 @@ def load_library(path=None):
     lib.cesx_mh_langevin_lineal_propose.argtypes = [vp, u64, vp, vp, vp, vp]
     lib.cesx_mh_langevin_lineal_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp]
     lib.cesx_mh_langevin_lineal_g.argtypes = [vp, dp]
+    lib.cesx_mh_hmc_lineal_begin.argtypes = [vp, u64, vp, vp, vp, vp]
+    lib.cesx_mh_hmc_lineal_leap.argtypes = [vp, vp, vp, vp, vp]
+    lib.cesx_mh_hmc_lineal_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp]
     lib.cesx_mh_hmc_begin.argtypes = [vp, u64, vp, vp, vp, vp]
     lib.cesx_mh_hmc_leap.argtypes = [vp, vp, vp, vp, vp]
     lib.cesx_mh_hmc_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
@@ -1571,6 +1575,42 @@ class Engine:
         buf = np.zeros((self.p, self.J), dtype=np.float64)
         self._check(self.lib.cesx_mh_langevin_lineal_g(self._h, _dptr(buf)))
         return buf
+
+    # -- the leapfrog step on a linear map (include/cesx.h, cesx_mh_hmc_lineal_*): after mh_langevin_lineal_start --
+    def mh_hmc_lineal_begin(self, step_index, U, xi=None, out=None):
+        """r = xi - (e / 2) g(U) and the first leapfrog position Q = U + e S r (cesx_mh_hmc_lineal_begin; e = 1 unless the
+        handle is armed); xi None: drawn on device in the MH counter domain of step_index.  The engine keeps the block and r."""
+        out = self.empty(self.p) if out is None else out
+        self._lvlin_check("mh_hmc_lineal_begin", (("U", U, self.p, self.torch_dtype), ("xi", xi, self.p, self.torch_dtype),
+                                                  ("out", out, self.p, self.torch_dtype)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_hmc_lineal_begin(self._h, int(step_index), U.data_ptr(),
+                                                          None if xi is None else xi.data_ptr(), out.data_ptr(), self._stream()))
+        self._keep_hl_b = (U, xi, out)
+        return out
+
+    def mh_hmc_lineal_leap(self, Q, GQ, out):
+        """g(Q) from the map ``GQ`` at Q, the full kick r = r - e g(Q) and the next position ``out`` = Q + e S r
+        (cesx_mh_hmc_lineal_leap); ``out`` is another buffer than ``Q``."""
+        self._lvlin_check("mh_hmc_lineal_leap", (("Q", Q, self.p, self.torch_dtype), ("GQ", GQ, self.n_obs, self.torch_dtype),
+                                                 ("out", out, self.p, self.torch_dtype)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_hmc_lineal_leap(self._h, Q.data_ptr(), GQ.data_ptr(), out.data_ptr(), self._stream()))
+        self._keep_hl_l = (Q, GQ, out)
+        return out
+
+    def mh_hmc_lineal_accept(self, step_index, U, Q, GQ, logu=None):
+        """phi(Q) and g(Q) from the map ``GQ`` at the last position, the half kick, the test
+        log u < phi(U) - phi(Q) + |xi|^2 / 2 - |r|^2 / 2, U := Q and g := g(Q) on the accepted columns
+        (cesx_mh_hmc_lineal_accept); logu as in ``mh_accept``."""
+        self._lvlin_check("mh_hmc_lineal_accept", (("U", U, self.p, self.torch_dtype), ("Q", Q, self.p, self.torch_dtype),
+                                                   ("GQ", GQ, self.n_obs, self.torch_dtype)))
+        if logu is not None and (logu.dtype != torch.float64 or logu.numel() != self.J or not logu.is_contiguous() or not logu.is_cuda):
+            raise ValueError("mh_hmc_lineal_accept: logu must be a contiguous float64 device tensor of J values")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_mh_hmc_lineal_accept(self._h, int(step_index), U.data_ptr(), Q.data_ptr(), GQ.data_ptr(),
+                                                           None if logu is None else logu.data_ptr(), self._stream()))
+        self._keep_hl_a = (U, Q, GQ, logu)
 
     # -- streaming summaries of the chains' draws (include/cesx.h, cesx_chain_summary_*) --
     def chain_summary_begin(self, n_draws):

@@ -112,9 +112,14 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          the most); ``fused=None`` is ``LANGEVIN_FUSED_DEFAULT``; the emulator refuses ``fused=True``.
                          ``summary=``, ``burn=``, ``marginals=``, ``start=``, ``noise=``, sharded noise, resume (the resumed
                          states are scored through the Langevin start) and ``trace_stride`` work as for ``update='langevin'``.
-                         It refuses what ``update='langevin'`` refuses, and the linear maps with or without
-                         ``enable_gradient()`` (no GEMM-form leapfrog yet: a follow-up); ``leapfrog=`` with any other
-                         ``update`` raises ``ValueError`` too.  No trajectory-length adaptation; the step: ``adapt=``.
+                         The linear maps take it after ``model.enable_gradient(leapfrog=True)`` (opt-in) at any p: with
+                         ``chains=M`` every position is update launches -- the gradient and the drift Q + S r of
+                         ``cesx_mh_langevin_lineal_*`` around a momentum block of the engine dtype, ``cesx_mh_hmc_lineal_begin``
+                         / ``_leap`` / ``_accept`` (kernels_hmclin.hip), the forward map once per position and phi at the last
+                         one only --; L = 1 is ``update='langevin'`` bit for bit; no fused kernel (``fused=True`` raises).
+                         It refuses what ``update='langevin'`` refuses, and the linear maps without that mark, with or without
+                         ``enable_gradient()``; ``leapfrog=`` with any other ``update`` raises ``ValueError`` too.  No
+                         trajectory-length adaptation; the step: ``adapt=``.
   kwarg ``adapt``        model_mh and gp_mh under ``update='langevin'`` and ``'hmc'``, on the host (one chain) and with ``chains=M``:
                          pooled step-size adaptation.  ``None`` / ``False``: off; ``True``: 100 steps; an int A: A steps; or a dict
                          with ``steps`` (100, 1 .. 65 536), ``target`` (0.574 under 'langevin', 0.651 under 'hmc'), ``gain`` (2)
@@ -134,8 +139,9 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          ``multiplier_history`` (A,): the mean acceptance probability of every adaptation step and the e it ran
                          with; ``self.accept`` and ``self.accept_chains`` cover the steps at the frozen step.  A call without
                          ``adapt=`` removes ``self.adapt``.  ``ValueError`` before an engine is created: another ``update`` (the
-                         random walk's and pCN's proposals are update launches), a linear map (its Langevin step is the GEMM
-                         form of kernels_lvlin.hip: a follow-up), ``A >= n_mcmc``, with ``chains=`` ``A % trace_stride != 0``
+                         random walk's and pCN's proposals are update launches), a linear map without the mark of
+                         ``enable_gradient(leapfrog=True)`` (with it the phase runs on the ADAPT kernels of kernels_hmclin.hip,
+                         armed behind the install and the start), ``A >= n_mcmc``, with ``chains=`` ``A % trace_stride != 0``
                          and ``summary=True`` with ``burn < A``.  Sharded chains are not pooled (``CESX_EUNSUPPORTED``).
   kwarg ``start``        'mean' (default, the reference's start ``enka.Ustar.mean(axis=1)``) or 'ensemble' (chain j starts at
                          ``enka.Ustar[:, j]``, M <= J)
@@ -526,10 +532,12 @@ class MCMC(object):
             self.__dict__.pop("adapt", None)
             return None
         A = spec["steps"]
-        if model is not None and (getattr(model, "model_name", None) in ("lineal", "lineal_log") or hasattr(model, "langevin_device")):
+        if (model is not None and not getattr(model, "leapfrog_device", False)
+                and (getattr(model, "model_name", None) in ("lineal", "lineal_log") or hasattr(model, "langevin_device"))):
             raise ValueError("adapt=: %r is a linear map, whose Langevin step is the GEMM form of kernels_lvlin.hip (the "
-                             "gradient on the update kernels); the multiplier lives in the leapfrog kernels: a follow-up -- "
-                             "tune delta by hand, or adapt on elliptic / banana or on the emulator (gp_mh)" % (model,))
+                             "gradient on the update kernels); the multiplier lives in the leapfrog kernels: the follow-up of "
+                             "kernels_hmclin.hip, which enable_gradient(leapfrog=True) opts into -- call that, tune delta by "
+                             "hand, or adapt on elliptic / banana or on the emulator (gp_mh)" % (model,))
         if A >= int(n_mcmc):
             raise ValueError("adapt=: the first %d of the call's n_mcmc steps adapt, and n_mcmc = %d leaves none at the step "
                              "found" % (A, int(n_mcmc)))
@@ -814,12 +822,15 @@ class MCMC(object):
 
     @staticmethod
     def _model_hmc_refusals(model, prior, device):
-        """What ``model_mh(update='hmc')`` cannot do: the linear maps (their gradient is a GEMM on the update kernels, and a
-        GEMM-form leapfrog is a follow-up), then everything ``update='langevin'`` refuses."""
-        if getattr(model, "model_name", None) in ("lineal", "lineal_log") or hasattr(model, "langevin_device"):
+        """What ``model_mh(update='hmc')`` cannot do: the linear maps without the mark of ``enable_gradient(leapfrog=True)``
+        (their gradient is a GEMM on the update kernels; the GEMM-form leapfrog of kernels_hmclin.hip is opt-in), then everything
+        ``update='langevin'`` refuses."""
+        if (not getattr(model, "leapfrog_device", False)
+                and (getattr(model, "model_name", None) in ("lineal", "lineal_log") or hasattr(model, "langevin_device"))):
             raise ValueError("update='hmc': %r is a linear map, with or without enable_gradient(); its gradient is an A^T "
-                             "product on the update kernels and there is no GEMM-form leapfrog yet (a follow-up) -- run "
-                             "update='langevin' after enable_gradient(), or update='hmc' on elliptic / banana" % (model,))
+                             "product on the update kernels and the GEMM-form leapfrog (the follow-up of the Langevin step, "
+                             "kernels_hmclin.hip) is opt-in -- call enable_gradient(leapfrog=True), run update='langevin' after "
+                             "enable_gradient(), or update='hmc' on elliptic / banana" % (model,))
         MCMC._as_hmc(MCMC._model_langevin_refusals, model, prior, device)
 
     def _model_mh_langevin_host(self, model, n_mcmc, prior, enka, Gamma, delta, enka_scaling, leapfrog=None, adapt=None):
@@ -892,7 +903,8 @@ class MCMC(object):
         return self._mh_eng
 
     def _mh_device(self, enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind, resume_keeps_start_phi, fused=False,
-                   fused_work=0, langevin=False, fused_steps_max=None, adapt=None, bind_adapt=None, delta=1.):
+                   fused_work=0, langevin=False, fused_steps_max=None, adapt=None, bind_adapt=None, delta=1.,
+                   arm_after_start=False):
         """M = kwargs['chains'] chains on the engine: what ``model_mh(chains=)`` and ``gp_mh(chains=)`` have in common.
 
         Gamma                    the data covariance handed to ``set_problem``
@@ -920,6 +932,9 @@ class MCMC(object):
                                  then ``eng.mh_adapt_read`` (the one synchronisation), the scales re-formed by
                                  ``scales_of(update, delta * multiplier)``, ``mh_set_proposal``, ``bind`` and ``score_start``
                                  again, and the remaining steps as without it.  ``self.adapt`` holds what was found
+        arm_after_start          when the engine is armed: False -- before ``bind_adapt`` and the start, as the models with a
+                                 Jacobian image and the emulator take it --; True -- behind them: the linear maps' install
+                                 (cesx_mh_langevin_lineal_set) and start (cesx_mh_langevin_lineal_start) refuse an armed handle
         ``self.fused_launches`` is the number of fused launches of the call, 0 on the step path.
         ``kwargs['summary'] = True`` (with ``kwargs['burn']`` steps left out) keeps the kept states on the device and sums
         them there (``eng.chain_summary_*``): ``self.summary`` (``finalise_summary``) instead of a trace in ``self.samples``,
@@ -981,7 +996,7 @@ class MCMC(object):
         eng = self._mh_engine(p, n, M)
         eng.set_problem(np.asarray(self.y_obs, dtype=np.float64).reshape(n), Gamma, mu, cov, mu)
         eng.mh_set_proposal(update, scales, kwargs.get("beta", 0.5))
-        if adapt:                                         # armed: the leapfrog launches run at e S until the next mh_set_proposal
+        if adapt and not arm_after_start:                 # armed: the leapfrog launches run at e S until the next mh_set_proposal
             eng.mh_adapt_set(adapt["steps"], adapt["target"], adapt["gain"], adapt["kappa"])
         score_start, score_accept, run_steps, propose = (tuple((bind_adapt if adapt else bind)(eng, M)) + (None,))[:4]
         P = eng.empty(p)
@@ -1001,6 +1016,8 @@ class MCMC(object):
             if not resume_keeps_start_phi or self.noise == "device":
                 score_start(U)
             base, kept = int(getattr(self, "_mh_next_step", 0)), []
+        if adapt and arm_after_start:                     # (the install and every start above ran unarmed)
+            eng.mh_adapt_set(adapt["steps"], adapt["target"], adapt["gain"], adapt["kappa"])
         if summary:                                       # the draws stay on the device: cesx_chain_summary_*
             eng.chain_summary_begin(n_draws)
         if marg:                                          # and are counted there: cesx_chain_hist_*, the same slices
@@ -1260,8 +1277,41 @@ class MCMC(object):
                 eng.mh_langevin_lineal_accept(step, U, P, GP, logu=logu)
             return lv_start, lv_accept, None, lv_propose
 
-        if langevin and not hasattr(model, "jacobian_device"):
+        def bind_hmc_lineal(eng, M, leapfrog=leapfrog):
+            # bind_langevin_lineal with the leapfrog loop on the host (cesx_mh_hmc_lineal_*): per position the forward map at Q,
+            # then the gradient, the kick and the drift into the OTHER of two position buffers (the drift launch reads Q while it
+            # writes the next one).  No fused run: the step is GEMMs
+            takes_out = hook_takes_out(model.forward_device)
+            G, GQ, Q2 = eng.empty(n), eng.empty(n), eng.empty(p)
+            model.langevin_device(eng)
+
+            def fwd(u, out):
+                if takes_out:
+                    return model.forward_device(eng, u, out=out)
+                out.copy_(model.forward_device(eng, u))
+                return out
+
+            def hm_start(U):                              # the Langevin start: phi and g of the states
+                fwd(U, G)
+                eng.mh_langevin_lineal_start(U, G)
+
+            def hm_begin(step, U, xi, Q):
+                eng.mh_hmc_lineal_begin(step, U, xi=xi, out=Q)
+
+            def hm_accept(step, U, Q, logu):
+                nxt = Q2
+                for _ in range(leapfrog - 1):
+                    fwd(Q, GQ)
+                    eng.mh_hmc_lineal_leap(Q, GQ, nxt)
+                    Q, nxt = nxt, Q
+                fwd(Q, GQ)
+                eng.mh_hmc_lineal_accept(step, U, Q, GQ, logu=logu)
+            return hm_start, hm_accept, None, hm_begin
+
+        lineal_grad = langevin and not hasattr(model, "jacobian_device")      # (a linear map: model_mh has checked langevin_device)
+        if lineal_grad:
             bind_langevin = bind_langevin_lineal
+            bind_hmc = bind_hmc_lineal
         if leapfrog is not None:
             bind_langevin = bind_hmc
         adapt = self._adapt_of(kwargs, n_mcmc, model)     # (model_mh has refused what it does not go with)
@@ -1269,7 +1319,9 @@ class MCMC(object):
         self._mh_device(enka, n_mcmc, prior, kwargs, Gamma, scales_of, bind_langevin if langevin else bind_pde if pde else bind,
                         resume_keeps_start_phi=not langevin, fused=fused, langevin=langevin,
                         fused_steps_max=None if leapfrog is None else self.HMC_GRADS_MAX // leapfrog, adapt=adapt, delta=delta,
-                        bind_adapt=lambda eng, M: bind_hmc(eng, M, leapfrog or 1, False))      # (the step path; 'langevin' is L = 1)
+                        bind_adapt=(lambda eng, M: bind_hmc_lineal(eng, M, leapfrog or 1)) if lineal_grad else
+                        (lambda eng, M: bind_hmc(eng, M, leapfrog or 1, False)),               # (the step path; 'langevin' is L = 1)
+                        arm_after_start=lineal_grad)
 
     def _gp_mh_device(self, enka, n_mcmc, prior, delta, enka_scaling, kwargs):
         import torch

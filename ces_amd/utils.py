@@ -87,7 +87,7 @@ class lineal(object):
 
     _exp_params = False        # lineal_log: the map acts on exp(theta)
 
-    def enable_gradient(self):
+    def enable_gradient(self, leapfrog=False):
         """Offer the gradient of the map to ``MCMC.model_mh(update='langevin')`` (build-only, opt-in: without this call the
         instance has neither attribute and the sampler refuses it as before).  The instance gains
 
@@ -95,7 +95,15 @@ class lineal(object):
         ``langevin_device(engine)``  with ``chains=M``: installs the map and hands A and b to the engine's adjoint images
                                      (cesx_mh_langevin_lineal_set), after which the Langevin step never forms a Jacobian: its
                                      gradient is an A^T product on the update kernels.
-        Returns ``self``."""
+        ``leapfrog=True`` additionally marks the instance (``leapfrog_device = True``) for ``update='hmc'`` and ``adapt=``: the
+        GEMM-form leapfrog of cesx_mh_hmc_lineal_* (kernels_hmclin.hip) on the same images.  Without it the mark is removed and
+        the two are refused, as they were.  Returns ``self``."""
+        if leapfrog not in (False, True):
+            raise ValueError("enable_gradient: leapfrog must be False or True, got %r" % (leapfrog,))
+        self.__dict__.pop("leapfrog_device", None)
+        if leapfrog:
+            self.leapfrog_device = True
+
         def jacobian(theta):
             A = np.asarray(self.A, dtype=np.float64)
             if not self._exp_params:

@@ -681,7 +681,7 @@ int cesx_mh_langevin_lineal_g(cesx_handle h, double* g_host);
    bounded: n_steps * leapfrog <= CESX_HMC_LAUNCH_GRADS_MAX gradient evaluations.  cesx_mh_stats counts one step per accept
    and n_steps per fused launch.
    CESX_ESTATE without cesx_set_problem, a proposal of kind CESX_MH_LANGEVIN or a cesx_mh_langevin_start /
-   cesx_gp_langevin_start as the LAST start (not cesx_mh_langevin_lineal_start: the linear maps have no leapfrog yet); leap and
+   cesx_gp_langevin_start as the LAST start (not cesx_mh_langevin_lineal_start: the linear maps have cesx_mh_hmc_lineal_* below); leap and
    accept also without a cesx_mh_hmc_begin since the start or the last accept; the cesx_gp_hmc_* calls without cesx_gp_set;
    run_map without an installed map of a fused kind.  CESX_EINVAL for a null pointer (xi_dev, logu_dev and trace_dev may be
    NULL), Q_dev aliasing U_dev, leapfrog outside 1 .. CESX_HMC_LEAPFROG_MAX, n_steps < 1, stride < 1,
@@ -699,6 +699,34 @@ int cesx_gp_hmc_accept(cesx_handle h, int mode, uint64_t step_index, void* U_dev
                        const double* var_dev, const double* dmean_dev, const double* dvar_dev, const double* logu_dev, void* stream);
 int cesx_mh_hmc_run_map(cesx_handle h, uint64_t step_index, int n_steps, int leapfrog, int stride, void* U_dev, void* trace_dev,
                         const void* xi_dev, const double* logu_dev, void* stream);
+/* The same leapfrog step for the LINEAR maps at any p (cesx_mh_langevin_lineal_*'s models, images and start; kernels_hmclin.hip):
+   every position is update launches -- the gradient g = S^T grad phi as cesx_mh_langevin_lineal_accept forms it, the drift
+   Q + S z as cesx_mh_langevin_lineal_propose's triangular launch -- with the momentum r a [p][J_local] block of the ENGINE
+   dtype between them (no fp64 momentum image: at p = 256 and 65 536 chains that would be 134 MB more).  One step of a chain
+   at U, e = 1 unless the handle is armed (cesx_mh_adapt_set after cesx_mh_langevin_lineal_start):
+       xi ~ N(0, I_p);   r = xi - (e / 2) g(U);   Q = U
+       L times:   Q = Q + e S r;   G(Q) (the caller's forward map), g(Q);   r = r - e g(Q), the last time r - (e / 2) g(Q)
+       log u < phi(U) - phi(Q) + (|xi|^2 / 2 - |r|^2 / 2);   accepted columns: U := Q, phi := phi(Q), g := g(Q), counter + 1
+   One step index whatever L is; the block and log u are cesx_mh_langevin_lineal_propose / _accept's for that index.
+       cesx_mh_hmc_lineal_begin    r and the first position Q_dev = U + e S r; the block (xi_dev or NULL: the device draw) is kept
+       cesx_mh_hmc_lineal_leap     from G_dev = the map at Q_dev: g(Q), the full kick, Qnext_dev = Q + e S r.  phi(Q) is NOT
+                                   formed (only the last position's is needed).  Qnext_dev must not alias Q_dev: the drift
+                                   launch reads Q while it writes Qnext (ping-pong between two buffers).  Called L - 1 times.
+       cesx_mh_hmc_lineal_accept   from G_dev at the last Q_dev: phi(Q), g(Q), the half kick inside the second norm, the test,
+                                   the masked copies.  phi is cesx_mh_start's bit for bit.  Unarmed and with no leap since the
+                                   begin (L = 1) the launch is cesx_mh_langevin_lineal_accept's own, so L = 1 IS the Langevin
+                                   step bit for bit and the two families alternate on one handle.
+   A NaN or an infinity anywhere in a trajectory (G, g, r, Q) makes the comparison false: that chain alone stays.
+   Armed: the three calls launch the ADAPT instantiations (e from device memory; z = e r is a second block, nothing stored is
+   rescaled), accept leaves alpha_j and is followed by the recursion; after n_steps accepts they return CESX_ESTATE.
+   CESX_ESTATE without a lineal image or unless the LAST start was cesx_mh_langevin_lineal_start; leap and accept also without a
+   cesx_mh_hmc_lineal_begin since the start or the last accept (a cesx_mh_langevin_lineal_propose ends a trajectory in flight).
+   CESX_EINVAL for a null pointer (xi_dev, logu_dev may be NULL), Q_dev aliasing U_dev, Qnext_dev aliasing Q_dev, a step index
+   >= 2^31.  None of these launches anything or touches U_dev, the chains' phi, g or the counters. */
+int cesx_mh_hmc_lineal_begin(cesx_handle h, uint64_t step_index, const void* U_dev, const void* xi_dev, void* Q_dev, void* stream);
+int cesx_mh_hmc_lineal_leap(cesx_handle h, const void* Q_dev, const void* G_dev, void* Qnext_dev, void* stream);
+int cesx_mh_hmc_lineal_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* Q_dev, const void* G_dev,
+                              const double* logu_dev, void* stream);
 /* MCMC.model_mh / gp_mh(chains=M, adapt=): pooled step-size adaptation of the leapfrog step above (kernels_adapt.hip and the
    ADAPT instantiations of kernels_hmc.hip).  One scalar multiplier e, shared by all chains, e_1 = 1.  Adaptation step
    t = 1 .. n_steps is the HMC step with e S in place of S, written without rescaling anything stored (g = S^T grad phi as the
@@ -721,7 +749,7 @@ int cesx_mh_hmc_run_map(cesx_handle h, uint64_t step_index, int n_steps, int lea
                             cesx_gp_hmc_leap / _accept launch the ADAPT kernels, every accept is followed by the recursion, and
                             after n_steps accepts they return CESX_ESTATE (read, then set the proposal).  While armed,
                             cesx_mh_hmc_run_map, every cesx_*_langevin_propose / _accept / _run_map and the
-                            cesx_mh_langevin_lineal_* family return CESX_ESTATE and launch nothing.  The starts
+                            cesx_mh_langevin_lineal_* family return CESX_ESTATE and launch nothing (cesx_mh_hmc_lineal_* is their armed form).  The starts
                             (cesx_mh_langevin_start, cesx_gp_langevin_start) stay available.  cesx_mh_set_proposal and
                             cesx_set_problem disarm the handle and drop the state.
        cesx_mh_adapt_read   synchronises; multiplier = ebar_t of the steps made (1 before the first), steps_done, and into
