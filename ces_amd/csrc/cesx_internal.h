@@ -487,6 +487,7 @@ struct Engine {
     MapState mp;                       // closed-form maps and their fused chain kernel (cesx_map_*, cesx_mh_run_map, kernels_maps.hip)
     ChainSumState cs;                  // streaming summaries of the chains' draws (cesx_chain_summary_*, kernels_chainsum.hip)
     ChainHistState ch;                 // streaming marginals of the chains' draws (cesx_chain_hist_*, kernels_chainhist.hip)
+    ChainAcfState ca;                  // streaming lagged sums of the chains' draws (cesx_chain_acf_*, kernels_chainacf.hip)
     // per-kernel profiling (cesx_profile_*)
     int prof_part = 0;                 // which moments launch (0: U x U, 1: the rest) the next profiled Gram launch is
     unsigned long long prof_step = 0;  // bumped by every first-half entry point (cesx_moments_uu*): the step the next profiled launches belong to
@@ -859,6 +860,11 @@ int chainhist_begin(Engine& e, const cesx_chain_hist_desc* d, hipStream_t s);
 int chainhist_add(Engine& e, const void* trace, int kept, hipStream_t s);
 int chainhist_read(Engine& e, unsigned long long* hist1, unsigned long long* out1, unsigned long long* hist2,
                    unsigned long long* out2, hipStream_t s);
+
+// kernels_chainacf.hip: the stage behind cesx_chain_acf_* (include/cesx.h); the entry points have checked the arguments and the state
+int chainacf_begin(Engine& e, long long n_draws, int lags, int n_chains);
+int chainacf_add(Engine& e, const void* trace, int kept, hipStream_t s);
+int chainacf_read(Engine& e, double* gsum, double* msum, double* m2sum, double* chain_gamma, double* chain_mean, hipStream_t s);
 
 // kernels_gpfit.hip: lml, gradient and status of the GPs gf.idx[0 .. n_active) at gf.theta into gf.out
 int launch_gpfit_eval(Engine& e, int n_active, hipStream_t s);

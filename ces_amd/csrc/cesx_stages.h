@@ -1,4 +1,4 @@
-// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gpp, gf, dc, l9, l6, mp, cs, ch).  Each owns its
+// The state of the stages behind Calibrate, one struct per stage (Engine members mh, gp, gpd, gpp, gf, dc, l9, l6, mp, cs, ch, ca).  Each owns its
 // device memory (DevBuf: freed with the struct), says what "nothing installed" is, and has one drop() that establishes it.
 // drop() releases the buffers whose size comes from the installed descriptor and keeps the ones sized by the engine's
 // shape alone (allocated on first use, reused by every later install).  No hip/ header: tools/devbuf_check.cpp runs these
@@ -183,6 +183,23 @@ struct ChainHistState {
     DevBuf<unsigned long long> tot2;           // [n_pairs][bins2][bins2], then [n_pairs] outside
     bool none() const { return bins == 0; }
     void drop() { bins = 0; bins2 = 0; n_pairs = 0; added = 0; }      // every buffer is sized by the engine: kept
+};
+
+// ---- streaming lagged sums of the chains' draws (cesx_chain_acf_*, kernels_chainacf.hip); state of its own: cesx_set_problem does not touch it ----
+struct ChainAcfState {
+    long long N = 0, added = 0, done = 0;      // draws of the run in hand (0: no cesx_chain_acf_begin), draws added, draws in the sums
+    int L = 0, LT = 0, C = 0;                  // lags, the ring's slots (kernels_chainacf.hip, acf_lt), chains followed
+    int pend = 0;                              // draws waiting in `pending`: added - done
+    // every buffer is [..][p][C]: sized by the run, grown by a begin that needs more and kept otherwise
+    DevBuf<double> c, S1;                      // every chain's first draw (the shift) and sum a
+    DevBuf<double> P;                          // [LT + 1] the lagged sums P_k
+    DevBuf<double> ring;                       // [LT] a_t in slot t mod LT: the last LT values
+    DevBuf<double> head;                       // [L] a_0 .. a_{L-1}
+    DevBuf<void> pending;                      // [ACF_BLOCK] draws of the C chains in the engine dtype
+    DevBuf<double> out;                        // [L + 1][p] sum G_k, then [p] each: cbar, sum (m - cbar), sum (m - cbar)^2
+    DevBuf<double> gamma, mean;                // [L + 1][p][C], [p][C]: only while a cesx_chain_acf_read runs
+    bool none() const { return N == 0; }
+    void drop() { N = 0; added = 0; done = 0; L = 0; LT = 0; C = 0; pend = 0; gamma.reset(); mean.reset(); }
 };
 
 }  // namespace cesx

@@ -2488,4 +2488,40 @@ int cesx_chain_hist_read(cesx_handle h, unsigned long long* hist1, unsigned long
     return chainhist_read(e, hist1, out1, hist2, out2, (hipStream_t)stream);
 }
 
+// ---- Streaming lagged sums of the chains' draws (MCMC(..., chains=M, summary=True, autocorr=...); kernels_chainacf.hip) ----
+
+// Failure rule: a refused call launches nothing and touches nothing; the run in hand goes on.
+int cesx_chain_acf_begin(cesx_handle h, int n_draws, int lags, int n_chains, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    (void)stream;                                         // nothing is launched: the first lag launch overwrites the stage's sums
+    if (e.J != e.Jg) { e.err = "cesx_chain_acf_begin: sharded chains (J_local != J_global) are not followed"; return CESX_EINVAL; }
+    if (lags < 1 || lags > CESX_CHAIN_ACF_LAGS_MAX) { e.err = "cesx_chain_acf_begin: lags must be in [1, " + std::to_string(CESX_CHAIN_ACF_LAGS_MAX) + "]"; return CESX_EINVAL; }
+    if (n_chains < 1 || n_chains > e.J) { e.err = "cesx_chain_acf_begin: n_chains must be in [1, J_local]"; return CESX_EINVAL; }
+    if (n_draws < 4 || n_draws < lags + 2) { e.err = "cesx_chain_acf_begin: n_draws must be >= max(4, lags + 2)"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    return chainacf_begin(e, n_draws, lags, n_chains);
+}
+
+int cesx_chain_acf_add(cesx_handle h, const void* trace, int kept, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!trace) { e.err = "cesx_chain_acf_add: null pointer"; return CESX_EINVAL; }
+    if (kept < 1) { e.err = "cesx_chain_acf_add: kept must be >= 1"; return CESX_EINVAL; }
+    if (e.ca.none()) { e.err = "cesx_chain_acf_add: cesx_chain_acf_begin has not been called"; return CESX_ESTATE; }
+    if (e.ca.added + kept > e.ca.N) { e.err = "cesx_chain_acf_add: more draws than cesx_chain_acf_begin announced"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    return chainacf_add(e, trace, kept, (hipStream_t)stream);
+}
+
+int cesx_chain_acf_read(cesx_handle h, double* gsum, double* msum, double* m2sum, double* chain_gamma, double* chain_mean, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (!gsum || !msum || !m2sum) { e.err = "cesx_chain_acf_read: null pointer"; return CESX_EINVAL; }
+    if (e.ca.none()) { e.err = "cesx_chain_acf_read: cesx_chain_acf_begin has not been called"; return CESX_ESTATE; }
+    if (e.ca.added != e.ca.N) { e.err = "cesx_chain_acf_read: fewer draws were added than cesx_chain_acf_begin announced"; return CESX_ESTATE; }
+    SET_DEVICE(e);
+    return chainacf_read(e, gsum, msum, m2sum, chain_gamma, chain_mean, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -43,7 +43,8 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_mh_hmc_begin", "cesx_mh_hmc_leap", "cesx_mh_hmc_accept", "cesx_gp_hmc_leap", "cesx_gp_hmc_accept", "cesx_mh_hmc_run_map",
            "cesx_mh_adapt_set", "cesx_mh_adapt_read",
            "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read",
-           "cesx_chain_hist_begin", "cesx_chain_hist_add", "cesx_chain_hist_read")
+           "cesx_chain_hist_begin", "cesx_chain_hist_add", "cesx_chain_hist_read",
+           "cesx_chain_acf_begin", "cesx_chain_acf_add", "cesx_chain_acf_read")
 L96_STATUS = {1: "the step size fell below the spacing between numbers (scipy's step-size failure)",
               2: "a state or an error norm was not finite",
               3: "max_attempts steps were attempted"}
@@ -331,6 +332,9 @@ def load_library(path=None):
     lib.cesx_chain_hist_begin.argtypes = [vp, vp, vp]
     lib.cesx_chain_hist_add.argtypes = [vp, vp, i32, vp]
     lib.cesx_chain_hist_read.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.cesx_chain_acf_begin.argtypes = [vp, i32, i32, i32, vp]
+    lib.cesx_chain_acf_add.argtypes = [vp, vp, i32, vp]
+    lib.cesx_chain_acf_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     if lib.cesx_abi_version() != ABI_VERSION:
         raise ImportError("libcesx.so ABI %d != binding ABI %d" % (lib.cesx_abi_version(), ABI_VERSION))
     if path == LIB_PATH:
@@ -393,6 +397,8 @@ class Engine:
         self._problem = None
         self._chain_hist_shape = None      # (bins, bins2d, pairs) of the run of histograms in hand
         self._keep_chain_hist = None
+        self._chain_acf_shape = None       # (lags, chains) of the run of lagged sums in hand
+        self._keep_chain_acf = None
 
     def close(self):
         """Destroy the handle and free its device memory now (what garbage collection would do later)."""
@@ -1705,6 +1711,44 @@ class Engine:
         self._keep_chain_hist = None
         return dict(hist1d=h1.astype(np.int64), below=o1[:, 0].astype(np.int64), above=o1[:, 1].astype(np.int64),
                     hist2d=h2.astype(np.int64), outside2d=o2.astype(np.int64))
+
+    # -- streaming lagged sums of the chains' draws (include/cesx.h, cesx_chain_acf_*) --
+    def chain_acf_begin(self, n_draws, lags, chains):
+        """Clear the stage for a run of ``n_draws`` draws per chain, lags 0 .. ``lags`` and the first ``chains`` chains
+        (cesx_chain_acf_begin).  ValueError for a limit of include/cesx.h; the run in hand then goes on."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_chain_acf_begin(self._h, int(n_draws), int(lags), int(chains), self._stream()))
+        self._chain_acf_shape = (int(lags), int(chains))
+
+    def chain_acf_add(self, trace):
+        """Add the draws of ``trace``, (kept, p, J) or one state (p, J), engine dtype, in order (cesx_chain_acf_add): the
+        argument of ``chain_summary_add``.  Fewer than 64 draws are copied into the stage's own memory; more are read in place."""
+        shape = tuple(trace.shape)
+        if (trace.dtype != self.torch_dtype or not trace.is_cuda or not trace.is_contiguous()
+                or shape[-2:] != (self.p, self.J) or len(shape) not in (2, 3)):
+            raise ValueError("chain_acf_add: trace must be a contiguous %s tensor of shape (kept, %d, %d) or (%d, %d)"
+                             % (self.torch_dtype, self.p, self.J, self.p, self.J))
+        kept = shape[0] if len(shape) == 3 else 1
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_chain_acf_add(self._h, trace.data_ptr(), kept, self._stream()))
+        self._keep_chain_acf = trace
+
+    def chain_acf_read(self, chains=False):
+        """The run's raw sums as host fp64 arrays (cesx_chain_acf_read): ``gsum`` (p, lags + 1), ``msum`` (p,), ``m2sum`` (p,);
+        with ``chains`` also every chain's ``chain_gamma`` (lags + 1, p, C) and ``chain_mean`` (p, C).  Synchronises."""
+        if self._chain_acf_shape is None:
+            raise CesxError(ESTATE, "chain_acf_read: chain_acf_begin has not been called")
+        L, Cn = self._chain_acf_shape
+        p = self.p
+        out = dict(gsum=np.empty((p, L + 1)), msum=np.empty(p), m2sum=np.empty(p))
+        if chains:
+            out.update(chain_gamma=np.empty((L + 1, p, Cn)), chain_mean=np.empty((p, Cn)))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.cesx_chain_acf_read(self._h, out["gsum"].ctypes.data, out["msum"].ctypes.data, out["m2sum"].ctypes.data,
+                                                     out["chain_gamma"].ctypes.data if chains else None,
+                                                     out["chain_mean"].ctypes.data if chains else None, self._stream()))
+        self._keep_chain_acf = None
+        return out
 
     def profile_enable(self, on=True):
         """on: False / True, 2 = bind only the events cesx_profile_gap needs, 3 / 4 = the update / the moments

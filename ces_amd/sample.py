@@ -52,7 +52,7 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          ``within`` = W and ``between`` = B_m (p,), the mean variance and the variance of the means
                          (ddof = 1) of the 2 M half-chains (each chain's first and last n // 2 draws); ``rhat`` =
                          sqrt(((n_h - 1) / n_h W + B_m) / W) and ``ess`` = min(2 M n_h, 2 M var+ / B_m) with n_h = n // 2
-                         (no rank normalisation, no autocorrelations).  The chains run exactly as without it;
+                         (no rank normalisation, no autocorrelations: ``autocorr=`` has those).  The chains run exactly as without it;
                          ``self.samples`` gains only the start state (a fresh run) and the call's last state, so a resume
                          works, and a resumed call summarises its own steps.
   kwarg ``marginals``    with ``chains=`` and ``summary=True`` (``ValueError`` without): histograms of every parameter and of
@@ -70,6 +70,19 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          ``marginal_density`` and ``marginal_quantiles`` read it; ``plots.find_levels(H=hist2d[k])`` gives
                          the contour levels.  The chains, ``self.summary`` and ``self.samples`` are as without it.  A call
                          without ``marginals=`` removes ``self.marginals``: the attribute is always the last call's.
+  kwarg ``autocorr``     with ``chains=`` and ``summary=True`` (``ValueError`` without): an effective sample size from the chains'
+                         autocorrelations, over exactly the draws the summary sums, from lagged sums kept on the device
+                         (``cesx_chain_acf_*``, kernels_chainacf.hip).  ``None`` / ``False``: off; ``True``: the defaults; an int:
+                         ``lags``; or a dict with ``lags`` (31, 1 .. 64) and ``chains`` (``min(M, 1024)``: the first C chains are
+                         followed); an unknown key, ``chains > M`` and fewer draws than ``lags + 2`` raise ``ValueError``.
+                         ``self.autocorr`` (``finalise_autocorr``) is a dict of host fp64 values: ``n``, ``chains`` (C), ``lags``,
+                         ``rho`` (p, lags + 1) the multi-chain autocorrelations 1 - (W - mean_j gamma_k) / var+, ``tau`` =
+                         -1 + 2 sum of Geyer's initial monotone sequence of pairs rho_2t + rho_2t+1, ``ess`` = M n / tau (for
+                         all M chains, from the C followed), ``truncated`` (p,) bool: no negative pair within the lags, so
+                         ``ess`` is an over-estimate -- raise ``lags`` or ``trace_stride`` --, ``within`` = W and ``var_plus``.
+                         A row in which no chain moved has ``ess = tau = nan``.  The chains, ``self.summary``,
+                         ``self.marginals`` and ``self.samples`` are as without it; a call without ``autocorr=`` removes
+                         ``self.autocorr``.  A host trace goes through ``autocorr_of_samples(samples, lags)``.
   kwarg ``update='langevin'``  gp_mh, on the host (one chain) and with ``chains=M``: a preconditioned Metropolis-adjusted
                          Langevin proposal from the closed-form gradients of the GPs (``emulate.GPR.predict_f_grad``; on the
                          device ``cesx_gp_predict_grad`` and ``cesx_gp_langevin_*``, kernels_gpgrad.hip).  With S the scales of
@@ -179,9 +192,9 @@ def fused_chunks(n_mcmc, stride, steps_max, buffer_bytes, bytes_per_step, work_m
 
 
 def _host_has_no_summary(kwargs):
-    """``summary=``, ``burn=`` and ``marginals=`` belong to the device paths of ``chains=M``."""
-    for name in ("summary", "burn", "marginals"):
-        if kwargs.get(name, None) is not None and not (name == "marginals" and kwargs[name] is False):
+    """``summary=``, ``burn=``, ``marginals=`` and ``autocorr=`` belong to the device paths of ``chains=M``."""
+    for name in ("summary", "burn", "marginals", "autocorr"):
+        if kwargs.get(name, None) is not None and not (name in ("marginals", "autocorr") and kwargs[name] is False):
             raise ValueError("%s=%r summarises the chains of chains=M on the device; the host path keeps every state in "
                              "self.samples" % (name, kwargs.get(name)))
 
@@ -216,6 +229,111 @@ def finalise_summary(raw, n_draws, chains):
         rhat = np.sqrt(var_plus / W)
         ess = np.minimum(2.0 * M * n, 2.0 * M * var_plus / B)
     return dict(n=N, chains=M, mean=c + d, cov=(cc - T * np.outer(d, d)) / (T - 1), rhat=rhat, ess=ess, within=W, between=B)
+
+
+AUTOCORR_KEYS = ("lags", "chains")
+AUTOCORR_LAGS_DEFAULT, AUTOCORR_LAGS_MAX, AUTOCORR_CHAINS_DEFAULT = 31, 64, 1024      # CESX_CHAIN_ACF_LAGS_MAX
+
+
+def autocorr_spec(autocorr, chains, summary, n_draws):
+    """What ``autocorr=`` asks for: ``None`` (off: ``None`` / ``False``) or ``(lags, C)``.  ``True``: the defaults; an int:
+    ``lags``; a dict: ``lags`` (31) and ``chains`` (``min(M, 1024)``).  ``ValueError`` for an unknown key, ``autocorr=`` without
+    ``summary=True``, ``lags`` outside [1, 64], ``chains`` outside [1, M] and fewer than ``lags + 2`` draws.  Pure: no engine."""
+    if autocorr is None or autocorr is False:
+        return None
+    if not summary:
+        raise ValueError("autocorr=%r follows the draws summary=True sums; without summary=True every kept state is in "
+                         "self.samples and autocorr_of_samples(self.samples, lags) reads them" % (autocorr,))
+    if autocorr is True:
+        autocorr = {}
+    elif isinstance(autocorr, (int, np.integer)):
+        autocorr = dict(lags=autocorr)
+    if not isinstance(autocorr, dict):
+        raise ValueError("autocorr must be None, False, True, an int (lags) or a dict with keys from %s, got %r" % (AUTOCORR_KEYS, autocorr))
+    unknown = [k for k in autocorr if k not in AUTOCORR_KEYS]
+    if unknown:
+        raise ValueError("autocorr: unknown key(s) %s (known: %s)" % (sorted(map(str, unknown)), ", ".join(AUTOCORR_KEYS)))
+    M = int(chains)
+    L = autocorr.get("lags", AUTOCORR_LAGS_DEFAULT)
+    C = autocorr.get("chains", min(M, AUTOCORR_CHAINS_DEFAULT))
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= L <= AUTOCORR_LAGS_MAX:
+        raise ValueError("autocorr: lags must be an integer in [1, %d], got %r" % (AUTOCORR_LAGS_MAX, L))
+    if isinstance(C, bool) or not isinstance(C, (int, np.integer)) or not 1 <= C <= M:
+        raise ValueError("autocorr: chains must be an integer in [1, %d] (the run's chains), got %r" % (M, C))
+    if n_draws < max(4, int(L) + 2):
+        raise ValueError("autocorr: %d draws per chain are fewer than lags + 2 = %d" % (n_draws, max(4, int(L) + 2)))
+    return int(L), int(C)
+
+
+def finalise_autocorr(raw, n, M_total, C, L):
+    """The ``MCMC.autocorr`` dict from the raw sums of ``Engine.chain_acf_read`` (host numpy on (p, L + 1) arrays).
+
+    ``raw``: ``gsum`` (p, L + 1) = sum over the C followed chains of G_k = sum_t (x_t - m)(x_{t+k} - m), m the chain's mean
+    of its ``n`` draws; ``msum`` (p,) = sum (m_j - c) and ``m2sum`` (p,) = sum (m_j - c)^2 about any shift c.  With
+    gamma_k = gsum_k / (C n): W = gsum_0 / (C (n - 1)), B / n = the ddof-1 variance of the chain means (0 for C = 1),
+    var+ = (n - 1) / n W + B / n, rho_0 = 1, rho_k = 1 - (W - gamma_k) / var+; Geyer's pairs Pi_t = rho_2t + rho_2t+1 for
+    t < (L + 1) // 2, cut at the first negative one and made monotone; tau = -1 + 2 sum Pi_t and ess = M_total n / tau: for
+    all ``M_total`` chains of the run, from the C followed.  ``truncated``: no negative pair within the lags (ess is then an
+    over-estimate).  A row with var+ = 0 -- no chain moved -- has ess = tau = nan."""
+    n, M_total, C, L = int(n), int(M_total), int(C), int(L)
+    g = np.asarray(raw["gsum"], dtype=np.float64).reshape(-1, L + 1)
+    ms = np.asarray(raw["msum"], dtype=np.float64).reshape(-1)
+    m2 = np.asarray(raw["m2sum"], dtype=np.float64).reshape(-1)
+    p = g.shape[0]
+    gam = g / (float(C) * n)
+    W = g[:, 0] / (float(C) * (n - 1))
+    Bn = np.maximum((m2 - ms * ms / C) / (C - 1), 0.0) if C > 1 else np.zeros(p)
+    var_plus = (n - 1) / n * W + Bn
+    rho = np.full((p, L + 1), np.nan)
+    tau, truncated = np.full(p, np.nan), np.zeros(p, dtype=bool)
+    for r in range(p):
+        if not (np.isfinite(var_plus[r]) and var_plus[r] > 0.0):
+            continue
+        rho[r] = 1.0 - (W[r] - gam[r]) / var_plus[r]
+        rho[r, 0] = 1.0
+        total, last, cut = 0.0, np.inf, False
+        for t in range((L + 1) // 2):
+            pair = rho[r, 2 * t] + rho[r, 2 * t + 1]
+            if pair < 0.0:
+                cut = True
+                break
+            last = min(last, pair)
+            total += last
+        tau[r], truncated[r] = -1.0 + 2.0 * total, not cut
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ess = M_total * n / tau
+    return dict(n=n, chains=C, lags=L, rho=rho, tau=tau, ess=ess, truncated=truncated, within=W, var_plus=var_plus)
+
+
+def autocorr_raw_of_samples(samples, lags):
+    """The raw sums ``finalise_autocorr`` reads -- ``gsum`` (p, L + 1), ``msum``, ``m2sum`` (p,) --, and every chain's
+    ``chain_gamma`` (L + 1, p, M) and ``chain_mean`` (p, M), from a host trace (p, n) or (p, n, M), centred sums in numpy."""
+    x = np.asarray(samples, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[:, :, None]
+    if x.ndim != 3:
+        raise ValueError("autocorr_of_samples: samples must have shape (p, n) or (p, n, M), got %s" % (x.shape,))
+    p, n, M = x.shape
+    L = lags
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or L < 1:
+        raise ValueError("autocorr_of_samples: lags must be an integer >= 1, got %r" % (lags,))
+    if n < max(4, L + 2):
+        raise ValueError("autocorr_of_samples: %d draws per chain are fewer than lags + 2 = %d" % (n, max(4, L + 2)))
+    m = x.mean(axis=1)                                         # (p, M)
+    z = x - m[:, None, :]
+    gamma = np.stack([(z[:, :n - k] * z[:, k:]).sum(axis=1) for k in range(L + 1)])      # (L + 1, p, M)
+    c = x[:, 0, :].mean(axis=1)
+    dm = m - c[:, None]
+    return dict(gsum=gamma.sum(axis=2).T.copy(), msum=dm.sum(axis=1), m2sum=(dm * dm).sum(axis=1), chain_gamma=gamma, chain_mean=m)
+
+
+def autocorr_of_samples(samples, lags=AUTOCORR_LAGS_DEFAULT):
+    """``MCMC.autocorr`` of a host trace ``samples`` (p, n) or (p, n, M): what ``autocorr=`` gives for the same draws, every
+    chain followed (drop the start state and the burn-in first: every column counts as a draw)."""
+    x = np.asarray(samples)
+    M = 1 if x.ndim == 2 else x.shape[-1]
+    raw = autocorr_raw_of_samples(x, lags)
+    return finalise_autocorr(raw, x.shape[1], M, M, int(lags))
 
 
 MARGINALS_KEYS = ("bins", "bins2d", "pairs", "range", "width")
@@ -941,6 +1059,8 @@ class MCMC(object):
         which gains the start state of a fresh run and the call's last state only.  The chains run as without it.
         ``kwargs['marginals']`` (``marginals_spec``; needs ``summary=True``) counts the same draws into histograms on the device
         (``eng.chain_hist_*``): ``self.marginals``.  The chains and ``self.summary`` are as without it.
+        ``kwargs['autocorr']`` (``autocorr_spec``; needs ``summary=True``) keeps the lagged sums of the same draws on the device
+        (``eng.chain_acf_*``): ``self.autocorr`` (``finalise_autocorr``).  Everything else is as without it.
         """
         import torch
         M = kwargs["chains"]
@@ -979,6 +1099,7 @@ class MCMC(object):
             raise ValueError("marginals=%r counts the draws summary=True sums; without summary=True every kept state is in "
                              "self.samples and numpy.histogram counts them" % (marg,))
         marg = marginals_spec(marg, enka.Ustar)
+        acf = autocorr_spec(kwargs.get("autocorr", None), M, summary, n_draws if summary else 0)
         p, n = enka.p, enka.n_obs
         scales = scales_of(update)
         start = kwargs.get("start", "mean")
@@ -1022,6 +1143,8 @@ class MCMC(object):
             eng.chain_summary_begin(n_draws)
         if marg:                                          # and are counted there: cesx_chain_hist_*, the same slices
             eng.chain_hist_begin(marg["edges"], marg["edges2d"], marg["pairs"])
+        if acf:                                           # and their lagged sums are kept there: cesx_chain_acf_*, the same slices
+            eng.chain_acf_begin(n_draws, acf[0], acf[1])
 
         def run_fused(k_first, n_steps):
             # launches of at most K_max steps (cesx_mh_run_map / cesx_gp_run; fused_chunks): K_max a multiple of the stride --
@@ -1051,6 +1174,8 @@ class MCMC(object):
                         eng.chain_summary_add(tr[t0:])
                         if marg:
                             eng.chain_hist_add(tr[t0:])
+                        if acf:
+                            eng.chain_acf_add(tr[t0:])
                 elif K // stride:
                     kept.extend(tr.cpu().numpy().astype(np.float64))
             if (summary or n_mcmc % stride) and n_mcmc > 0:   # the run's last state, where the trace does not hold it
@@ -1075,6 +1200,8 @@ class MCMC(object):
                         eng.chain_summary_add(U)
                         if marg:
                             eng.chain_hist_add(U)
+                        if acf:
+                            eng.chain_acf_add(U)
                     if k + 1 == n_mcmc:
                         kept.append(eng.to_host(U))
                 elif (k + 1) % stride == 0 or k + 1 == n_mcmc:
@@ -1102,6 +1229,9 @@ class MCMC(object):
             self.marginals = dict(n=n_draws, chains=M, edges=marg["edges"], hist1d=counts["hist1d"], below=counts["below"],
                                   above=counts["above"], pairs=marg["pairs"], edges2d=marg["edges2d"], hist2d=counts["hist2d"],
                                   outside2d=counts["outside2d"])
+        self.__dict__.pop("autocorr", None)              # nor an earlier call's autocorrelations
+        if acf:
+            self.autocorr = finalise_autocorr(eng.chain_acf_read(), n_draws, M, acf[1], acf[0])
         steps, rate, per = eng.mh_stats(per_chain=True)
 
         new = np.stack(kept, axis=1) if kept else np.zeros((p, 0, M))      # (p, n_new, M)

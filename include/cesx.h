@@ -835,6 +835,38 @@ int cesx_chain_hist_add(cesx_handle h, const void* trace_dev, int kept, void* st
 int cesx_chain_hist_read(cesx_handle h, unsigned long long* hist1, unsigned long long* out1, unsigned long long* hist2,
                          unsigned long long* out2, void* stream);
 
+/* ---- Streaming lagged sums of the chains' draws (MCMC(..., chains=M, summary=True, autocorr=...); kernels_chainacf.hip) --
+   What an autocorrelation ESS needs of every parameter (row) of the first C = n_chains chains, summed from the draws while
+   they are in device memory: the input of cesx_chain_summary_add, a third stage beside it.  All state is fp64 (an fp32 draw
+   converts exactly).  For row r, chain j < C and the run's draws x_0 .. x_{N-1}, with the chain's shift c = x_0 and
+   a_t = x_t - c, the stage keeps S1 = sum a_t, P_k = sum_{t=0}^{N-1-k} a_t a_{t+k} for k = 0 .. L, and the first and the
+   last L of the a_t.  Each P_k is ONE running sum in increasing t (one fma per draw), so the sums do not depend, bit for
+   bit, on how the N draws are cut into add calls.  Draws added fewer than 64 at a time wait in the stage's own memory
+   (engine dtype) until 64 are there; the sums then move once per block, not once per draw.  read forms, with d = S1 / N,
+   Hd_k = S1 - (the last k of a) and Tl_k = S1 - (the first k of a),
+       G_k = P_k - d (Hd_k + Tl_k) + (N - k) d^2     ( = sum_t (x_t - m)(x_{t+k} - m) with m = c + d, exactly ),
+   and sums over the C chains in a fixed order, without atomics.  The state belongs to the handle, is sized by the run
+   (p x C x (2 LT + L + 3) doubles with LT = 8, 32 or 64 the first of them >= L, plus 64 p C draws; at p = 256, C = 65 536,
+   L = 31: 13 GB and, fp32, 4 GB), grown by a begin that needs more and kept until cesx_destroy; cesx_set_problem does not
+   touch it.  The followed chains are the first C of the [kept][p][J_local] layout. */
+#define CESX_CHAIN_ACF_LAGS_MAX 64
+/* Clears the stage for a run of N = n_draws draws, L = lags in [1, CESX_CHAIN_ACF_LAGS_MAX] and C = n_chains in
+   [1, J_local].  CESX_EINVAL (text in cesx_last_error) outside these, for n_draws < max(4, lags + 2) or for a sharded handle
+   (J_local != J_global); the run in hand, if any, then goes on unharmed.  Launches nothing. */
+int cesx_chain_acf_begin(cesx_handle h, int n_draws, int lags, int n_chains, void* stream);
+/* Adds `kept` draws laid out [kept][p][J_local] in the engine dtype: the arguments of cesx_chain_summary_add.  Reads the
+   draws and writes only the stage's own memory (what waits there is read by a later add or by read: the caller's buffer
+   is free on return of the launches).  CESX_ESTATE without a begin or past N draws, CESX_EINVAL for a null pointer or
+   kept < 1; neither launches anything. */
+int cesx_chain_acf_add(cesx_handle h, const void* trace_dev, int kept, void* stream);
+/* HOST outputs; synchronises `stream`.  gsum [p][L + 1] = sum over the chains of G_k; msum [p] = sum (m_j - cbar) and
+   m2sum [p] = sum (m_j - cbar)^2 about cbar = the mean of the chains' first draws; optional (NULL allowed) chain_gamma
+   [L + 1][p][C]: every chain's G_k, and chain_mean [p][C]: every chain's m.  CESX_ESTATE unless exactly N draws were
+   added (nothing is launched then), CESX_EINVAL for a null gsum, msum or m2sum; the stage stays readable until the next
+   begin. */
+int cesx_chain_acf_read(cesx_handle h, double* gsum, double* msum, double* m2sum, double* chain_gamma, double* chain_mean,
+                        void* stream);
+
 /* ---- Emulate: GP prediction and the GP sampler over the columns (ces/emulate.py, ces/sample.py:17-119) --
    One exact GP per output, trained on the host (ces_amd/emulate.py); the engine holds its own fp64 image of them and
    evaluates them for every column at once.  GP i maps an input x to z = A_i (x - c) (A_i = diag(1/l_i) S^{-1} lower
