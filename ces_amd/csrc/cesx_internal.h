@@ -804,6 +804,13 @@ int launch_gp_score_dense(Engine& e, bool start, const void* X, const double* me
 int gp_proj_prepare(Engine& e, int k);
 int launch_gp_score_proj(Engine& e, bool start, const void* X, const double* mean, const double* var, void* U,
                          const double* logu, unsigned step, hipStream_t s);
+// gp_proj_group: the lanes of one chain's group (16, 32 or 64) for k; gp_proj_lds: the dynamic LDS of a workgroup of either kernel
+int gp_proj_group(int k);
+size_t gp_proj_lds(int k);
+// kernels_gpprojgrad.hip: the gradient coefficients of CESX_GP_PROJ from the rows (gpp.k x J): phid [J] the data term of phi
+// (launch_gp_score_proj's bits), ca and cb [gpp.k][J] the a_t and b_t lv_score reads in mode CESX_GP_PROJ
+int gp_proj_coef_prepare(Engine& e, int k);
+int launch_gp_proj_coef(Engine& e, const double* mean, const double* var, double* phid, double* ca, double* cb, hipStream_t s);
 
 // kernels_darcy.hip: G = the installed Darcy map of the columns of U (engine dtype in and out, fp64 inside); status (J int32,
 // or nullptr): 0, the 1-based column of the zero pivot of a particle whose outputs are NaN, or minus the column that held a

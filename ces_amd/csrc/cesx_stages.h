@@ -29,7 +29,8 @@ struct MhState {
     DevBuf<double> bS;                 // [p][p] b S, fp64 row-major: the proposal as gp_chain_kernel reads it (cesx_gp_run)
     std::vector<double> h_bS;          // [p][p] b S on the host: cesx_mh_run_map passes it by value
     DevBuf<double> lv_g, lv_gp;        // Langevin: [p][J] g = S^T grad phi of the chains' states and of the proposals (kernels_gpgrad.hip)
-    DevBuf<double> lv_a, lv_b, lv_gphi; // Langevin: [n][J], [n][J], [p][J] what lv_score keeps per chain: a_i, b_i, grad phi
+    DevBuf<double> lv_a, lv_b, lv_gphi; // Langevin: [max(n, k)][J] twice, [p][J] what lv_score keeps per chain: a_i, b_i, grad phi (k: CESX_GP_PROJ's rows)
+    DevBuf<double> phi_data;           // Langevin, CESX_GP_PROJ: [J] the data term of phi of the states being scored (kernels_gpprojgrad.hip)
     // HMC under a Langevin proposal (cesx_mh_hmc_* / cesx_gp_hmc_*, kernels_hmc.hip): the chains' phi, g and noise block are the Langevin step's
     bool hm_begun = false;             // a cesx_mh_hmc_begin since the start or the last accept: xi and hm_r belong to a trajectory in flight
     DevBuf<double> hm_r;               // [p][J] the momentum r of the trajectory in flight

@@ -906,7 +906,10 @@ int cesx_mh_set_proposal(cesx_handle h, int kind, const double* S, double beta) 
     if (kind == CESX_MH_LANGEVIN) {            // what the lv_* kernels keep per chain (kernels_gpgrad.hip)
         TRY_BUF(e.mh.lv_g.ensure((size_t)p * (size_t)e.J * 8)); TRY_BUF(e.mh.lv_gp.ensure((size_t)p * (size_t)e.J * 8));
         TRY_BUF(e.mh.lv_gphi.ensure((size_t)p * (size_t)e.J * 8)); TRY_BUF(e.mh.hm_r.ensure((size_t)p * (size_t)e.J * 8));
-        TRY_BUF(e.mh.lv_a.ensure((size_t)e.n * (size_t)e.J * 8)); TRY_BUF(e.mh.lv_b.ensure((size_t)e.n * (size_t)e.J * 8));
+        // (rows for max(n, k): CESX_GP_PROJ's coefficients are k-dimensional; a descriptor installed later grows them, proj_rows)
+        const size_t rows = (size_t)std::max(e.n, e.gpp.k);
+        TRY_BUF(e.mh.lv_a.ensure(rows * (size_t)e.J * 8)); TRY_BUF(e.mh.lv_b.ensure(rows * (size_t)e.J * 8));
+        TRY_BUF(e.mh.phi_data.ensure((size_t)e.J * 8));
     }
     TRY_BUF(e.mh.phi.ensure((size_t)e.J * 8)); TRY_BUF(e.mh.cnt.ensure((size_t)e.J * 8));
     e.mh.a = kind == CESX_MH_PCN ? std::sqrt(1.0 - beta * beta) : 1.0;
@@ -1106,6 +1109,7 @@ int cesx_gp_proj_set(cesx_handle h, const cesx_gp_proj_desc* d) {
     TRY(upload(e, e.gpp.R, R.data(), R.size() * 8)); TRY(upload(e, e.gpp.Rt, Rt.data(), Rt.size() * 8));
     TRY(upload(e, e.gpp.a0, d->a0, (size_t)k * 8));
     TRY(gp_proj_prepare(e, k));
+    TRY(gp_proj_coef_prepare(e, k));
     e.gpp.c_perp = d->c_perp; e.gpp.half_logdet_gamma = d->half_logdet_gamma;
     e.gpp.logdet = d->logdet ? 1 : 0;
     e.gpp.k = k;
@@ -1216,7 +1220,7 @@ int cesx_gp_predict_grad(cesx_handle h, const void* X, double* mean, double* var
 // an armed handle (cesx_mh_adapt_set) runs adaptation steps through cesx_mh_hmc_begin / _leap / _accept and cesx_gp_hmc_leap /
 // _accept alone: every other step of the Langevin family would move the chains at a step the recursion does not see
 static int adapt_refuses(Engine& e) {
-    if (e.mh.ad_armed) { e.err = "the handle is armed for step-size adaptation (cesx_mh_adapt_set): its steps are cesx_mh_hmc_begin / _leap / _accept and cesx_gp_hmc_leap / _accept; cesx_mh_adapt_read, then cesx_mh_set_proposal, ends the phase"; return CESX_ESTATE; }
+    if (e.mh.ad_armed) { e.err = "the handle is armed for step-size adaptation (cesx_mh_adapt_set): its steps are cesx_mh_hmc_begin / _leap / _accept and cesx_gp_hmc_leap / _accept (cesx_gp_proj_hmc_leap / _accept); cesx_mh_adapt_read, then cesx_mh_set_proposal, ends the phase"; return CESX_ESTATE; }
     return CESX_OK;
 }
 
@@ -2013,6 +2017,111 @@ int cesx_gp_hmc_accept(cesx_handle h, int mode, uint64_t step_index, void* U, co
     SET_DEVICE(e);
     FLUSH(e);
     TRY(launch_hmc(e, 2, mode, const_cast<void*>(Q), mean, var, dmean, dvar, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    if (e.mh.ad_armed) { TRY(launch_adapt_update(e, (hipStream_t)stream)); ++e.mh.ad_done; }
+    e.mh.hm_begun = false;
+    ++e.mh.steps;
+    return CESX_OK;
+}
+
+// ---- the gradient samplers on the projected Sigma (CESX_GP_PROJ; kernels_gpprojgrad.hip, then the lv_* / hm_* kernels) ----
+
+// what cesx_gp_proj_coef and the cesx_gp_proj_langevin_* / cesx_gp_proj_hmc_* calls need of the descriptor, the emulator and the rows
+static int proj_check(Engine& e, const double* mean, const double* var, const double* dmean, const double* dvar, bool grads) {
+    if (e.gpp.none()) { e.err = "cesx_gp_proj: no descriptor (cesx_gp_proj_set after cesx_set_problem)"; return CESX_ESTATE; }
+    if (e.gp.none()) { e.err = "cesx_gp_proj: cesx_gp_set has not been called"; return CESX_ESTATE; }
+    if (e.gp.matern12) { e.err = "cesx_gp_proj: a Matern12 kernel is not differentiable at its training points"; return CESX_EUNSUPPORTED; }
+    if (e.gp.n != e.gpp.k) { e.err = "cesx_gp_proj: the emulator's n_gp differs from the descriptor's k"; return CESX_EINVAL; }
+    if (!mean || !var || (grads && (!dmean || !dvar))) { e.err = "cesx_gp_proj: null pointer (the projected Sigma needs var and dvar)"; return CESX_EINVAL; }
+    return CESX_OK;
+}
+
+// lv_a / lv_b hold max(n, k) rows: a descriptor installed after the proposal, with k > n_obs, grows them here (what is in
+// them is scratch of one launch; a launch in flight may still read the old ones)
+static int proj_rows(Engine& e) {
+    const size_t need = (size_t)std::max(e.n, e.gpp.k) * (size_t)e.J * 8;
+    if (e.mh.lv_a.bytes >= need && e.mh.lv_b.bytes >= need) return CESX_OK;
+    CESX_HIP(hipDeviceSynchronize());
+    TRY_BUF(e.mh.lv_a.ensure(need)); TRY_BUF(e.mh.lv_b.ensure(need));
+    return CESX_OK;
+}
+
+int cesx_gp_proj_coef(cesx_handle h, const double* mean, const double* var, double* phi, double* a, double* b, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(proj_check(e, mean, var, nullptr, nullptr, false));
+    if (!phi || !a || !b) { e.err = "cesx_gp_proj_coef: null pointer"; return CESX_EINVAL; }
+    SET_DEVICE(e);
+    FLUSH(e);
+    return launch_gp_proj_coef(e, mean, var, phi, a, b, (hipStream_t)stream);
+}
+
+int cesx_gp_proj_langevin_start(cesx_handle h, const void* U, const double* mean, const double* var, const double* dmean,
+                                const double* dvar, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(langevin_check_state(e, false));
+    if (!U) { e.err = "cesx_gp_proj_langevin_start: null pointer"; return CESX_EINVAL; }
+    TRY(proj_check(e, mean, var, dmean, dvar, true));
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(proj_rows(e));
+    TRY(launch_gp_proj_coef(e, mean, var, e.mh.phi_data, e.mh.lv_a, e.mh.lv_b, (hipStream_t)stream));
+    TRY(launch_gp_langevin(e, 0, CESX_GP_PROJ, U, mean, var, dmean, dvar, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream));
+    e.mh.started = true;
+    e.mh.lin_started = false;
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;
+    e.mh.steps = 0;
+    return CESX_OK;
+}
+
+int cesx_gp_proj_langevin_accept(cesx_handle h, uint64_t step_index, void* U, const void* P, const double* mean, const double* var,
+                                 const double* dmean, const double* dvar, const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(langevin_check_state(e, true));
+    if (!e.mh.lv_proposed) { e.err = "cesx_gp_proj_langevin_accept: no cesx_gp_langevin_propose since the start or the last accept"; return CESX_ESTATE; }
+    if (!U || !P) { e.err = "cesx_gp_proj_langevin_accept: null pointer"; return CESX_EINVAL; }
+    if (U == P) { e.err = "cesx_gp_proj_langevin_accept: P must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_gp_proj_langevin_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    TRY(proj_check(e, mean, var, dmean, dvar, true));
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(proj_rows(e));
+    TRY(launch_gp_proj_coef(e, mean, var, e.mh.phi_data, e.mh.lv_a, e.mh.lv_b, (hipStream_t)stream));
+    TRY(launch_gp_langevin(e, 2, CESX_GP_PROJ, P, mean, var, dmean, dvar, U, nullptr, logu, mh_step_word(step_index), (hipStream_t)stream));
+    e.mh.lv_proposed = false; e.mh.hm_begun = false;
+    ++e.mh.steps;
+    return CESX_OK;
+}
+
+int cesx_gp_proj_hmc_leap(cesx_handle h, void* Q, const double* mean, const double* var, const double* dmean, const double* dvar,
+                          void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hmc_check_state(e, true));
+    if (!Q) { e.err = "cesx_gp_proj_hmc_leap: null pointer"; return CESX_EINVAL; }
+    TRY(proj_check(e, mean, var, dmean, dvar, true));
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(proj_rows(e));
+    TRY(launch_gp_proj_coef(e, mean, var, e.mh.phi_data, e.mh.lv_a, e.mh.lv_b, (hipStream_t)stream));
+    return launch_hmc(e, 1, CESX_GP_PROJ, Q, mean, var, dmean, dvar, nullptr, nullptr, 0u, (hipStream_t)stream);
+}
+
+int cesx_gp_proj_hmc_accept(cesx_handle h, uint64_t step_index, void* U, const void* Q, const double* mean, const double* var,
+                            const double* dmean, const double* dvar, const double* logu, void* stream) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    TRY(hmc_check_state(e, true));
+    if (!U || !Q) { e.err = "cesx_gp_proj_hmc_accept: null pointer"; return CESX_EINVAL; }
+    if (U == Q) { e.err = "cesx_gp_proj_hmc_accept: Q must not alias U"; return CESX_EINVAL; }
+    if (step_index >= 0x80000000ull) { e.err = "cesx_gp_proj_hmc_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    TRY(proj_check(e, mean, var, dmean, dvar, true));
+    SET_DEVICE(e);
+    FLUSH(e);
+    TRY(proj_rows(e));
+    TRY(launch_gp_proj_coef(e, mean, var, e.mh.phi_data, e.mh.lv_a, e.mh.lv_b, (hipStream_t)stream));
+    TRY(launch_hmc(e, 2, CESX_GP_PROJ, const_cast<void*>(Q), mean, var, dmean, dvar, U, logu, mh_step_word(step_index), (hipStream_t)stream));
     if (e.mh.ad_armed) { TRY(launch_adapt_update(e, (hipStream_t)stream)); ++e.mh.ad_done; }
     e.mh.hm_begun = false;
     ++e.mh.steps;

@@ -326,7 +326,8 @@ static int lv_t(Engine& e, int what, int mode, const void* X, const double* mean
                 const double* dvar, void* U, void* P, const double* logu, unsigned step, hipStream_t s) {
     LvArgs<T> a{};
     a.mean = mean; a.var = var; a.dmean = dmean; a.dvar = dvar;
-    a.n = e.n; a.p = e.p; a.mode = mode; a.M = e.J;
+    a.n = mode == CESX_GP_PROJ ? e.gpp.k : e.n; a.p = e.p; a.mode = mode; a.M = e.J;
+    a.phid = e.mh.phi_data;
     a.y = e.d_y; a.gw = e.d_gw; a.gam = e.d_Gamma; a.Lg = e.whiten ? e.d_Wh : nullptr;
     a.X = (const T*)X; a.mu = e.d_mu; a.sw = e.d_sw; a.LSi = e.diag_sigma ? nullptr : e.mh.LSi.get();
     a.S = e.mh.bS;

@@ -43,8 +43,8 @@ struct GpProjArgs {
     MhChains c;
 };
 
-static int gp_proj_group(int k) { return k <= 16 ? 16 : k <= 32 ? 32 : 64; }
-static size_t gp_proj_lds(int k) {
+int gp_proj_group(int k) { return k <= 16 ? 16 : k <= 32 ? 32 : 64; }
+size_t gp_proj_lds(int k) {
     return (size_t)(GPP_THREADS / gp_proj_group(k)) * ((size_t)k * (k + 1) / 2 + 2 * (size_t)k) * 8;
 }
 

@@ -150,7 +150,8 @@ static int hm_t(Engine& e, int what, int mode, void* Q, const double* mean, cons
     HmArgs<T> h{};
     LvArgs<T>& a = h.lv;                            // (filled as lv_t of kernels_gpgrad.hip fills it for a proposal)
     a.mean = mean; a.var = var; a.dmean = dmean; a.dvar = dvar;
-    a.n = e.n; a.p = e.p; a.mode = mode; a.M = e.J;
+    a.n = mode == CESX_GP_PROJ ? e.gpp.k : e.n; a.p = e.p; a.mode = mode; a.M = e.J;
+    a.phid = e.mh.phi_data;
     a.y = e.d_y; a.gw = e.d_gw; a.gam = e.d_Gamma; a.Lg = e.whiten ? e.d_Wh : nullptr;
     a.X = (const T*)Q; a.mu = e.d_mu; a.sw = e.d_sw; a.LSi = e.diag_sigma ? nullptr : e.mh.LSi.get();
     a.S = e.mh.bS;

@@ -9,7 +9,8 @@ namespace cesx {
 template <typename T>
 struct LvArgs {
     const double *mean, *var, *dmean, *dvar;        // the GP rows [n][M] and their gradients [n][p][M] at X
-    int n, p, mode; long long M;
+    const double* phid;                             // CESX_GP_PROJ: [M] the data term of phi at X (gp_proj_coef_kernel)
+    int n, p, mode; long long M;                    // (CESX_GP_PROJ: n is the descriptor's k)
     const double *y, *gw, *gam, *Lg;                // gp_score_kernel's data: y (whitened when Lg != nullptr), 1 / Gamma_ii, Gamma, L_Gamma^{-1}
     const T* X; const double *mu, *sw, *LSi;        // and its prior: diagonal (sw) or dense (LSi = L_Sigma^{-1})
     const double* S;                                // [p][p] the lower-triangular scale
@@ -29,7 +30,10 @@ __device__ __forceinline__ double lv_score(const LvArgs<T>& a, long long j) {
     const int n = a.n, p = a.p;
     const size_t M = (size_t)a.M;
     double s = 0.0;
-    if (a.mode == CESX_GP_GAMMA) {
+    if (a.mode == CESX_GP_PROJ) {
+        // ca and cb are filled: a_t = e_t, b_t = 1/2 ([logdet] h_t - e_t^2) of gp_proj_coef_kernel (kernels_gpprojgrad.hip), which
+        // factored I_k + R diag(v) R^T of this chain; the data term of phi is a.phid[j] and s sums the prior term alone
+    } else if (a.mode == CESX_GP_GAMMA) {
         if (a.Lg) {
             for (int i = 0; i < n; ++i) {
                 double w = 0.0;
@@ -95,6 +99,8 @@ __device__ __forceinline__ double lv_score(const LvArgs<T>& a, long long j) {
         for (int q = r; q < p; ++q) acc = fma(a.S[(size_t)q * p + r], a.gphi[q * M + j], acc);
         a.gx[r * M + j] = acc;
     }
+    // (CESX_GP_PROJ: gp_score_proj_kernel's final expression, 1/2 q + ld + 1/2 s, so a start here leaves cesx_gp_start's bits)
+    if (a.mode == CESX_GP_PROJ) return a.phid[j] + 0.5 * s;
     return 0.5 * s;
 }
 

@@ -585,7 +585,9 @@ def predict_gps(enka, X, mute_bar=True, **kwargs):
     if kwargs.get('grad', False):
         for name in ('pca_tools', 'separable'):
             if kwargs.get(name, None) not in (None, False):
-                raise ValueError("predict_gps(grad=True): %s has no gradient path (the gradients are those of the GP rows)" % name)
+                raise ValueError("predict_gps(grad=True): %s has no gradient path (the gradients are those of the GP rows%s)"
+                                 % (name, "; gp_mh(chains=M, sigma_form='projected') differentiates the projected Sigma on the "
+                                          "device from the k GPs' own rows" if name == 'pca_tools' else ""))
 
     if kwargs.get('device', False):
         return _predict_gps_device(enka, X, gpmodels, kwargs)

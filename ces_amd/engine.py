@@ -33,6 +33,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_mh_set_proposal", "cesx_mh_start", "cesx_mh_propose", "cesx_mh_accept", "cesx_mh_stats", "cesx_mh_phi",
            "cesx_gp_set", "cesx_gp_predict", "cesx_gp_start", "cesx_gp_accept", "cesx_gp_run", "cesx_gp_dense_set", "cesx_gp_proj_set",
            "cesx_gp_predict_grad", "cesx_gp_langevin_start", "cesx_gp_langevin_propose", "cesx_gp_langevin_accept",
+           "cesx_gp_proj_coef", "cesx_gp_proj_langevin_start", "cesx_gp_proj_langevin_accept", "cesx_gp_proj_hmc_leap", "cesx_gp_proj_hmc_accept",
            "cesx_gpfit_set", "cesx_gpfit_ntheta", "cesx_gpfit_eval", "cesx_gpfit_factors",
            "cesx_darcy_set", "cesx_darcy_apply", "cesx_darcy_set_streamed", "cesx_darcy_workspace_bytes", "cesx_lorenz_set", "cesx_lorenz_apply",
            "cesx_lorenz_three_set", "cesx_lorenz_three_apply", "cesx_map_set", "cesx_map_apply", "cesx_mh_run_map",
@@ -289,6 +290,11 @@ def load_library(path=None):
     lib.cesx_gp_langevin_start.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     lib.cesx_gp_langevin_propose.argtypes = [vp, u64, vp, vp, vp, vp]
     lib.cesx_gp_langevin_accept.argtypes = [vp, i32, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gp_proj_coef.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gp_proj_langevin_start.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gp_proj_langevin_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gp_proj_hmc_leap.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.cesx_gp_proj_hmc_accept.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cesx_gpfit_set.argtypes = [vp, C.POINTER(GpFitDesc)]
     lib.cesx_gpfit_ntheta.argtypes = [vp]
     lib.cesx_gpfit_eval.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
@@ -1132,11 +1138,16 @@ class Engine:
 
     def gp_langevin_start(self, mode, U, mean, var, dmean, dvar):
         """phi and g = S^T grad phi of the current states U from their GP rows and gradients (``gp_predict_grad`` at U) in
-        likelihood mode ``mode`` ('gamma', 'var', 'gamma_var'); counters cleared (cesx_gp_langevin_start)."""
+        likelihood mode ``mode`` ('gamma', 'var', 'gamma_var'); counters cleared (cesx_gp_langevin_start).  Mode 'proj': the
+        projected Sigma of ``gp_proj_set``, rows (k, J) and gradients (k, p, J) (cesx_gp_proj_langevin_start)."""
         ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
         with torch.cuda.device(self.device):
-            self._check(self.lib.cesx_gp_langevin_start(self._h, GP_MODES[mode], U.data_ptr(), ptr(mean), ptr(var), ptr(dmean),
-                                                        ptr(dvar), self._stream()))
+            if mode == "proj":
+                self._check_proj(self.lib.cesx_gp_proj_langevin_start(self._h, U.data_ptr(), ptr(mean), ptr(var), ptr(dmean),
+                                                                      ptr(dvar), self._stream()))
+            else:
+                self._check(self.lib.cesx_gp_langevin_start(self._h, GP_MODES[mode], U.data_ptr(), ptr(mean), ptr(var), ptr(dmean),
+                                                            ptr(dvar), self._stream()))
         self._keep_lv_s = (U, mean, var, dmean, dvar)
 
     def gp_langevin_propose(self, step_index, U, xi=None, out=None):
@@ -1156,9 +1167,40 @@ class Engine:
             assert logu.dtype == torch.float64 and logu.numel() == self.J and logu.is_contiguous()
         ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
         with torch.cuda.device(self.device):
-            self._check(self.lib.cesx_gp_langevin_accept(self._h, GP_MODES[mode], int(step_index), U.data_ptr(), P.data_ptr(),
-                                                         ptr(mean), ptr(var), ptr(dmean), ptr(dvar), ptr(logu), self._stream()))
+            if mode == "proj":
+                self._check_proj(self.lib.cesx_gp_proj_langevin_accept(self._h, int(step_index), U.data_ptr(), P.data_ptr(), ptr(mean),
+                                                                       ptr(var), ptr(dmean), ptr(dvar), ptr(logu), self._stream()))
+            else:
+                self._check(self.lib.cesx_gp_langevin_accept(self._h, GP_MODES[mode], int(step_index), U.data_ptr(), P.data_ptr(),
+                                                             ptr(mean), ptr(var), ptr(dmean), ptr(dvar), ptr(logu), self._stream()))
         self._keep_lv_a = (U, P, mean, var, dmean, dvar, logu)
+
+    def _check_proj(self, rc):
+        """``_check`` for the cesx_gp_proj_* calls: EUNSUPPORTED is a Matern12 image (not the reference's missing LM_procedure)."""
+        if rc == EUNSUPPORTED:
+            raise CesxError(rc, self.lib.cesx_last_error(self._h).decode())
+        self._check(rc)
+
+    def gp_proj_coef(self, mean, var, out=None):
+        """(phi_data (J,), a (k, J), b (k, J)), float64 device tensors: the data term of phi in mode 'proj' and the gradient
+        coefficients a_t = d phi / d m_t, b_t = d phi / d v_t of the projected Sigma from the rows ``mean``, ``var`` (k, J)
+        (cesx_gp_proj_coef; the descriptor of ``gp_proj_set``).  ``out``: a (phi, a, b) tuple to write into."""
+        k = mean.shape[0]
+        if k != getattr(self, "gp_n", k):         # (the kernel reads the descriptor's k rows: n_gp == k is the C side's check)
+            raise ValueError("gp_proj_coef: %d rows for the emulator's n_gp = %d" % (k, self.gp_n))
+        if out is None:
+            out = (torch.empty(self.J, dtype=torch.float64, device=self.device),
+                   torch.empty((k, self.J), dtype=torch.float64, device=self.device),
+                   torch.empty((k, self.J), dtype=torch.float64, device=self.device))
+        for name, t, shape in (("mean", mean, (k, self.J)), ("var", var, (k, self.J)), ("phi", out[0], (self.J,)),
+                               ("a", out[1], (k, self.J)), ("b", out[2], (k, self.J))):
+            if t is None or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("gp_proj_coef: %s must be a contiguous float64 device tensor of shape %s" % (name, shape))
+        with torch.cuda.device(self.device):
+            self._check_proj(self.lib.cesx_gp_proj_coef(self._h, mean.data_ptr(), var.data_ptr(), out[0].data_ptr(),
+                                                        out[1].data_ptr(), out[2].data_ptr(), self._stream()))
+        self._keep_gp_pc = (mean, var, out)
+        return out
 
     # -- GP training: the batched likelihood and gradient (include/cesx.h, cesx_gpfit_*; ces_amd/emulate.py drives it) --
     def gpfit_set(self, X, Y, family, ard=True, mean="zero"):
@@ -1473,8 +1515,12 @@ class Engine:
         """``mh_hmc_leap`` on the GP rows and gradients at Q (``gp_predict_grad``) in likelihood mode ``mode`` (cesx_gp_hmc_leap)."""
         ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
         with torch.cuda.device(self.device):
-            self._check(self.lib.cesx_gp_hmc_leap(self._h, GP_MODES[mode], Q.data_ptr(), ptr(mean), ptr(var), ptr(dmean), ptr(dvar),
-                                                  self._stream()))
+            if mode == "proj":                   # (cesx_gp_proj_hmc_leap: the projected Sigma of ``gp_proj_set``)
+                self._check_proj(self.lib.cesx_gp_proj_hmc_leap(self._h, Q.data_ptr(), ptr(mean), ptr(var), ptr(dmean), ptr(dvar),
+                                                                self._stream()))
+            else:
+                self._check(self.lib.cesx_gp_hmc_leap(self._h, GP_MODES[mode], Q.data_ptr(), ptr(mean), ptr(var), ptr(dmean),
+                                                      ptr(dvar), self._stream()))
         self._keep_hm_l = (Q, mean, var, dmean, dvar)
 
     def gp_hmc_accept(self, mode, step_index, U, Q, mean, var, dmean, dvar, logu=None):
@@ -1483,8 +1529,12 @@ class Engine:
             assert logu.dtype == torch.float64 and logu.numel() == self.J and logu.is_contiguous()
         ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
         with torch.cuda.device(self.device):
-            self._check(self.lib.cesx_gp_hmc_accept(self._h, GP_MODES[mode], int(step_index), U.data_ptr(), Q.data_ptr(),
-                                                    ptr(mean), ptr(var), ptr(dmean), ptr(dvar), ptr(logu), self._stream()))
+            if mode == "proj":                   # (cesx_gp_proj_hmc_accept)
+                self._check_proj(self.lib.cesx_gp_proj_hmc_accept(self._h, int(step_index), U.data_ptr(), Q.data_ptr(), ptr(mean),
+                                                                  ptr(var), ptr(dmean), ptr(dvar), ptr(logu), self._stream()))
+            else:
+                self._check(self.lib.cesx_gp_hmc_accept(self._h, GP_MODES[mode], int(step_index), U.data_ptr(), Q.data_ptr(),
+                                                        ptr(mean), ptr(var), ptr(dmean), ptr(dvar), ptr(logu), self._stream()))
         self._keep_hm_a = (U, Q, mean, var, dmean, dvar, logu)
 
     def mh_hmc_run_map(self, step_index, n_steps, leapfrog, U, stride=1, trace=None, xi=None, logu=None):

@@ -90,8 +90,11 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          P = U + S (xi - g(U) / 2), accepted when
                          log u < phi(U) - phi(P) + |xi|^2 / 2 - |xi - (g(U) + g(P)) / 2|^2 / 2.  The draws per step are the random
                          walk's (xi, then u).  Likelihoods: Gamma (dense or diagonal), diag(gvars) and diag(Gamma) +
-                         diag(gvars).  ``fused=True``, ``pca_tools``, ``separable``, emulators without gradients and Matern12
-                         kernels raise ``ValueError``.  ``summary=``,
+                         diag(gvars); and, with ``chains=M, sigma_form='projected'`` only, the Sigma of ``pca_tools``
+                         (``cesx_gp_proj_langevin_*`` / ``cesx_gp_proj_hmc_*``: kernels_gpprojgrad.hip forms the coefficients of
+                         grad m_t and grad v_t from the k x k factor per chain; ``MCMC.langevin_phi_grad_pca`` is the n-space
+                         restatement).  ``fused=True``, ``pca_tools`` on the host or with ``sigma_form='dense'``, ``separable``,
+                         emulators without gradients and Matern12 kernels raise ``ValueError``.  ``summary=``,
                          ``burn=``, ``marginals=``, ``start=``, ``noise=``, resume and ``trace_stride`` work as for the random walk.
                          model_mh takes it for a model with a Jacobian (``ces_amd.utils.elliptic`` and ``banana``:
                          ``model.jacobian`` on the host, ``model.jacobian_device`` -- ``cesx_map_jac`` -- with ``chains=M``): the
@@ -737,15 +740,20 @@ class MCMC(object):
     @staticmethod
     def _langevin_refusals(kwargs, prior):
         """What ``gp_mh(update='langevin')`` cannot do, host and device alike: every refusal is a ValueError with the reason."""
-        if kwargs.get("pca_tools", None) is not None:
-            raise ValueError("update='langevin': pca_tools has no gradient path (the dense and the projected Sigma are not "
-                             "differentiated); run the random walk (update=None) with pca_tools")
+        projected = False
+        if kwargs.get("pca_tools", None) is not None:     # differentiated on the device alone, in the projected form (DESIGN.md 5p)
+            projected = kwargs.get("chains", None) is not None and kwargs.get("sigma_form", None) == "projected"
+            if not projected:
+                raise ValueError("update='langevin': pca_tools has a gradient path only as chains=M, sigma_form='projected' (the "
+                                 "k x k projected Sigma is differentiated on the device); the host path and sigma_form='dense' "
+                                 "have none: pass chains=M, sigma_form='projected', or run the random walk (update=None) with "
+                                 "pca_tools")
         if kwargs.get("separable", False):
             raise ValueError("update='langevin': separable predicts one point at a time and has no gradient path")
         if not (hasattr(prior, "mean") and hasattr(prior, "cov")):
             raise ValueError("update='langevin': the prior must expose .mean and .cov (its gradient is cov^{-1} (u - mean))")
         Gamma = kwargs.get("Gamma", None)
-        if Gamma is not None and kwargs.get("noise_compounded", False):
+        if Gamma is not None and kwargs.get("noise_compounded", False) and not projected:
             G = np.asarray(Gamma, dtype=np.float64)
             if np.any(G != np.diag(np.diag(G))):
                 raise ValueError("update='langevin': noise_compounded with a dense Gamma has no gradient path (Gamma + "
@@ -770,6 +778,40 @@ class MCMC(object):
         w = np.linalg.solve(np.asarray(prior_cov, dtype=np.float64), (u - np.asarray(prior_mean, dtype=np.float64).reshape(1, -1)).T)
         phi = phi + 0.5 * ((u - np.asarray(prior_mean, dtype=np.float64).reshape(1, -1)).T * w).sum(axis=0)
         return phi, grad + w.T
+
+    @staticmethod
+    def langevin_phi_grad_pca(mean, var, dmean, dvar, u, y, Gamma, VD_k, mG, logdet, prior_mean, prior_cov):
+        """phi (up to the prior's constant) and grad phi at the states ``u`` (N, p) under ``pca_tools``: the k GP rows ``mean``,
+        ``var`` (k, N) and their gradients ``dmean``, ``dvar`` (k, N, p), B = ``VD_k`` (n, k), d = B m + mG - y and
+        Sigma_j = Gamma + B diag(v_j) B^T.  The literal n-space form in numpy, vectorised over the states -- ``solve`` with
+        Sigma_j, e = B^T Sigma^{-1} d, h = diag(B^T Sigma^{-1} B) --
+            phi = 1/2 d^T Sigma^{-1} d [+ 1/2 log det Sigma]                      (``logdet``: noise_compounded)
+            grad phi = sum_t (e_t grad m_t + 1/2 ([logdet] h_t - e_t^2) grad v_t) + prior_cov^{-1} (u - prior_mean):
+        the restatement the device's projected form (include/cesx.h, cesx_gp_proj_langevin_*) is held to.  A state whose
+        Sigma is not positive definite has phi = NaN."""
+        B = np.asarray(VD_k, dtype=np.float64)
+        n, k = B.shape
+        Gam = np.asarray(Gamma, dtype=np.float64).reshape(n, n)
+        mean, var = np.asarray(mean, dtype=np.float64), np.asarray(var, dtype=np.float64)
+        N = mean.shape[1]
+        d = B @ mean + np.asarray(mG, dtype=np.float64).reshape(n, 1) - np.asarray(y, dtype=np.float64).reshape(n, 1)      # (n, N)
+        Sig = Gam[None] + np.einsum("it,tj,lt->jil", B, var, B)                      # (N, n, n)
+        rhs = np.concatenate([d.T[:, :, None], np.broadcast_to(B, (N, n, k))], axis=2)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ev = np.linalg.eigvalsh(Sig)
+            sol = np.linalg.solve(Sig, rhs)                                          # Sigma^{-1} [d | B]
+            e = np.einsum("it,ji->tj", B, sol[:, :, 0])                              # (k, N)
+            phi = 0.5 * (d.T * sol[:, :, 0]).sum(axis=1)
+            b = -0.5 * e * e
+            if logdet:
+                h = np.einsum("it,jit->tj", B, sol[:, :, 1:])
+                phi = phi + 0.5 * np.log(ev).sum(axis=1)
+                b = 0.5 * (h - e * e)
+            phi = np.where(ev[:, 0] > 0.0, phi, np.nan)
+        grad = np.einsum("tn,tnq->nq", e, dmean) + np.einsum("tn,tnq->nq", b, dvar)
+        du = (u - np.asarray(prior_mean, dtype=np.float64).reshape(1, -1)).T
+        w = np.linalg.solve(np.asarray(prior_cov, dtype=np.float64), du)
+        return phi + 0.5 * (du * w).sum(axis=0), grad + w.T
 
     @staticmethod
     def langevin_correction(xi, g_current, g_proposal):

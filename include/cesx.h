@@ -1028,6 +1028,44 @@ typedef struct {
    without a problem.  A later cesx_set_problem drops the descriptor.  cesx_gp_start / cesx_gp_accept in mode CESX_GP_PROJ
    return CESX_ESTATE without one, and need var_dev and n_gp == k. */
 int cesx_gp_proj_set(cesx_handle h, const cesx_gp_proj_desc* desc);
+/* The gradient samplers on the projected Sigma: MCMC.gp_mh(chains=M, pca_tools=, sigma_form='projected', update='langevin' /
+   'hmc').  Per chain, with a = a0 + R m, A = I_k + R diag(v) R^T = L L^T and z = L^{-1} a (the factor of CESX_GP_PROJ above):
+       phi_data = 1/2 (c_perp + |z|^2) [+ half_logdet_gamma + sum log L_cc]        (the data term of cesx_gp_start's phi, its bits)
+       w   = L^{-T} z = A^{-1} a
+       e_t = (R^T w)_t = d phi / d m_t                       ( = B_t^T Sigma^{-1} d in the data space )
+       h_t = |L^{-1} R[:, t]|^2 = (R^T A^{-1} R)_tt          ( = B_t^T Sigma^{-1} B_t )
+       a_t = e_t,   b_t = 1/2 ([logdet] h_t - e_t^2) = d phi / d v_t
+       grad phi = sum_t (a_t grad m_t + b_t grad v_t) + Sigma_prior^{-1} (u - mu)
+   (without the descriptor's logdet flag the h term is absent: the gradient is the gradient of the phi that is scored).  With
+   R = I and a diagonal Gamma this is the variance mode of cesx_gp_langevin_*.  One launch (kernels_gpprojgrad.hip) on the
+   placement of the score launch -- a sub-wave group of lanes per chain, the factor resident in LDS -- forms phi_data, a and
+   b, all in fp64 in one fixed order: bit-reproducible, independent of J_local, of the column and of the neighbours; a pivot
+   that is not > 0 or not finite makes phi_data, a and b of that chain NaN (a proposal into it is rejected, a start state in
+   it stays stuck).  The lv_* / hm_* kernels then form the prior term, grad phi and g = S^T grad phi as in the other modes.
+       cesx_gp_proj_coef            the coefficient launch alone, from the (k x J_local) rows into caller buffers: phi_dev
+                                    [J_local], a_dev and b_dev [k][J_local], fp64
+       cesx_gp_proj_langevin_start / cesx_gp_proj_langevin_accept, cesx_gp_proj_hmc_leap / cesx_gp_proj_hmc_accept
+                                    cesx_gp_langevin_start / _accept and cesx_gp_hmc_leap / _accept without `mode`: the rows
+                                    and gradients (k x J_local, k x p x J_local) of cesx_gp_predict_grad.  The proposal and the
+                                    begin of a trajectory are cesx_gp_langevin_propose and cesx_mh_hmc_begin, which take no
+                                    mode; steps of both families alternate on one handle, and an armed handle
+                                    (cesx_mh_adapt_set) adapts through the hmc pair as through cesx_gp_hmc_*.
+   The cesx_gp_langevin_* and cesx_gp_hmc_* calls keep answering CESX_EINVAL for CESX_GP_DENSE and CESX_GP_PROJ.
+   CESX_ESTATE without a descriptor (cesx_gp_proj_set) or cesx_gp_set, and in the sequencing states of the namesakes;
+   CESX_EUNSUPPORTED for an emulator with a Matern12 GP; CESX_EINVAL for n_gp != k, a null pointer (var_dev and dvar_dev are
+   needed), P_dev / Q_dev aliasing U_dev or a step index >= 2^31.  None of these launches anything. */
+int cesx_gp_proj_coef(cesx_handle h, const double* mean_dev, const double* var_dev, double* phi_dev, double* a_dev, double* b_dev,
+                      void* stream);
+int cesx_gp_proj_langevin_start(cesx_handle h, const void* U_dev, const double* mean_dev, const double* var_dev,
+                                const double* dmean_dev, const double* dvar_dev, void* stream);
+int cesx_gp_proj_langevin_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* P_dev, const double* mean_dev,
+                                 const double* var_dev, const double* dmean_dev, const double* dvar_dev, const double* logu_dev,
+                                 void* stream);
+int cesx_gp_proj_hmc_leap(cesx_handle h, void* Q_dev, const double* mean_dev, const double* var_dev, const double* dmean_dev,
+                          const double* dvar_dev, void* stream);
+int cesx_gp_proj_hmc_accept(cesx_handle h, uint64_t step_index, void* U_dev, const void* Q_dev, const double* mean_dev,
+                            const double* var_dev, const double* dmean_dev, const double* dvar_dev, const double* logu_dev,
+                            void* stream);
 
 /* ---- Emulate: training the GPs on device (ces_amd/emulate.py train_gps(device=True)) --------------------
    The log marginal likelihood of n_gp exact GPs on SHARED training inputs X and its gradient, all GPs of a call in the same
