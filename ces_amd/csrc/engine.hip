@@ -958,8 +958,10 @@ int cesx_mh_accept(cesx_handle h, uint64_t step_index, void* U, const void* P, c
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U || !P || !GP) { e.err = "cesx_mh_accept: null pointer"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull) { e.err = "cesx_mh_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
-    if (e.mh.none() || !e.mh.started) { e.err = "cesx_mh_accept: cesx_mh_start has not been called"; return CESX_ESTATE; }
+    // (the kind first, as cesx_mh_start, cesx_mh_propose, cesx_mh_run_map and cesx_gp_run answer: under a Langevin proposal the call is
+    //  refused as such, whether or not one of the Langevin starts has run)
     if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_mh_accept: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }
+    if (e.mh.none() || !e.mh.started) { e.err = "cesx_mh_accept: cesx_mh_start has not been called"; return CESX_ESTATE; }
     SET_DEVICE(e);
     FLUSH(e);
     TRY(mh_score(e, false, P, GP, U, logu, mh_step_word(step_index), (hipStream_t)stream));
@@ -1170,8 +1172,8 @@ int cesx_gp_accept(cesx_handle h, int mode, uint64_t step_index, void* U, const 
     Engine& e = *reinterpret_cast<Engine*>(h);
     if (!U || !P) { e.err = "cesx_gp_accept: null pointer"; return CESX_EINVAL; }
     if (step_index >= 0x80000000ull) { e.err = "cesx_gp_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
+    if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_gp_accept: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }      // (the kind first: cesx_mh_accept)
     if (e.mh.none() || !e.mh.started) { e.err = "cesx_gp_accept: cesx_gp_start has not been called"; return CESX_ESTATE; }
-    if (e.mh.kind == CESX_MH_LANGEVIN) { e.err = "cesx_gp_accept: the proposal is CESX_MH_LANGEVIN (cesx_gp_langevin_*)"; return CESX_EINVAL; }
     TRY(gp_check_mode(e, mode, mean, var));
     SET_DEVICE(e);
     FLUSH(e);

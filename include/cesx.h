@@ -762,6 +762,24 @@ int cesx_mh_hmc_lineal_accept(cesx_handle h, uint64_t step_index, void* U_dev, c
 #define CESX_ADAPT_STEPS_MAX 65536
 int cesx_mh_adapt_set(cesx_handle h, int n_steps, double target, double gain, double kappa);
 int cesx_mh_adapt_read(cesx_handle h, double* multiplier, int* steps_done, double* history_host);
+/* Call order across the families.  The sections above state each family's sequencing against itself; where two of them meet on
+   one handle (tests/sampler_reuse_cases.py holds the whole table, state by entry point):
+     - One start serves both random-walk families: cesx_mh_accept and cesx_mh_run_map follow a cesx_gp_start, cesx_gp_accept and
+       cesx_gp_run a cesx_mh_start.  phi, the counters and the step count are the same memory; the caller answers for scoring
+       the proposals with the likelihood the start scored the states with.
+     - Under a proposal of kind CESX_MH_LANGEVIN the random-walk calls (cesx_mh_start / _propose / _accept / _run_map, cesx_gp_start /
+       _accept / _run) return CESX_EINVAL whether or not a Langevin start has run: the kind is looked at before the start.
+     - cesx_mh_langevin_start, cesx_gp_langevin_start and cesx_gp_proj_langevin_start are ONE family: each leaves phi and g in the
+       same memory, and cesx_mh_langevin_propose / _accept / _run_map, cesx_gp_langevin_propose / _accept, cesx_gp_proj_langevin_accept
+       and the cesx_mh_hmc_* / cesx_gp_hmc_* / cesx_gp_proj_hmc_* calls follow any of the three.  cesx_mh_langevin_lineal_start is the
+       other family (g in the engine dtype, in memory of its own): after it only cesx_mh_langevin_lineal_* and cesx_mh_hmc_lineal_*
+       step, and after one of the three only the calls above.
+     - A start is accepted while a proposal or a trajectory is pending and ends it.
+     - cesx_mh_langevin_lineal_set on a handle whose LAST start was cesx_mh_langevin_lineal_start ends that start -- the chains' g
+       belonged to the image it replaces --: until the next start every step, cesx_mh_langevin_lineal_g, cesx_mh_phi and
+       cesx_mh_stats return CESX_ESTATE.  After one of the other three starts the start stands, and a pending proposal or
+       trajectory is ended.
+     - cesx_gp_predict and cesx_gp_predict_grad need cesx_gp_set alone, in every state. */
 
 /* ---- Streaming summaries of the chains' draws (MCMC(..., chains=M, summary=True); kernels_chainsum.hip) --
    The sums behind the pooled mean and covariance, the split R-hat and an effective sample size of a run of
