@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcesx.so")
-SOURCES = ["engine.hip", "kernels_stats.hip", "kernels_gram.hip", "kernels_gram2.hip", "kernels_dense.hip", "kernels_update.hip", "kernels_update2.hip", "kernels_update3.hip", "kernels_update4.hip", "kernels_calib.hip", "kernels_mh.hip", "kernels_gp.hip", "kernels_gpchain.hip", "kernels_gpgrad.hip", "kernels_gpdense.hip", "kernels_gpproj.hip", "kernels_gpprojgrad.hip", "kernels_gpfit.hip", "kernels_darcy.hip", "kernels_darcy_grad.hip", "kernels_darcy_stream.hip", "kernels_l96.hip", "kernels_l63.hip", "kernels_maps.hip", "kernels_lvlin.hip", "kernels_hmclin.hip", "kernels_hmc.hip", "kernels_adapt.hip", "kernels_chainsum.hip", "kernels_chainhist.hip", "kernels_chainacf.hip", "comm.hip"]
+SOURCES = ["engine.hip", "kernels_stats.hip", "kernels_gram.hip", "kernels_gram2.hip", "kernels_dense.hip", "kernels_update.hip", "kernels_update2.hip", "kernels_update3.hip", "kernels_update4.hip", "kernels_calib.hip", "kernels_mh.hip", "kernels_gp.hip", "kernels_gpchain.hip", "kernels_gpgrad.hip", "kernels_gpdense.hip", "kernels_gpproj.hip", "kernels_gpprojgrad.hip", "kernels_gpfit.hip", "kernels_darcy.hip", "kernels_darcy_grad.hip", "kernels_darcy_chain.hip", "kernels_darcy_stream.hip", "kernels_l96.hip", "kernels_l63.hip", "kernels_maps.hip", "kernels_lvlin.hip", "kernels_hmclin.hip", "kernels_hmc.hip", "kernels_adapt.hip", "kernels_chainsum.hip", "kernels_chainhist.hip", "kernels_chainacf.hip", "comm.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("cesx_internal.h", "cesx_stages.h", "devbuf.h", "rk45_tables.h", "lv_score.h", "darcy_stages.h")] + [os.path.join(os.path.dirname(HERE), "include", "cesx.h")]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -857,6 +857,11 @@ int launch_hmc(Engine& e, int what, int mode, void* Q, const double* mean, const
                const double* dvar, void* U, const double* logu, unsigned step, hipStream_t s);
 int launch_mh_hmc_run_map(Engine& e, uint64_t step_index, int n_steps, int leapfrog, int stride, void* U, void* trace,
                           const void* xi, const double* logu, hipStream_t s);
+// kernels_darcy_chain.hip: the same steps on a READY-MADE gradient (cesx_mh_grad_source, CESX_MH_GRAD_READY): G [n][J] and d [p][J] =
+// the data term of grad phi at X (cesx_darcy_grad), one wave per chain.  what 0: phi and g of the states X into mh.phi / mh.lv_g,
+// counters cleared; 1: the Langevin accept of the proposal X; 2: the leap at X = Q, advanced in place; 3: the leapfrog accept at X
+int launch_darcy_chain(Engine& e, int what, const void* X, const double* G, const double* d, void* U, const double* logu,
+                       unsigned step, hipStream_t s);
 // kernels_adapt.hip: the step-size recursion behind an armed handle's accept (cesx_mh_adapt_*): mh.ad_alpha -> mh.ad_state, a
 // row of mh.ad_hist.  While mh.ad_armed, launch_hmc launches the ADAPT instantiations, which read mh.ad_state[0]
 int launch_adapt_update(Engine& e, hipStream_t s);

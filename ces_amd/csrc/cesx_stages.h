@@ -52,9 +52,11 @@ struct MhState {
     DevBuf<double> ad_alpha;           // [J] the chains' acceptance probabilities of the step in hand
     DevBuf<double> ad_state;           // [4] e, log e, log ebar, t
     DevBuf<double> ad_hist;            // [ad_n][2] row t - 1: e_t, abar_t
+    // where the Langevin / leapfrog entry points take the data term of grad phi from (cesx_mh_grad_source): the Jacobian image, or ready-made
+    int grad_source = 0;               // CESX_MH_GRAD_JACOBIAN; CESX_MH_GRAD_READY: the dc_* kernels (kernels_darcy_chain.hip)
     bool none() const { return kind < 0; }
     // every buffer is sized by the engine: kept -- but the adaptation's history, which its step count sizes
-    void drop() { kind = -1; started = false; lv_proposed = false; hm_begun = false; lin = 0; lin_started = false; ad_armed = false; ad_n = 0; ad_done = 0; ad_hist.reset(); }
+    void drop() { kind = -1; grad_source = 0; started = false; lv_proposed = false; hm_begun = false; lin = 0; lin_started = false; ad_armed = false; ad_n = 0; ad_done = 0; ad_hist.reset(); }
 };
 
 // ---- GP emulator over the columns (cesx_gp_*, kernels_gp.hip) ----

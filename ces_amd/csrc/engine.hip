@@ -1891,7 +1891,8 @@ int cesx_mh_langevin_start(cesx_handle h, const void* U, const double* G, const 
     if (!U || !G || !DG) { e.err = "cesx_mh_langevin_start: null pointer"; return CESX_EINVAL; }
     SET_DEVICE(e);
     FLUSH(e);
-    TRY(launch_gp_langevin(e, 0, CESX_GP_GAMMA, U, G, nullptr, DG, nullptr, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream));
+    if (e.mh.grad_source == CESX_MH_GRAD_READY) TRY(launch_darcy_chain(e, 0, U, G, DG, nullptr, nullptr, 0u, (hipStream_t)stream));      // (DG: [p][J] ready-made)
+    else TRY(launch_gp_langevin(e, 0, CESX_GP_GAMMA, U, G, nullptr, DG, nullptr, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream));
     e.mh.started = true;
     e.mh.lin_started = false;
     e.mh.lv_proposed = false; e.mh.hm_begun = false;
@@ -1928,7 +1929,8 @@ int cesx_mh_langevin_accept(cesx_handle h, uint64_t step_index, void* U, const v
     if (step_index >= 0x80000000ull) { e.err = "cesx_mh_langevin_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
     SET_DEVICE(e);
     FLUSH(e);
-    TRY(launch_gp_langevin(e, 2, CESX_GP_GAMMA, P, G, nullptr, DG, nullptr, U, nullptr, logu, mh_step_word(step_index), (hipStream_t)stream));
+    if (e.mh.grad_source == CESX_MH_GRAD_READY) TRY(launch_darcy_chain(e, 1, P, G, DG, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    else TRY(launch_gp_langevin(e, 2, CESX_GP_GAMMA, P, G, nullptr, DG, nullptr, U, nullptr, logu, mh_step_word(step_index), (hipStream_t)stream));
     e.mh.lv_proposed = false; e.mh.hm_begun = false;
     ++e.mh.steps;
     return CESX_OK;
@@ -1988,6 +1990,7 @@ int cesx_mh_hmc_leap(cesx_handle h, void* Q, const double* G, const double* DG, 
     if (!Q || !G || !DG) { e.err = "cesx_mh_hmc_leap: null pointer"; return CESX_EINVAL; }
     SET_DEVICE(e);
     FLUSH(e);
+    if (e.mh.grad_source == CESX_MH_GRAD_READY) return launch_darcy_chain(e, 2, Q, G, DG, nullptr, nullptr, 0u, (hipStream_t)stream);
     return launch_hmc(e, 1, CESX_GP_GAMMA, Q, G, nullptr, DG, nullptr, nullptr, nullptr, 0u, (hipStream_t)stream);
 }
 
@@ -2001,10 +2004,22 @@ int cesx_mh_hmc_accept(cesx_handle h, uint64_t step_index, void* U, const void* 
     if (step_index >= 0x80000000ull) { e.err = "cesx_mh_hmc_accept: MH step indices are limited to 2^31"; return CESX_EINVAL; }
     SET_DEVICE(e);
     FLUSH(e);
-    TRY(launch_hmc(e, 2, CESX_GP_GAMMA, const_cast<void*>(Q), G, nullptr, DG, nullptr, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    if (e.mh.grad_source == CESX_MH_GRAD_READY) TRY(launch_darcy_chain(e, 3, Q, G, DG, U, logu, mh_step_word(step_index), (hipStream_t)stream));
+    else TRY(launch_hmc(e, 2, CESX_GP_GAMMA, const_cast<void*>(Q), G, nullptr, DG, nullptr, U, logu, mh_step_word(step_index), (hipStream_t)stream));
     if (e.mh.ad_armed) { TRY(launch_adapt_update(e, (hipStream_t)stream)); ++e.mh.ad_done; }
     e.mh.hm_begun = false;
     ++e.mh.steps;
+    return CESX_OK;
+}
+
+// Where the four calls above take the data term of grad phi from (include/cesx.h): an install like cesx_mh_adapt_set -- no chains, no launch
+int cesx_mh_grad_source(cesx_handle h, int source) {
+    if (!h) return CESX_EINVAL;
+    Engine& e = *reinterpret_cast<Engine*>(h);
+    if (source != CESX_MH_GRAD_JACOBIAN && source != CESX_MH_GRAD_READY) { e.err = "cesx_mh_grad_source: source must be CESX_MH_GRAD_JACOBIAN or CESX_MH_GRAD_READY"; return CESX_EINVAL; }
+    if (!e.problem_set || e.mh.none() || e.mh.kind != CESX_MH_LANGEVIN) { e.err = "cesx_mh_grad_source: no Langevin proposal (cesx_mh_set_proposal with CESX_MH_LANGEVIN after cesx_set_problem)"; return CESX_ESTATE; }
+    if (source == CESX_MH_GRAD_READY && e.p > 256) { e.err = "cesx_mh_grad_source: CESX_MH_GRAD_READY serves p <= 256 (the chain's vectors live in LDS)"; return CESX_EUNSUPPORTED; }
+    e.mh.grad_source = source;
     return CESX_OK;
 }
 

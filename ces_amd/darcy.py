@@ -39,7 +39,8 @@ default host flow is unchanged.  ``enable_gradient()`` (build-only, opt-in) adds
 symmetric, so the gradient of the data misfit is one more solve on the same factorisation -- ``jacobian`` and
 ``misfit_gradient`` on the host, ``gradient_device`` on the device (cesx_darcy_grad, ces_amd/csrc/kernels_darcy_grad.hip: the
 resident solver only), and with ``jacobian`` the host path of ``MCMC.model_mh(update='langevin' / 'hmc', adapt=)``; with
-``chains=M`` those updates stay refused: no sampler step takes the adjoint launch yet.
+``chains=M`` those updates run on ``gradient_device``: one adjoint launch per position, its gradient handed ready-made to the
+Langevin and leapfrog entry points (cesx_mh_grad_source, ces_amd/csrc/kernels_darcy_chain.hip).
 
 PARITY UNPINNED: the MATLAB reference cannot run here, so there is no golden
 output; tests validate the restatement through the PDE itself (discrete
@@ -246,7 +247,7 @@ class model(object):
     def enable_gradient(self):
         """Offer the gradient of the map, to the host path of ``MCMC.model_mh(update='langevin' / 'hmc', adapt=)`` and to callers
         of their own (build-only, opt-in: without this call the instance has none of the attributes and the sampler refuses it
-        as before; with ``chains=M`` it stays refused: no sampler step takes the adjoint launch yet).  The 5-point operator is
+        as before; with ``chains=M`` the sampler runs on ``gradient_device``, one adjoint launch per position).  The 5-point operator is
         symmetric, so the adjoint solve is a second right-hand side of the forward solve's factorisation.  The instance gains
 
         ``jacobian(xi)``                          on the host, (n_obs, p): one sparse LU and n_obs adjoint solves

@@ -43,7 +43,7 @@ EXPORTS = ("cesx_abi_version", "cesx_create", "cesx_destroy", "cesx_last_error",
            "cesx_mh_langevin_lineal_accept", "cesx_mh_langevin_lineal_g",
            "cesx_mh_hmc_lineal_begin", "cesx_mh_hmc_lineal_leap", "cesx_mh_hmc_lineal_accept",
            "cesx_mh_hmc_begin", "cesx_mh_hmc_leap", "cesx_mh_hmc_accept", "cesx_gp_hmc_leap", "cesx_gp_hmc_accept", "cesx_mh_hmc_run_map",
-           "cesx_mh_adapt_set", "cesx_mh_adapt_read",
+           "cesx_mh_adapt_set", "cesx_mh_adapt_read", "cesx_mh_grad_source",
            "cesx_chain_summary_begin", "cesx_chain_summary_add", "cesx_chain_summary_read",
            "cesx_chain_hist_begin", "cesx_chain_hist_add", "cesx_chain_hist_read",
            "cesx_chain_acf_begin", "cesx_chain_acf_add", "cesx_chain_acf_read")
@@ -55,6 +55,7 @@ GPFIT_MEANS = {"zero": 0, "constant": 1, "linear": 2}   # CESX_GPFIT_MEAN_*
 GP_MODES = {"gamma": 0, "var": 1, "gamma_var": 2, "dense": 3, "proj": 4}     # CESX_GP_GAMMA / _VAR / _GAMMA_VAR / _DENSE / _PROJ: Sigma of MCMC.gp_mh (ces/sample.py:48-55)
 GP_DENSE_NMAX = 128                                   # CESX_GP_DENSE_NMAX
 GP_PROJ_KMAX = 128                                    # CESX_GP_PROJ_KMAX
+GRAD_SOURCES = {"jacobian": 0, "ready": 1}            # CESX_MH_GRAD_JACOBIAN / _READY (cesx_mh_grad_source)
 MAP_KINDS = {"elliptic": 1, "banana": 2, "exp": 3}    # CESX_MAP_ELLIPTIC / _BANANA / _EXP (ces_amd.utils elliptic, banana, lineal_log)
 MAP_FUSED = ("elliptic", "banana")                    # the kinds cesx_mh_run_map has a kernel for
 
@@ -336,6 +337,7 @@ def load_library(path=None):
     lib.cesx_mh_hmc_run_map.argtypes = [vp, u64, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.cesx_mh_adapt_set.argtypes = [vp, i32, C.c_double, C.c_double, C.c_double]
     lib.cesx_mh_adapt_read.argtypes = [vp, dp, C.POINTER(C.c_int32), dp]
+    lib.cesx_mh_grad_source.argtypes = [vp, i32]
     lib.cesx_chain_summary_begin.argtypes = [vp, i32, vp]
     lib.cesx_chain_summary_add.argtypes = [vp, vp, i32, vp]
     lib.cesx_chain_summary_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1588,6 +1590,18 @@ class Engine:
         the next ``mh_set_proposal`` the ``mh_hmc_*`` / ``gp_hmc_*`` steps run at e S and every accept updates e on the device."""
         with torch.cuda.device(self.device):
             self._check(self.lib.cesx_mh_adapt_set(self._h, int(n_steps), float(target), float(gain), float(kappa)))
+
+    def mh_grad_source(self, source):
+        """Where ``mh_langevin_start`` / ``_accept`` and ``mh_hmc_leap`` / ``_accept`` take the data term of grad phi from
+        (cesx_mh_grad_source): ``'jacobian'`` -- their ``DG`` is the (n_obs, p, J) image, the default after every
+        ``mh_set_proposal`` -- or ``'ready'`` -- ``DG`` is the (p, J) float64 block d of ``darcy_grad`` at the same states."""
+        if source not in GRAD_SOURCES:
+            raise ValueError("mh_grad_source: %r is neither 'jacobian' nor 'ready'" % (source,))
+        with torch.cuda.device(self.device):
+            rc = self.lib.cesx_mh_grad_source(self._h, GRAD_SOURCES[source])
+            if rc == EUNSUPPORTED:            # (p > 256, not the reference's missing LM_procedure of _check)
+                raise CesxError(rc, self.lib.cesx_last_error(self._h).decode())
+            self._check(rc)
 
     def mh_adapt_read(self):
         """``dict(multiplier, steps, history (steps, 2))`` of the adaptation phase: the averaged multiplier, the steps made and

@@ -109,7 +109,14 @@ Build-only extras of ``model_mh`` and ``gp_mh`` (not in the reference):
                          ``cesx_mh_langevin_lineal_*`` -- the gradient on the update kernels from images the engine forms
                          once (``model.langevin_device``), z = xi - g / 2 and the random walk's triangular launch for the
                          proposal, and one accept kernel (kernels_lvlin.hip) -- with no Jacobian image and no fused kernel
-                         (``fused=True`` raises).  A model without a Jacobian (a plain ``lineal`` / ``lineal_log``, Darcy,
+                         (``fused=True`` raises).  The Darcy models take it after ``model.enable_gradient()`` (``darcy.model`` /
+                         ``model_trunc``, the resident solver): with ``chains=M`` a state costs ONE adjoint launch
+                         (``model.gradient_device`` -- ``cesx_darcy_grad``: G, phi_d and d = d phi_d / du) and the step is
+                         ``cesx_mh_langevin_*`` / ``cesx_mh_hmc_*`` under ``cesx_mh_grad_source(READY)``, which take d where the
+                         closed-form maps hand over an (n_obs, p, M) Jacobian image (kernels_darcy_chain.hip: one wave per
+                         chain); no fused kernel (``fused=True`` raises); a start state whose solve fails raises
+                         ``ValueError``, a proposal or a leapfrog position whose solve fails is rejected.  A model without a
+                         Jacobian (a plain ``lineal`` / ``lineal_log`` / Darcy model,
                          every 'pde' model) and ``flag_noise=True`` raise ``ValueError`` before an engine is created.
   kwarg ``update='hmc'``  model_mh and gp_mh, on the host (one chain) and with ``chains=M``: Hamiltonian Monte Carlo with kwarg
                          ``leapfrog=L`` (an integer in [1, 64], default 4) leapfrog steps per accept test, on the pieces of
@@ -893,9 +900,10 @@ class MCMC(object):
         ``update='langevin'`` (build-only): the Metropolis-adjusted Langevin step for a model that offers its gradient --
         ``elliptic`` and ``banana`` (``jacobian`` / ``jacobian_device``), ``lineal`` and ``lineal_log`` after
         ``enable_gradient()`` (``jacobian`` / ``langevin_device``: the adjoint launches of cesx_mh_langevin_lineal_*, at any
-        p), and on the host path ``darcy.model`` / ``model_trunc`` after ``enable_gradient()`` (``jacobian``: one sparse LU and
-        n_obs adjoint solves per state; with ``chains=M`` they are refused -- ``gradient_device`` evaluates the gradient of
-        the misfit on the device, but no sampler step takes it yet); module docstring.
+        p), and ``darcy.model`` / ``model_trunc`` after ``enable_gradient()`` (on the host ``jacobian``: one sparse LU and
+        n_obs adjoint solves per state; with ``chains=M`` ``gradient_device``: one adjoint launch per position, and the
+        Langevin / leapfrog entry points under ``cesx_mh_grad_source(READY)`` -- ``update='hmc'``, ``leapfrog=``, ``adapt=``,
+        ``summary=`` and the rest as for ``elliptic``, no fused kernel); module docstring.
         """
         leapfrog = self._hmc_leapfrog(kwargs)             # build-only; refused before any engine is created
         if kwargs.get("update", None) == "langevin":
@@ -971,12 +979,13 @@ class MCMC(object):
     def _model_langevin_refusals(model, prior, device):
         """What ``model_mh(update='langevin')`` cannot do, host and device alike: every refusal is a ValueError with the reason."""
         need = "jacobian_device" if device else "jacobian"
-        has = hasattr(model, need) or (device and hasattr(model, "langevin_device"))      # (langevin_device: the adjoint launch of the linear maps)
+        # (langevin_device: the adjoint launches of the linear maps; gradient_device: the adjoint launch of the Darcy models)
+        has = hasattr(model, need) or (device and (hasattr(model, "langevin_device") or hasattr(model, "gradient_device")))
         if getattr(model, "type", None) == "pde" or not hasattr(model, "jacobian") or not has:
             raise ValueError("update='langevin' needs the gradient of phi, and %r offers no Jacobian (model.%s; "
                              "ces_amd.utils.elliptic and banana do, lineal and lineal_log after enable_gradient(): their "
-                             "gradient is an A^T product, the Darcy models after enable_gradient() on the host path: chains=M has no "
-                             "sampler step that takes their adjoint launch); the Lorenz models have no adjoint; "
+                             "gradient is an A^T product, the Darcy models after enable_gradient(): chains=M takes their "
+                             "adjoint launch, model.gradient_device); the Lorenz models have no adjoint; "
                              "gp_mh(update='langevin') differentiates the emulator instead" % (model, need))
         if getattr(model, "flag_noise", False):
             raise ValueError("update='langevin': a noisy map (flag_noise=True) has no gradient of phi")
@@ -1483,7 +1492,57 @@ class MCMC(object):
                 eng.mh_hmc_lineal_accept(step, U, Q, GQ, logu=logu)
             return hm_start, hm_accept, None, hm_begin
 
-        lineal_grad = langevin and not hasattr(model, "jacobian_device")      # (a linear map: model_mh has checked langevin_device)
+        def darcy_hooks(eng, M):
+            # what bind_langevin_darcy and bind_hmc_darcy share: the three outputs of the adjoint launch (G, phi_d, d), fp64, the
+            # source of the gradient -- set behind every mh_set_proposal, which returns it to the Jacobian image -- and the start
+            import torch
+            out = (torch.empty((n, M), dtype=torch.float64, device=eng.device),
+                   torch.empty((M,), dtype=torch.float64, device=eng.device),
+                   torch.empty((p, M), dtype=torch.float64, device=eng.device))
+            model.ensure_installed(eng)
+            eng.mh_grad_source("ready")
+
+            def grad(X):                                  # (G, d) at X: a state whose solve failed has NaN in both
+                model.gradient_device(eng, X, out=out)
+                return out[0], out[2]
+
+            def start(U):
+                eng.mh_langevin_start(U, *grad(U))
+                bad = torch.nonzero(torch.isnan(out[1])).reshape(-1)          # the one read of a start: phi_d is NaN where the solve failed
+                if bad.numel():
+                    raise ValueError("chains=: the forward model failed at the start state of chain %d (its system is "
+                                     "singular or left fp64's range: no phi and no gradient to compare a proposal with)" % int(bad[0]))
+            return grad, start
+
+        def bind_langevin_darcy(eng, M):
+            # bind_langevin with the adjoint launch where it forms the Jacobian image (cesx_darcy_grad; cesx_mh_grad_source)
+            grad, lv_start = darcy_hooks(eng, M)
+
+            def lv_propose(step, U, xi, P):
+                eng.mh_langevin_propose(step, U, xi=xi, out=P)
+
+            def lv_accept(step, U, P, logu):
+                eng.mh_langevin_accept(step, U, P, *grad(P), logu=logu)
+            return lv_start, lv_accept, None, lv_propose
+
+        def bind_hmc_darcy(eng, M, leapfrog=leapfrog, fused=False):
+            # bind_hmc likewise: per position one adjoint launch at Q, then the kick.  No fused run (model_mh has refused fused=True)
+            grad, hm_start = darcy_hooks(eng, M)
+
+            def hm_begin(step, U, xi, Q):
+                eng.mh_hmc_begin(step, U, xi=xi, out=Q)
+
+            def hm_accept(step, U, Q, logu):
+                for _ in range(leapfrog - 1):
+                    eng.mh_hmc_leap(Q, *grad(Q))
+                eng.mh_hmc_accept(step, U, Q, *grad(Q), logu=logu)
+            return hm_start, hm_accept, None, hm_begin
+
+        darcy_grad = langevin and hasattr(model, "gradient_device") and not hasattr(model, "jacobian_device")
+        lineal_grad = langevin and not darcy_grad and not hasattr(model, "jacobian_device")      # (a linear map: model_mh has checked langevin_device)
+        if darcy_grad:
+            bind_langevin = bind_langevin_darcy
+            bind_hmc = bind_hmc_darcy
         if lineal_grad:
             bind_langevin = bind_langevin_lineal
             bind_hmc = bind_hmc_lineal

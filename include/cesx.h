@@ -781,6 +781,28 @@ int cesx_mh_hmc_lineal_accept(cesx_handle h, uint64_t step_index, void* U_dev, c
 #define CESX_ADAPT_STEPS_MAX 65536
 int cesx_mh_adapt_set(cesx_handle h, int n_steps, double target, double gain, double kappa);
 int cesx_mh_adapt_read(cesx_handle h, double* multiplier, int* steps_done, double* history_host);
+/* Where cesx_mh_langevin_start / _accept and cesx_mh_hmc_leap / _accept take the data term of grad phi from -- an install like
+   cesx_mh_adapt_set: no chains, no launch.  For a map whose gradient comes from ONE adjoint solve per state (cesx_darcy_grad) the
+   [n][p][J] Jacobian image these calls read is what the adjoint exists to avoid.
+       CESX_MH_GRAD_JACOBIAN   (default) DG_dev is the [n_obs][p][J_local] image: everything above, untouched
+       CESX_MH_GRAD_READY      DG_dev is a [p][J_local] fp64 block d = d phi_d / du, the data term of grad phi READY-MADE (dphi_dev
+                               of cesx_darcy_grad at the same states).  G_dev is still [n_obs][J_local] and phi is still summed
+                               from it -- the data sum and the prior of cesx_mh_langevin_start, term for term in their order --,
+                                   grad phi = d + Sigma_prior^{-1} (u - mu),   g = S^T grad phi
+                               and the kick, the norms, the test, the NaN rule and the masked copies are those of the calls above
+                               (the ADAPT forms on an armed handle).  A state whose solve failed has NaN in G_dev and d: rejected
+                               like any NaN.  Return codes, the call order, the counters, cesx_mh_stats, cesx_mh_phi and
+                               cesx_mh_adapt_* are unchanged; cesx_mh_langevin_propose and cesx_mh_hmc_begin read g alone and are
+                               the same launches under either source.  The kernels (kernels_darcy_chain.hip) give a chain one
+                               wave, the rows of its triangular products across the lanes, every sum in one fixed order: runs
+                               are bit-identical, and leapfrog = 1 is the Langevin step.  p <= 256.
+   The source returns to CESX_MH_GRAD_JACOBIAN on every cesx_mh_set_proposal and cesx_set_problem: a sequence that never makes
+   this call never sees READY.  The *_run_map, *_lineal_* and cesx_gp_* entry points ignore it.
+   CESX_EINVAL: any other source.  CESX_ESTATE: no proposal of kind CESX_MH_LANGEVIN.  CESX_EUNSUPPORTED: READY on an engine
+   with p > 256.  It launches nothing and touches neither the chains' phi, g nor the counters. */
+#define CESX_MH_GRAD_JACOBIAN 0
+#define CESX_MH_GRAD_READY    1
+int cesx_mh_grad_source(cesx_handle h, int source);
 /* Call order across the families.  The sections above state each family's sequencing against itself; where two of them meet on
    one handle (tests/sampler_reuse_cases.py holds the whole table, state by entry point):
      - One start serves both random-walk families: cesx_mh_accept and cesx_mh_run_map follow a cesx_gp_start, cesx_gp_accept and
